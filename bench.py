@@ -715,6 +715,41 @@ def same_numbers_as_one_gpu(gsi, device, n, Ns, decay, K, p, q, world, seed, Sv,
             "what": "rank 0 re-runs the step on one GPU (no communicator) from the same samples and the stacked Omega blocks"}
 
 
+DUMP_BYTES = 48 * 10**6                  # what --dump-outputs may write in all (the files' headers aside): well under 64 MB
+
+
+def dump_row_sample(n, l):
+    """The rows of Z that --dump-outputs keeps: all of them when they fit, else a fixed sample (seed 0, ascending) sized so
+    that Z's rows and S stay under DUMP_BYTES -- the same rows in every run with the same arguments."""
+    import numpy as np
+    m = max(min(n, (DUMP_BYTES - 8 * l) // (8 * l)), 1)
+    if m >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+
+
+def gather_rows(ctx, Zloc, n, rows):
+    """Z[rows] of an n-row Z that is row-sharded over the ranks (Zloc: this rank's shard), on every rank (collective)."""
+    import numpy as np
+    row0, nloc = ctx.shard(n)
+    world = ctx.rank()[1]
+    if world == 1:
+        return Zloc[rows]
+    mine = (rows >= row0) & (rows < row0 + nloc)
+    part = np.zeros((rows.size, Zloc.shape[1]))
+    part[mine] = Zloc[rows[mine] - row0]
+    allp = ctx.host_allgather(part.ravel()).reshape(world, rows.size, Zloc.shape[1])
+    return allp[rows // -(-n // world), np.arange(rows.size)]
+
+
+def write_outputs(dirname, arrays):
+    """arrays -> dirname/<name>.npy (float64, C order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n):
     """`python3 bench.py --gpus N` without a launcher: THIS process becomes the launcher.  It never touches the GPU (no HIP
     call, the product library is not even loaded here) -- N fresh children are started with RANK / LOCAL_RANK / WORLD_SIZE
@@ -834,7 +869,13 @@ def main():
                     help="skip the host-boundary block (host-pointer entry points at C1, C2 -- a 34 GB host matrix -- and the headline)")
     ap.add_argument("--no-implicit", action="store_true",
                     help="N > 1: skip the one row-sharded step of the implicit 10^6 x 10^6 covariance")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): "
+                         "S.npy (the l singular values) and Z_rows.npy (Z's rows, or a fixed seeded sample of them -- "
+                         "bench.dump_row_sample -- that keeps the files under 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))            # the launcher: no GPU call before or after this line
@@ -902,7 +943,7 @@ def main():
     # are from it -- when the whole problem fits one GPU comfortably (n <= 2e6: 16 GB of samples, 5 GB panels)
     vs_one_gpu = world > 1 and rank == 0 and n <= 2000000 and not args.no_full_parity
     want_host = full_parity or (world == 1 and not use_dist and not args.no_boundary)     # the boundary block re-uploads the samples
-    keep = {} if (want_host or vs_one_gpu) else None
+    keep = {} if (want_host or vs_one_gpu or args.dump_outputs) else None
     elapsed, phases, Sv = run_steps(gsi, ctx, op, n, K, p, q, args.steps, args.warmup, barrier, keep=keep, rows=use_dist)
     elapsed = max_over_ranks(elapsed)
     pinfo = run_steps.last_path_info                     # of exactly the timed steps
@@ -925,17 +966,27 @@ def main():
     dev_bytes = ctx.device_bytes()
     host = None
     Z0_rows = None
+    Zh = keep["Z"].to_host() if keep is not None else None     # after the timed region: the last timed step's Z (this rank's rows)
+    if args.dump_outputs:
+        dumped = {"S": Sv, "Z_rows": gather_rows(ctx, Zh, n, dump_row_sample(n, l))}
+        if rank == 0:
+            write_outputs(args.dump_outputs, dumped)
+        del dumped
     if vs_one_gpu:
-        Z0_rows = keep["Z"].to_host()
+        Z0_rows = Zh
         keep["Omega"].close()
         keep["Z"].close()
     if want_host:                        # after the timed region: what the oracle / the boundary block need, off the device
         try:
-            host = {"samples": gsi.device_samples(op, Ns), "Omega": keep["Omega"].to_host(), "Z": keep["Z"].to_host()}
+            host = {"samples": gsi.device_samples(op, Ns), "Omega": keep["Omega"].to_host(), "Z": Zh}
         except Exception:                # noqa: BLE001 -- not enough host memory: the n = 16384 sample is what remains
             host = None
         keep["Omega"].close()
         keep["Z"].close()
+    if keep is not None:
+        keep["Omega"].close()
+        keep["Z"].close()
+    del Zh
     op.close()
 
     ms_per_step = 1e3 * elapsed / args.steps
