@@ -548,17 +548,30 @@ __global__ void cq_identity_kernel(double* __restrict__ X, int l) {
 // the rounding error of the Gram matrix; here s = 4 l sqrt(m) u trace(G) (the probabilistic size of that error,
 // u = 2^-53, trace(G) = |Y|_F^2), which extends the reach from cond ~1e11 to ~1e13: if it is ever too small the
 // Cholesky pivots flag it and the caller falls back -- a wrong guess costs time, never accuracy.
+// Floor: 4x the pivot threshold of the Cholesky that follows (tiny = 16 l eps max_i G_ii, cq_diagmax_kernel /
+// cq_chol_inv_kernel), so that the shifted pivots (>= s in exact arithmetic) clear it.  Without it a short panel
+// with one dominant column (sqrt(m) trace(G) < 8 max_i G_ii: m < 64 at most) was flagged by its own shift and went
+// to Householder at any condition number (10 x 2 and 40 x 7 at cond 1e8).  The floor is below the paper's s for
+// m >= 12, and below the probabilistic s for m >= 1024, where nothing changes.
 __global__ __launch_bounds__(256) void cq_shift_kernel(double* __restrict__ G, int l, double m) {
-  __shared__ double s[256];
-  double tr = 0.0;
-  for (int i = threadIdx.x; i < l; i += 256) tr += G[i + (int64_t)i * l];
+  __shared__ double s[256], mx[256];
+  double tr = 0.0, dm = 0.0;
+  for (int i = threadIdx.x; i < l; i += 256) {
+    const double g = G[i + (int64_t)i * l];
+    tr += g;
+    dm = fmax(dm, g);
+  }
   s[threadIdx.x] = tr;
+  mx[threadIdx.x] = dm;
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
+    if (threadIdx.x < st) {
+      s[threadIdx.x] += s[threadIdx.x + st];
+      mx[threadIdx.x] = fmax(mx[threadIdx.x], mx[threadIdx.x + st]);
+    }
     __syncthreads();
   }
-  const double shift = 4.0 * (double)l * sqrt(m) * (0.5 * DBL_EPSILON) * s[0];
+  const double shift = fmax(4.0 * (double)l * sqrt(m) * (0.5 * DBL_EPSILON) * s[0], 4.0 * 16.0 * (double)l * DBL_EPSILON * mx[0]);
   for (int i = threadIdx.x; i < l; i += 256) G[i + (int64_t)i * l] += shift;
 }
 

@@ -112,7 +112,12 @@ def test_lu_singular_raises(gsi, ctx):
 def test_qr_thinQ(gsi, ctx, m, l):
     rng = np.random.default_rng(3 * m + l)
     Y = rng.standard_normal((m, l)) @ np.diag(np.logspace(0, -8, l))
+    before = ctx.counters()
     Q, R = gsi.qr_thinQ(Y, return_R=True)
+    after = ctx.counters()
+    # full rank, cond ~ 1e8: one of the two Cholesky tiers, never Householder
+    assert after["householder"] - before["householder"] == 0, (before, after)
+    assert (after["cholqr2"] - before["cholqr2"]) + (after["scholqr3"] - before["scholqr3"]) == 1, (before, after)
     assert np.abs(Q.T @ Q - np.eye(l)).max() < 1e-13
     assert np.abs(Q @ R - Y).max() < 1e-13 * np.abs(Y).max() * l
     assert np.abs(np.tril(R, -1)).max() == 0.0
@@ -548,7 +553,18 @@ def test_randsvd_wide_sketch(gsi, ctx, n, K, p, q):
     B = rng.standard_normal((n, n)) / np.sqrt(n)
     A = B @ np.diag(np.logspace(0, -3, n)) @ B.T          # SPD, slowly decaying spectrum
     Omega = rng.standard_normal((n, K + p))
-    Z, S = gsi.randsvd(A, K, p, q, Omega=Omega, return_S=True)
+    # Own context: in the shared one, an earlier panel of the same height (1500 rows) that needed the shifted tier
+    # makes the next eight factorizations of that height start at the second tier (hip_backend.hip, skip_tier1_);
+    # in the whole -m gpu run this call then ran shifted CholeskyQR3 twice and CholeskyQR2 never.
+    c = gsi.Context(0)
+    try:
+        before = c.counters()
+        Z, S = gsi.randsvd(A, K, p, q, Omega=Omega, return_S=True, ctx=c)
+        after = c.counters()
+    finally:
+        c.close()
+    # the first tier ran (l = 320: fused Cholesky; l = 512: the blocked one, cholqr.hip)
+    assert after["cholqr2"] - before["cholqr2"] >= 1, (before, after)
     Zref, Sref, _ = orc.randsvd_full(A, K, p, q, Omega)
     assert rel_sv_err(S, Sref, K) < 1e-9
     assert np.linalg.norm(Z @ Z.T - Zref @ Zref.T) < 1e-8 * np.linalg.norm(Zref @ Zref.T)
@@ -1118,9 +1134,9 @@ print("rccl-sharded-lu-ok")
 #      values.  Separate processes: the switches are read once per process. --------------------------------------------
 @pytest.mark.gpu
 def test_headline_size_properties(gsi):
-    import os, subprocess, sys, tempfile
+    import json, os, subprocess, sys, tempfile
     code = r'''
-import os, sys, numpy as np
+import json, os, sys, numpy as np
 import gsi_amd as gsi
 ctx = gsi.Context(0)
 n, Ns, K, p, q = 1000000, 1024, 256, 64, 2
@@ -1145,6 +1161,7 @@ if os.environ.get("GSI_TEST_FULL"):
     assert np.abs(T - np.diag(Sh[:j])).max() < 1e-6 * Sh[0]             # V'AV = diag(S) on the leading vectors (q = 2)
     assert np.linalg.norm(AV - V[:, :j] * Sh[:j]) < 1e-5 * Sh[0] * np.sqrt(j)
 np.save(sys.argv[1], Sh)
+print("counters " + json.dumps(ctx.counters()))
 print("headline-ok")
 '''
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1156,6 +1173,9 @@ print("headline-ok")
             path = os.path.join(td, tag + ".npy")
             r = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True, timeout=900, env=env, cwd=here)
             assert r.returncode == 0 and "headline-ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+            # both kernel families really ran CholeskyQR2 (a Householder fall-back would compare Householder with itself)
+            cnt = json.loads([s for s in r.stdout.splitlines() if s.startswith("counters ")][-1][len("counters "):])
+            assert cnt["cholqr2"] > 0 and cnt["householder"] == 0, (tag, cnt)
             out[tag] = np.load(path)
     S1, S2 = out["dedicated"], out["general"]
     assert np.abs(S1 - S2).max() < 1e-11 * S1[0], np.abs(S1 - S2).max() / S1[0]
