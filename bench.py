@@ -17,6 +17,12 @@ no torch, no second communication layer.  The N > 1 line also carries which LU f
 self-test mask of the in-kernel pivot exchange, collectives per step, ranks seen) and ONE row-sharded step of the
 n = 10^6 implicit dense covariance -- the operator north_star's ">= 6x at 8 GPUs" is about.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline figure needs and nothing else: it sets up, warms
+up, times the K steps, writes --dump-outputs if asked and prints the line, with the figures derived from the timed steps
+themselves (roofline, phases, path counters).  Everything that takes runs of its own -- the secondary workloads, the host
+boundary block, the CPU oracle (cpu_baseline, parity at the sample and at the full size), and for N > 1 the skew-split step,
+the one-GPU re-run and the row-sharded implicit step -- runs only with --full; there the --no-* options leave parts out.
+
 metric value = algorithmic GB/s of the whole job: [(2q+2) products x (16 n N_s + 16 n l) + (2q + 2) panel
                factorizations x 16 n l] bytes / step time        
 roofline     = the dominant kernel, the fp64 MFMA contraction gemm_f64_kernel: 2 n N_s l flop per launch over its
@@ -847,7 +853,7 @@ class Rendezvous:
             shutil.rmtree(self.dir, ignore_errors=True)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -859,6 +865,10 @@ def main():
     ap.add_argument("--p", type=int, default=64)
     ap.add_argument("--q", type=int, default=2)
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: secondary workloads, the host-boundary "
+                         "block, the CPU oracle and parity legs, and for N > 1 the skew-split step, the one-GPU re-run and "
+                         "the row-sharded implicit step (the --no-* options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the C2 dense and the implicit 10^6 steps")
     ap.add_argument("--no-fft-512cube", action="store_true", help="skip the one 512^3 FFT-operator step (~230 GB of HBM)")
@@ -873,10 +883,17 @@ def main():
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): "
                          "S.npy (the l singular values) and Z_rows.npy (Z's rows, or a fixed seeded sample of them -- "
                          "bench.dump_row_sample -- that keeps the files under 64 MB)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: the headline and nothing that needs runs of its own -- every part --full would add is left out
+        args.no_cpu_baseline = args.no_secondary = args.no_boundary = args.no_full_parity = args.no_implicit = True
+    return args
 
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))            # the launcher: no GPU call before or after this line
     # stdout carries exactly ONE line (the JSON result of rank 0): libraries that chat on fd 1 (RCCL's version banner)
@@ -949,11 +966,12 @@ def main():
     pinfo = run_steps.last_path_info                     # of exactly the timed steps
     ranks_phases = skew_split = None
     if use_dist:
-        # the same phases per rank (max / min), and ONE more step with skew barriers (profile level 2): what is waiting for the
-        # slowest rank and what is work -- outside the timed region, the barriers are extra collectives
+        # the same phases per rank (max / min), and with --full ONE more step with skew barriers (profile level 2): what is
+        # waiting for the slowest rank and what is work -- outside the timed region, the barriers are extra collectives
         ranks_phases = phases_over_ranks(ctx, phases, args.steps)
-        _, ph2, _ = run_steps(gsi, ctx, op, n, K, p, q, 1, 0, barrier, rows=True, profile=2)
-        skew_split = phases_over_ranks(ctx, ph2, 1)
+        if args.full:
+            _, ph2, _ = run_steps(gsi, ctx, op, n, K, p, q, 1, 0, barrier, rows=True, profile=2)
+            skew_split = phases_over_ranks(ctx, ph2, 1)
     counters = ctx.counters()
     counters.update({"lu_form": pinfo["lu_form"], "lu_forms_run_in_timed_steps": pinfo["lu_forms_run"],
                      "lu_selftest_mask": pinfo["lu_selftest_mask"],
@@ -1052,7 +1070,7 @@ def main():
             "metric": "randSVD GB/s + top-k singular-value rel-err, n=1e6 rank=256", "value": value, "unit": "GB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": f"n={n} grid points, LowRankCovMatrix over N_s={Ns} synthetic sample fields "
                                    f"({8.0 * n * Ns / 1e9:.1f} GB in HBM), rank K={K}, p={p} (l={l}), q={q} "
                                    f"(BASELINE.json metric config; SURVEY.md 8d C4-ii)"

@@ -1,8 +1,9 @@
 """The driver's multi-GPU command on the one-GPU box: `GSI_BENCH_ONE_GPU=1 python3 bench.py --gpus 2
---steps 3` -- bench.py starts its own two rank processes (both on GPU 0, joined by the library's shared-memory communicator;
+--steps 3 --full` -- bench.py starts its own two rank processes (both on GPU 0, joined by the library's shared-memory communicator;
 RCCL refuses two ranks on one device), and the line must say what ran: n_gpus, the LU form and the self-test mask of the
 in-kernel pivot exchange, collectives per step, the ranks the communicator joined, the N-rank numbers against the one-GPU
-path, and ONE row-sharded step of the implicit 10^6 x 10^6 covariance (the operator north_star's >= 6x names)."""
+path, and ONE row-sharded step of the implicit 10^6 x 10^6 covariance (the operator north_star's >= 6x names): the last two
+are runs of their own, so they come with --full."""
 import json
 import os
 import subprocess
@@ -20,7 +21,7 @@ def test_bench_gpus_2_starts_by_itself_on_one_gpu(gsi):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GSI_BENCH_RDV"):
         env.pop(k, None)
     env["GSI_BENCH_ONE_GPU"] = "1"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--full"], capture_output=True, text=True,
                        timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

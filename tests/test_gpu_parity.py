@@ -1185,7 +1185,7 @@ print("headline-ok")
 #      on the operator the HIP path ran on (samples, Omega downloaded), products in GEMM form.  Runs by default (VERDICT r4
 #      item 3: the metric's own parity belongs in the driver-run suite; ~130 s of host LAPACK and ~40 GB of host memory on the
 #      GPU box, the suite stays under its 900 s limit); GSI_SKIP_HEADLINE_PARITY=1 opts out, as for the C2 test.  bench.py runs
-#      the same comparison in every default run and records it in the driver's line. -----------------------------------
+#      the same comparison in every --full run and records it in that line. -----------------------------------
 @pytest.mark.gpu
 @pytest.mark.skipif(bool(__import__("os").environ.get("GSI_SKIP_HEADLINE_PARITY")),
                     reason="opted out (GSI_SKIP_HEADLINE_PARITY=1): ~2 minutes of host LAPACK at n = 1e6")

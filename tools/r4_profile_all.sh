@@ -1,7 +1,8 @@
 #!/bin/bash
 # the round-4 profile set -- the driver's command, its kernel trace, its PMC traffic passes; FFT kernel stats + PMC
 R=$GRAFT_REPO_ROOT; cd $R
-timeout -k 10 700 python bench.py > gpurun_out/r04_bench_line.json 2> gpurun_out/r04_bench_line.err; echo bench_rc=$?
+LINE=${1:?usage: bash tools/r4_profile_all.sh <path of the full bench line, without .json>}
+timeout -k 10 700 python bench.py --full > "$LINE.json" 2> "$LINE.err"; echo bench_rc=$?
 bash tools/profile_bench.sh r04 > /dev/null 2>&1 || exit 1
 cp gpurun_out/prof_r04_kernel_stats.csv gpurun_out/r04_bench_kernel_stats.csv; cp gpurun_out/prof_r04_dispatch_summary.json gpurun_out/r04_bench_dispatch_summary.json
 bash tools/pmc_bench_traffic.sh > gpurun_out/r04_pmc_bench_traffic.log 2>&1; tail -3 gpurun_out/r04_pmc_bench_traffic.log
@@ -27,9 +28,9 @@ find $R/gpurun_out/prof_pc -name "*kernel_stats.csv" -exec cp {} $R/gpurun_out/r
 cd $R
 rm -rf gpurun_out/prof_pc
 rm -rf gpurun_out/prof_fft_r04 gpurun_out/prof_fft3_r04 gpurun_out/prof_fft512_r04 gpurun_out/pmc_fft_r04_*_[1-4]
-python - <<'PY'
-import json
-d=json.load(open("gpurun_out/r04_bench_line.json"))
+python - "$LINE.json" <<'PY'
+import json, sys
+d=json.load(open(sys.argv[1]))
 print(round(d["ms_per_step"],2), round(d["value"],1), round(d["roofline"]["frac"],3), {k:round(v,2) for k,v in d["phases_ms_per_step"].items()})
 for k,v in d["secondary"].items(): print(k, {a:(round(b,4) if isinstance(b,float) else b) for a,b in v.items() if not isinstance(b,(dict,str))})
 PY
