@@ -172,6 +172,23 @@ class Backend {
     (void)Xr;
     return false;
   }
+  // ---- randsvd's sample-space tail for a LowRankCovMatrix A = S S' c (one rank) ----
+  // G (N x N, ld N) <- S'S for the samples S (n x N, ld), both triangles, in a fixed summation order.  false: not available.
+  virtual bool sample_gram(const double* S, int64_t ld, int64_t n, int64_t N, double* G) {
+    (void)S; (void)ld; (void)n; (void)N; (void)G;
+    return false;
+  }
+  // Everything randsvd computes after its last panel LU L, in the coordinates of range(S): given T = S'L (N x l, ld N) and
+  // G = S'S, Y = A L = S (c T) is factored by CholeskyQR2 on coefficient matrices (the Gram matrix of S M is M'(G M)), W = A'Q
+  // likewise, and svd(B) comes from the l x l factors; Z (n x l, ld ldz) = S C with C = N_s x K coefficients, its last l - K
+  // columns zero, and Sv (l) the singular values.  false (declines, Z and Sv untouched): a Cholesky broke down, a second
+  // round's Gram matrix was not near the identity, l > N - 1 (centred samples span N - 1 dimensions), or a shape it does not
+  // cover; the caller then forms Y = S (c T) and runs the ordinary path.
+  virtual bool lowrank_tail(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
+                            int64_t K, double c, double* Z, int64_t ldz, double* Sv) {
+    (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)l; (void)K; (void)c; (void)Z; (void)ldz; (void)Sv;
+    return false;
+  }
   // G (l x l, ld l), columns orthogonalised in place by one-sided Jacobi; on return
   // U (l x l) = left singular vectors sorted by descending S, S (l) singular values.
   virtual void svd_small(double* G, int64_t l, double* U, double* S) = 0;

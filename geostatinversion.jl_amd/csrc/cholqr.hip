@@ -681,6 +681,32 @@ void cholqr2_R(hipStream_t st, int64_t l64, double* small, double* R) {
 }
 const double* cholqr2_X2(const double* small, int64_t l) { return small + 5 * (size_t)l * (size_t)l; }
 
+// ---- the sample-space tail of randsvd (hip_backend.hip:lowrank_tail): Gram matrices formed from coefficients ----
+// G (l x l) <- symmetric: the strictly lower triangle mirrors the upper one
+void mirror_upper(hipStream_t st, double* G, int64_t l) {
+  hipLaunchKernelGGL(cq_mirror_upper_kernel, dim3(64), dim3(256), 0, st, G, (int)l);
+}
+// One CholeskyQR round on a Gram matrix the caller formed (M'(G M) for the panel S M): made symmetric from its upper triangle,
+// the orthogonality check of a second round (check: flag |= 2 when max |Gm - I| > 0.1, as cq_round), then R = chol(Gm) in
+// place and X = R^-1 by the fused kernel (flag |= 1 on a negligible pivot).  false: l beyond the fused kernel (nothing queued).
+bool cq_gram_round(hipStream_t st, double* Gm, int64_t l64, double* X, bool check, int32_t* flag) {
+  const int l = (int)l64;
+  if (l < 1 || l > CQF_MAXL) return false;
+  hipLaunchKernelGGL(cq_mirror_upper_kernel, dim3(64), dim3(256), 0, st, Gm, l);
+  if (check)
+    hipLaunchKernelGGL(cq_orth_check_kernel, dim3(grid_for((int64_t)l * l, 64)), dim3(256), 0, st, Gm, l, 0.1, flag);
+  static std::atomic<uint64_t> attr_mask{0};
+  if (first_use_on_this_device(attr_mask))
+    (void)hipFuncSetAttribute((const void*)cq_chol_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CQF_LDS_BYTES);
+  hipLaunchKernelGGL(cq_chol_inv_kernel, dim3(1), dim3(CQF_THREADS), CQF_LDS_BYTES, st, Gm, l, X, flag,
+                     (unsigned long long*)nullptr);
+  return true;
+}
+// R (l x l) <- R2 R1, both upper triangular
+void tri_product(hipStream_t st, const double* R2, const double* R1, int64_t l, double* R) {
+  hipLaunchKernelGGL(cq_triprod_kernel, dim3(grid_for(l * l, 256)), dim3(256), 0, st, R2, R1, (int)l, R);
+}
+
 // Shifted CholeskyQR3, the tier between CholeskyQR2 and Householder: panels with cond up to ~1e15 (sketches of
 // fast-decaying covariance spectra after the power iterations).  Y -> T (shifted round) -> S (plain round); third
 // Gram matrix, its orthogonality check, R3 and R3^-1.  Y is NOT modified.  Afterwards flag != 0 means "not trusted".

@@ -955,6 +955,92 @@ class HipBackend : public Backend {
     phase_end(PH_SMALL_GEMM);
     return true;
   }
+  // G = S'S of a LowRankCovMatrix's samples: the upper tiles of the general contraction (fixed K split: the same bits on
+  // every call), mirrored.  2 n N^2 flop less the skipped lower tiles, once per operator (pipeline.cpp caches it).
+  bool sample_gram(const double* S, int64_t ld, int64_t n, int64_t N, double* G) override {
+    bind();
+    if (n < 1 || N < 1) return false;
+    double* ws = gemm_ws(hipk::gemm_syrk_workspace_doubles(N, n) + 64);
+    hipk::gemm_f64_syrk_upper(st_, N, n, S, ld, G, N, ws);
+    hipk::mirror_upper(st_, G, N);
+    check_launch("sample_gram");
+    return true;
+  }
+  // randsvd after its last panel LU, in sample space (Backend::lowrank_tail).  With A = c S S',
+  // T = S'L and G = S'S every tall panel of the deferred path is S times an N x l coefficient matrix:
+  //   Y = S A0, A0 = c T;   CholeskyQR2 of Y: Gram A0'(G A0) -> R1, X1;  A1 = A0 X1 (Q1 = S A1);  Gram A1'(G A1) -> R2, X2
+  //   W = A'Q1 = S B0, B0 = c G A1;  CholeskyQR2 of W: B0'(G B0) -> RW1, XW1;  B1 = B0 XW1;  B1'(G B1) -> RW2, XW2
+  //   svd(RW2 RW1 X2) = U S V';  Z = S C,  C = B1 (XW2 U sqrt(S))[:, 0:K]
+  // -- the operations of qr_thinQ_deferred + op_mul_t + svd_tall_fused with the tall products replaced by N x l ones; one tall
+  // product (Z, K = N) is left.  Each Gram matrix is the exact one of its panel up to eps |M|^2 |G| (against eps |S M|^2 when
+  // the panel is formed): the second rounds' check catches a panel whose coefficients grew too large for that to hold.
+  bool lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
+                    int64_t K, double c, double* Z, int64_t ldz, double* Sv) override {
+    bind();
+    static const bool off = (getenv("GSI_NO_CHOLQR") != nullptr);
+    if (off || l < 1 || l > 384 || l > N - 1 || K < 1 || K > l || N > 4096 || n < 2 * l) return false;
+    const size_t Nl = ((size_t)N * l + 7) & ~(size_t)7, ll = ((size_t)l * l + 7) & ~(size_t)7;
+    Scratch buf(this, 3 * Nl + 12 * ll);
+    double* A0 = buf.p;                 // c T; then B0; then C
+    double* A1 = A0 + Nl;               // A0 X1; then B1
+    double* P = A1 + Nl;                // G times the current coefficients
+    double* Gr[4];                      // the four Gram matrices, each R in place afterwards
+    for (int i = 0; i < 4; ++i) Gr[i] = P + Nl + (size_t)i * ll;
+    double* X[4];                       // X1, X2, XW1, XW2
+    for (int i = 0; i < 4; ++i) X[i] = P + Nl + (size_t)(4 + i) * ll;
+    double* R = P + Nl + 8 * ll;
+    double* Rf = R + ll;
+    double* U = Rf + ll;
+    double* Mm = U + ll;
+    size_t gmax = hipk::gemm_workspace_doubles(N, l, N);
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, N));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, l));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, l));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, K, l));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(n, K, N));
+    double* ws = gemm_ws(gmax + 64);
+    // one round on the panel S M: P = G M, Gram = M'P, R = chol(Gram) in place, X = R^-1
+    auto round = [&](const double* M, int i, bool check) {
+      hipk::gemm_f64(st_, false, N, l, N, 1.0, G, N, M, N, 0.0, P, N, ws);
+      hipk::gemm_f64(st_, true, l, l, N, 1.0, M, N, P, N, 0.0, Gr[i], l, ws);
+      (void)hipk::cq_gram_round(st_, Gr[i], l, X[i], check, flags_ + 9);
+    };
+    int32_t f = 0;
+    phase_begin(PH_QR);
+    HIP_CHECK(hipMemsetAsync(flags_ + 9, 0, sizeof(int32_t), st_));
+    hipk::scal_copy(st_, (int64_t)N * l, c, T, A0);                                          // Y = S A0
+    round(A0, 0, false);
+    hipk::gemm_f64(st_, false, N, l, l, 1.0, A0, N, X[0], l, 0.0, A1, N, ws);               // Q1 = Y R1^-1 = S A1
+    round(A1, 1, true);                                                                       // X2 = R2^-1: Q = Q1 X2
+    hipk::scal_copy(st_, (int64_t)N * l, c, P, A0);                                          // W = A'Q1 = S (c G A1) = S B0
+    round(A0, 2, false);
+    hipk::gemm_f64(st_, false, N, l, l, 1.0, A0, N, X[2], l, 0.0, A1, N, ws);               // W RW1^-1 = S B1
+    round(A1, 3, true);
+    check_launch("lowrank_tail");
+    HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (f != 0) {
+      phase_end(PH_QR);
+      return false;                                         // nothing of Z or Sv written: the caller's path takes over
+    }
+    hipk::tri_product(st_, Gr[3], Gr[2], l, R);                                               // R_W = RW2 RW1
+    hipk::gemm_f64(st_, false, l, l, l, 1.0, R, l, X[1], l, 0.0, Rf, l, ws);                // svd(W X2) = svd(R_W X2)
+    phase_end(PH_QR);
+    n_cholqr_ += 2;
+    phase_begin(PH_SVD);
+    svd_small(Rf, l, U, Sv);
+    hipk::scale_cols_sqrt(st_, U, l, Sv, K);
+    phase_end(PH_SVD);
+    phase_begin(PH_SMALL_GEMM);
+    hipk::gemm_f64(st_, false, l, K, l, 1.0, X[3], l, U, l, 0.0, Mm, l, ws);                // XW2 U sqrt(S), first K columns
+    hipk::gemm_f64(st_, false, N, K, l, 1.0, A1, N, Mm, l, 0.0, A0, N, ws);                 // C = B1 (XW2 U sqrt(S))
+    hipk::gemm_f64(st_, false, n, K, N, 1.0, Sm, lds, A0, N, 0.0, Z, ldz, ws);              // Z = S C
+    // the last l - K columns of Z are zero by definition (RandMatFact.jl:87)
+    if (K < l) HIP_CHECK(hipMemsetAsync(Z + (size_t)K * ldz, 0, sizeof(double) * ((size_t)(l - K - 1) * ldz + n), st_));
+    check_launch("lowrank_tail");
+    phase_end(PH_SMALL_GEMM);
+    return true;
+  }
   void svd_small(double* G, int64_t l, double* U, double* S) override {
     bind();
     if (l > 5000) throw Error(GSI_ERR_ARG, "sketch width l = K+p > 5000 is not supported by the LDS-resident block Jacobi SVD");

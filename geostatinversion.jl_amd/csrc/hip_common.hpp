@@ -174,6 +174,11 @@ void cholqr2_apply(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, 
                    double* R, double* small_ws, double* gemm_ws);
 void cholqr2_R(hipStream_t st, int64_t l, double* small_ws, double* R);         // R = R2 R1 after cholqr2_factor
 const double* cholqr2_X2(const double* small_ws, int64_t l);                    // R2^-1 (l x l) after cholqr2_factor
+void mirror_upper(hipStream_t st, double* G, int64_t l);                          // strictly lower <- upper
+// R = chol(Gm) in place and X = R^-1 for a Gram matrix formed by the caller (upper triangle read, then mirrored); check: the
+// second round's |Gm - I| test.  false: l > 384 (nothing queued)
+bool cq_gram_round(hipStream_t st, double* Gm, int64_t l, double* X, bool check, int32_t* flag);
+void tri_product(hipStream_t st, const double* R2, const double* R1, int64_t l, double* R);   // R = R2 R1 (upper triangular)
 void scholqr3_factor(hipStream_t st, const double* Y, int64_t m, int64_t l, int64_t ld, double* T, int64_t ldt,
                      double* S, int64_t lds, double* small_ws, int32_t* flag, double* gemm_ws);
 void scholqr3_apply(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const double* S, int64_t lds,

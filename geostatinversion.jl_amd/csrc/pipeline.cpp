@@ -711,10 +711,29 @@ static Buf rangefinder_rows(const Operator& A, const double* Omega_loc, int64_t 
 // `defer` (randsvd on one rank): the final thin Q may come back one tall product short -- Q = Q1 X2 with Q1 in backend
 // workspace (Backend::qr_thinQ_deferred); the returned Buf is then empty and defer->Q1 / ldq / X2 are set.
 struct DeferredQ { const double* Q1 = nullptr; int64_t ldq = 0; Buf X2; };
-static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer);
+// `last` (randsvd of a LowRankCovMatrix on one rank, sample-space tail): the range finder stops in front of its last product
+// A*X and hands back X (n x l, ld n) -- the last LU'd panel, or Omega when q = 0 -- with everything before it as always.
+struct LastPanel { Buf own; const double* X = nullptr; int64_t ldx = 0; };
+static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer,
+                            LastPanel* last = nullptr);
 Buf rangefinder(const Operator& A, const double* Omega, int64_t l, int64_t q) { return rangefinder_impl(A, Omega, l, q, nullptr); }
 
-static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer) {
+// the single-rank end of the range finder: the thin Q of Y (m x l, ld m), deferred into defer when it can be
+static Buf final_q_single(const Operator& A, Buf& Y, int64_t l, DeferredQ* defer) {
+  Context& c = *A.ctx;
+  Backend* be = c.be.get();
+  if (defer != nullptr) {
+    ScopedPhase ph(be, PH_QR);
+    defer->X2 = Buf(be, (size_t)l * l);
+    if (be->qr_thinQ_deferred(Y.p, A.m, l, A.m, &defer->Q1, &defer->ldq, defer->X2.p)) return Buf();
+    defer->X2.reset();
+    defer->Q1 = nullptr;
+  }
+  tsqr(c, A, Y, l);                                         // pivoted-QR range       :57-58, 75-76
+  return std::move(Y);
+}
+
+static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer, LastPanel* last) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
   if (q < 0)   // RandMatFact.jl:62-64
@@ -723,19 +742,11 @@ static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, i
   if (l < 1 || l > A.m || l > A.n) throw Error(GSI_ERR_ARG, "rangefinder: need 1 <= l <= min(size(A))");
   const bool single = (c.nranks() == 1);
   const int64_t m = A.m, n = A.n;
-  auto final_q_single = [&](Buf& Y) -> bool {               // true: deferred, Y is no longer needed
-    if (defer == nullptr || !single) return false;
-    ScopedPhase ph(be, PH_QR);
-    defer->X2 = Buf(be, (size_t)l * l);
-    if (be->qr_thinQ_deferred(Y.p, m, l, m, &defer->Q1, &defer->ldq, defer->X2.p)) return true;
-    defer->X2.reset();
-    defer->Q1 = nullptr;
-    return false;
-  };
   if (q == 0) {
+    if (last != nullptr && single) { last->X = Omega; last->ldx = n; return Buf(); }
     Buf Yloc(be, (size_t)std::max<int64_t>(A.mloc, 1) * l);
     op_mul(A, Omega, n, l, Yloc.p, A.mloc);                 // Y = A*Omega            :55
-    if (final_q_single(Yloc)) return Buf();
+    if (single) return final_q_single(A, Yloc, l, defer);
     tsqr(c, A, Yloc, l);                                    //                        :57-58
     return Yloc;
   }
@@ -762,15 +773,17 @@ static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, i
     if (shard_y) op_mul_t(A, yl, ldyl, l, Z.p, n);          // Q = A'*Q               :67
     else op_mul_t(A, Yfull.p + A.row0, m, l, Z.p, n);
     lu_panel(c, Z.p, n, l);                                 // Q = lu(Q).L            :68-69 (Z is replicated by the all-reduce)
+    if (i == q && last != nullptr && single) {              // the caller takes it from here (randsvd's sample-space tail)
+      last->own = std::move(Z);
+      last->X = last->own.p;
+      last->ldx = n;
+      return Buf();
+    }
     op_mul(A, Z.p, n, l, yl, ldyl);                         // Q = A*Q                :70
     if (i < q) lu_y();                                      //                        :72-73
   }
   Z.reset();                                                // the QR below wants a panel of its own (512^3: each is tens of GB)
-  if (single) {
-    if (final_q_single(Yfull)) return Buf();
-    tsqr(c, A, Yfull, l);                                   // pivoted-QR range       :75-76
-    return Yfull;
-  }
+  if (single) return final_q_single(A, Yfull, l, defer);
   Yfull.reset();
   tsqr(c, A, Yloc, l);
   return Yloc;
@@ -829,6 +842,26 @@ static void svd_rows(const Operator& A, Buf& Q, int64_t K, int64_t l, double* Zl
   if (lz < l) be->fill_zero(Zloc + (size_t)lz * ldz, (size_t)(l - lz) * ldz);
 }
 
+// The sample Gram matrix of a LowRankCovMatrix, made on first use (Operator::gram); null when the backend has none.
+static const double* sample_gram(const Operator& A) {
+  Backend* be = A.ctx->be.get();
+  if (A.gram.p != nullptr) return A.gram.p;
+  Buf G(be, (size_t)A.N * A.N);
+  {
+    ScopedPhase ph(be, PH_OTHER);                           // (not PH_GEMM_T: bench.py's roofline counts those as S'X products)
+    if (!be->sample_gram(A.data.p, A.ld, A.mloc, A.N, G.p)) return nullptr;
+  }
+  A.gram = std::move(G);
+  return A.gram.p;
+}
+
+// randsvd's sample-space tail: one rank, a LowRankCovMatrix of at most 4096 samples, and a sketch
+// narrower than the N - 1 dimensions the centred samples span.  GSI_NO_LOWRANK_TAIL=1 switches it off (A/B, tests).
+static bool lowrank_tail_applies(const Operator& A, int64_t l) {
+  static const bool off = (getenv("GSI_NO_LOWRANK_TAIL") != nullptr);
+  return !off && A.kind == OP_LOWRANK && !A.ctx->comm && A.m == A.n && A.mloc == A.m && A.N <= 4096 && l <= A.N - 1;
+}
+
 void randsvd(const Operator& A, const double* Omega, int64_t K, int64_t p, int64_t q, double* Z, double* S) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
@@ -837,7 +870,32 @@ void randsvd(const Operator& A, const double* Omega, int64_t K, int64_t p, int64
   // One rank, no communicator: the thin Q is only ever used as B = Q'A (:85), so its last tall product is deferred into the
   // l x l factor of svd(B) -- Q = Q1 X2, W = A'Q1, svd(W X2) -- when CholeskyQR2 applies (the usual case).
   DeferredQ dq;
-  Buf Q = rangefinder_impl(A, Omega, l, q, c.comm ? nullptr : &dq);   // Q = rangefinder(A, K+p, q)     :84
+  // A LowRankCovMatrix on one rank goes further: after the last panel LU L nothing needs a tall panel but Z, so the range
+  // finder hands back L, T = S'L is formed, and the backend finishes in the coordinates of range(S) (Backend::lowrank_tail).
+  // Where it declines, Y = S T / (N - 1) is formed with the products op_mul runs and the ordinary path follows, bit for bit.
+  LastPanel last;
+  const bool tail = lowrank_tail_applies(A, l);
+  Buf Q = rangefinder_impl(A, Omega, l, q, c.comm ? nullptr : &dq, tail ? &last : nullptr);   // Q = rangefinder(A, K+p, q)  :84
+  if (last.X != nullptr) {
+    Buf T(be, (size_t)A.N * l);
+    {
+      ScopedPhase ph(be, PH_GEMM_T);
+      be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, last.X, last.ldx, 0.0, T.p, A.N);        // T = S'L  (op_mul's first product)
+    }
+    const double* G = sample_gram(A);
+    if (G != nullptr && be->lowrank_tail(A.data.p, A.ld, A.n, A.N, G, T.p, l, K, 1.0 / (double)(A.N - 1), Z, A.n, S)) {
+      c.lowrank_tails += 1;
+      return;
+    }
+    Buf Y(be, (size_t)A.m * l);
+    {
+      ScopedPhase ph(be, PH_GEMM_N);
+      be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T.p, A.N, 0.0, Y.p, A.m);   // Y = A*L   :70
+    }
+    T.reset();
+    last.own.reset();
+    Q = final_q_single(A, Y, l, &dq);
+  }
   if (dq.Q1 != nullptr) {
     Buf W(be, (size_t)A.n * l);
     op_mul_t(A, dq.Q1, dq.ldq, l, W.p, A.n);                // B = Q'*A  (held as A'Q1; X2 follows in svd_tall)   :85
