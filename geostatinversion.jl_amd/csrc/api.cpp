@@ -197,6 +197,8 @@ int gsi_ctx_path_info(gsi_ctx* ctx, int64_t* out, int64_t n_out) {
     for (int f = 0; f < (int)Context::LU_FORMS; ++f) v[GSI_PATH_LU_FORM_COUNTS + f] = c.lu_form_count[f];
     v[GSI_PATH_SVD_CAP_HITS] = c.be->svd_cap_hits();
     v[GSI_PATH_LOWRANK_TAILS] = c.lowrank_tails;
+    v[GSI_PATH_LOWRANK_POWER_STEPS] = c.lowrank_power_steps;
+    v[GSI_PATH_LOWRANK_POWER_DECLINES] = c.lowrank_power_declines;
     for (int64_t i = 0; i < n_out; ++i) out[i] = i < GSI_PATH_INFO_COUNT ? v[i] : 0;
   });
 }

@@ -99,6 +99,12 @@ class Backend {
   // Y (m x l, ld) <- L of lu(Y) in pivoted row order; ipiv (device int32[l]) may be null.
   // Sets *singular_flag (backend int, see flags()) to j+1 on an exactly zero pivot.
   virtual void lu_L(double* Y, int64_t m, int64_t l, int64_t ld, int32_t* ipiv_host_or_null) = 0;
+  // lu_L, with the LAPACK interchanges (0-based: row j <-> row ipiv[j] at step j) left on the device at *ipiv_dev, valid
+  // until the next factorization.  false: not available, nothing ran.
+  virtual bool lu_L_keep(double* Y, int64_t m, int64_t l, int64_t ld, int32_t** ipiv_dev) {
+    (void)Y; (void)m; (void)l; (void)ld; (void)ipiv_dev;
+    return false;
+  }
   // ---- the same factorization ROW-SHARDED (SURVEY.md 8e "sharded alternative"): primitives on this rank's rows
   //      [row0, row0 + mloc) of the m x l panel, ld = leading dimension of the local block; the exchange between ranks is
   //      pipeline.cpp:lu_panel_sharded.  Blocks of `lus_block()` columns, leaves of 8; per element the arithmetic of lu_L.
@@ -187,6 +193,18 @@ class Backend {
   virtual bool lowrank_tail(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
                             int64_t K, double c, double* Z, int64_t ldz, double* Sv) {
     (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)l; (void)K; (void)c; (void)Z; (void)ldz; (void)Sv;
+    return false;
+  }
+  // One power step of the range finder in sample space.  The panel Y = c S T (T: N x l, ld N) was
+  // factored by lu_L_keep into ipiv and L (n x l, ld ldl): P Y = L U, so L = (P S) C with C = c T U^-1, where
+  // U = L11^-1 (P Y)[0:l] comes from the pivot rows, and
+  //   T_next = S'L = G C + S[mv]' ((S[perm(mv)] - S[mv]) C)          (mv: the at most 2 l rows the interchanges move)
+  // (N x l, ld N) with no n x l product.  false (declines; T_next undefined): (P S) C differs from the L in memory by more
+  // than 1e-8 on the l pivot rows or a fixed sample of the others, the factorization flagged a zero pivot, or a shape it
+  // does not cover; the caller then forms S'L from L.
+  virtual bool lowrank_power_step(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T,
+                                  const int32_t* ipiv, const double* L, int64_t ldl, int64_t l, double c, double* T_next) {
+    (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)ipiv; (void)L; (void)ldl; (void)l; (void)c; (void)T_next;
     return false;
   }
   // G (l x l, ld l), columns orthogonalised in place by one-sided Jacobi; on return

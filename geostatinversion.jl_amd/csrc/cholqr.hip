@@ -322,6 +322,9 @@ __device__ __forceinline__ void cqf_block_row_col(double* __restrict__ gcol /* G
 // block rows, [3] trailing updates with the next diagonal block inside them, [4] diagonal inverses, [5] W = R X_jj, [6] the
 // inverse's tiles (GSI_CQ_TRACE=1)
 #define CQF_STAMP(ph) do { if (trace != nullptr && tid == 0) { const unsigned long long now_ = wall_clock64(); trace[ph] += now_ - t_last; t_last = now_; } } while (0)
+__device__ __forceinline__ void cqf_tri_inverse(const double* __restrict__ G, int l, double* __restrict__ X, double* Us,
+                                                double* Ds, int tid, int lane, int wave, unsigned long long* trace,
+                                                unsigned long long& t_last);
 __global__ __launch_bounds__(CQF_THREADS) void cq_chol_inv_kernel(double* __restrict__ G, int l, double* __restrict__ X,
                                                                   int32_t* __restrict__ flag, unsigned long long* __restrict__ trace) {
   unsigned long long t_last = (trace != nullptr) ? wall_clock64() : 0ull;
@@ -444,8 +447,16 @@ __global__ __launch_bounds__(CQF_THREADS) void cq_chol_inv_kernel(double* __rest
     __syncthreads();
     CQF_STAMP(3);
   }
+  cqf_tri_inverse(G, l, X, Us, Ds, tid, lane, wave, trace, t_last);
+}
 
-  // ================= X = R^-1 =================
+// ================= X = R^-1 =================
+// R (l x l, ld l) upper triangular, nothing below its diagonal read; X zero below the diagonal blocks on entry.  All threads
+// of a CQF_THREADS workgroup; Us / Ds: the LDS images of cq_chol_inv_kernel.
+__device__ __forceinline__ void cqf_tri_inverse(const double* __restrict__ G, int l, double* __restrict__ X, double* Us,
+                                                double* Ds, int tid, int lane, int wave, unsigned long long* trace,
+                                                unsigned long long& t_last) {
+  const int nblk = (l + CQ_TB - 1) / CQ_TB;
   // diagonal blocks: X_jj = U_jj^-1, one wave per block, all at once
   for (int jb = wave; jb < nblk; jb += CQF_THREADS / 64) {
     const int j0 = jb * CQ_TB;
@@ -527,6 +538,15 @@ __global__ __launch_bounds__(CQF_THREADS) void cq_chol_inv_kernel(double* __rest
   }
 }
 #undef CQF_STAMP
+// X = R^-1 alone: the second half of cq_chol_inv_kernel on an upper triangular R the caller has (U of a panel LU)
+__global__ __launch_bounds__(CQF_THREADS) void cq_tri_inv_kernel(const double* __restrict__ R, int l, double* __restrict__ X) {
+  extern __shared__ double cqf_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int64_t e = tid; e < (int64_t)l * l; e += CQF_THREADS) X[e] = 0.0;
+  __syncthreads();
+  unsigned long long t_last = 0;
+  cqf_tri_inverse(R, l, X, cqf_lds, cqf_lds + CQ_TB * CQF_LDU, tid, lane, wave, nullptr, t_last);
+}
 
 static inline int grid_for(int64_t total, int cap = 2048) {
   int64_t g = (total + 255) / 256;
@@ -705,6 +725,71 @@ bool cq_gram_round(hipStream_t st, double* Gm, int64_t l64, double* X, bool chec
 // R (l x l) <- R2 R1, both upper triangular
 void tri_product(hipStream_t st, const double* R2, const double* R1, int64_t l, double* R) {
   hipLaunchKernelGGL(cq_triprod_kernel, dim3(grid_for(l * l, 256)), dim3(256), 0, st, R2, R1, (int)l, R);
+}
+
+// ---- randsvd's power steps in sample space (hip_backend.hip:lowrank_power_step) ----
+// R (nr x N, ld ldr): row k = S[src[k], :] - S[sub[k], :], or S[src[k], :] where sub[k] < 0.  Consecutive threads take
+// consecutive k of one sample column: the stores are contiguous, the loads one row of S apart (8 bytes each, whatever the order).
+__global__ __launch_bounds__(256) void lr_gather_rows_kernel(const double* __restrict__ S, int64_t lds, int64_t N,
+                                                             const int64_t* __restrict__ src, const int64_t* __restrict__ sub,
+                                                             int64_t nr, double* __restrict__ R, int64_t ldr) {
+  const int64_t total = nr * N;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = e % nr, c = e / nr;
+    const double* col = S + c * lds;
+    const int64_t s = sub[k];
+    double v = col[src[k]];
+    if (s >= 0) v -= col[s];
+    R[k + c * ldr] = v;
+  }
+}
+// part[blockIdx.x] = max over its share of k < nchk, j < l of |E[k, j] - L[rows[k], j]|; NaN counts as +inf
+__global__ __launch_bounds__(256) void lr_check_rows_kernel(const double* __restrict__ E, int64_t lde,
+                                                            const double* __restrict__ L, int64_t ldl,
+                                                            const int64_t* __restrict__ rows, int64_t nchk, int64_t l,
+                                                            double* __restrict__ part) {
+  __shared__ double red[4];
+  double mx = 0.0;
+  const int64_t total = nchk * l;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = e % nchk, j = e / nchk;
+    const double d = fabs(E[k + j * lde] - L[rows[k] + j * ldl]);
+    if (!(d <= mx)) mx = (d != d) ? INFINITY : d;
+  }
+  for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+// Lt (l x l, ld l) <- L11' for the unit lower triangle L11 on top of L (ld ldl): unit upper triangular
+__global__ __launch_bounds__(256) void lr_l11_transpose_kernel(const double* __restrict__ L, int64_t ldl, int64_t l,
+                                                               double* __restrict__ Lt) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < l * l; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = e % l, j = e / l;
+    Lt[e] = (i < j) ? L[j + i * ldl] : (i == j ? 1.0 : 0.0);
+  }
+}
+void lr_l11_transpose(hipStream_t st, const double* L, int64_t ldl, int64_t l, double* Lt) {
+  hipLaunchKernelGGL(lr_l11_transpose_kernel, dim3(grid_for(l * l, 512)), dim3(256), 0, st, L, ldl, l, Lt);
+}
+// X = R^-1 (l x l, ld l) of an upper triangular R: the inverse half of the fused Cholesky kernel.  false: l beyond it
+bool tri_inverse(hipStream_t st, const double* R, int64_t l64, double* X) {
+  const int l = (int)l64;
+  if (l < 1 || l > CQF_MAXL) return false;
+  static std::atomic<uint64_t> attr_mask{0};
+  if (first_use_on_this_device(attr_mask))
+    (void)hipFuncSetAttribute((const void*)cq_tri_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CQF_LDS_BYTES);
+  hipLaunchKernelGGL(cq_tri_inv_kernel, dim3(1), dim3(CQF_THREADS), CQF_LDS_BYTES, st, R, l, X);
+  return true;
+}
+void lr_gather_rows(hipStream_t st, const double* S, int64_t lds, int64_t N, const int64_t* src, const int64_t* sub,
+                    int64_t nr, double* R, int64_t ldr) {
+  if (nr < 1 || N < 1) return;
+  hipLaunchKernelGGL(lr_gather_rows_kernel, dim3(grid_for(nr * N, 1024)), dim3(256), 0, st, S, lds, N, src, sub, nr, R, ldr);
+}
+void lr_check_rows(hipStream_t st, const double* E, int64_t lde, const double* L, int64_t ldl, const int64_t* rows,
+                   int64_t nchk, int64_t l, double* part, int nparts) {
+  hipLaunchKernelGGL(lr_check_rows_kernel, dim3(nparts), dim3(256), 0, st, E, lde, L, ldl, rows, nchk, l, part);
 }
 
 // Shifted CholeskyQR3, the tier between CholeskyQR2 and Householder: panels with cond up to ~1e15 (sketches of

@@ -504,6 +504,15 @@ class HipBackend : public Backend {
 
   // ---- panels ----
   void lu_L(double* Y, int64_t m, int64_t l, int64_t ld, int32_t* ipiv_host) override {
+    lu_L_impl(Y, m, l, ld, ipiv_host, nullptr);
+  }
+  // every form below leaves its interchanges in ws_lu_ (untouched until the next factorization): no form declines
+  bool lu_L_keep(double* Y, int64_t m, int64_t l, int64_t ld, int32_t** ipiv_dev) override {
+    if (ipiv_dev == nullptr) return false;
+    lu_L_impl(Y, m, l, ld, nullptr, ipiv_dev);
+    return true;
+  }
+  void lu_L_impl(double* Y, int64_t m, int64_t l, int64_t ld, int32_t* ipiv_host, int32_t** ipiv_dev_out) {
     bind();
     // Panels of up to 4096 rows per CU: leaves held in registers, left-looking blocks, streaming rank-64 updates
     // (panel_lu_leaf.hip).  Everything else takes the streamed leaves below.
@@ -544,6 +553,7 @@ class HipBackend : public Backend {
       w2.info = flags_ + 0;
       hipk::lu2_L(st_, Y, m, l, ld, w2);
       check_launch("lu2_L");
+      if (ipiv_dev_out) *ipiv_dev_out = w2.ipiv;
       if (ipiv_host) {
         HIP_CHECK(hipMemcpyAsync(ipiv_host, w2.ipiv, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));
         HIP_CHECK(hipStreamSynchronize(st_));
@@ -560,6 +570,7 @@ class HipBackend : public Backend {
     int32_t* ipiv_dev = nullptr;
     hipk::lu3_L(st_, Y, m, l, ld, ws_lu_.p, flags_ + 0, &ipiv_dev);
     check_launch("lu3_L");
+    if (ipiv_dev_out) *ipiv_dev_out = ipiv_dev;
     if (ipiv_host) {
       HIP_CHECK(hipMemcpyAsync(ipiv_host, ipiv_dev, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));
       HIP_CHECK(hipStreamSynchronize(st_));
@@ -1040,6 +1051,110 @@ class HipBackend : public Backend {
     check_launch("lowrank_tail");
     phase_end(PH_SMALL_GEMM);
     return true;
+  }
+  // One power step of the range finder in sample space (Backend::lowrank_power_step).  The LU of
+  // Y = c S T gives L = P Y U^-1 = (P S) C, C = c T U^-1, so S'L = S'P S C = G C + S'(P - I) S C, and P - I is non-zero on
+  // the <= 2 l rows the interchanges move.  The factorization keeps its U12 blocks in a workspace, so U is re-formed from the
+  // l pivot rows: U = L11^-1 (P Y)[0:l] = c L11^-1 S[perm(0:l)] T.  Launches: one gather (the moved rows, their differences,
+  // the check rows -- the pivot rows first), S_piv T (l x l x N), L11', its inverse, U, U^-1 (the inverses one workgroup
+  // each), C (N x l x l), E = [D; S_chk] C, the check, G C (N x l x N), S[mv]' E (N x l x 2l).  Two host syncs: the pivots,
+  // and the check's verdict.  Fixed shapes and orders, no atomics: repeated calls give the same bits.
+  bool lowrank_power_step(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T,
+                          const int32_t* ipiv, const double* L, int64_t ldl, int64_t l, double c, double* Tn) override {
+    bind();
+    static const bool trace = (getenv("GSI_LOWRANK_POWER_TRACE") != nullptr);
+    constexpr int64_t NSAMPLE = 256;        // rows below the pivot block that the check also reads
+    constexpr int NPARTS = 128;             // workgroups of the check (partial maxima)
+    constexpr double CHECK_MAX = 1e-8;      // |(P S) C - L|max above this: the coefficients no longer reproduce L (declined)
+    if (l < 1 || l > 384 || N < 1 || N > 4096 || n < 2 * l || n >= ((int64_t)1 << 31)) return false;
+    std::vector<int32_t> piv((size_t)l);
+    int32_t info = 0;
+    HIP_CHECK(hipMemcpyAsync(piv.data(), ipiv, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipMemcpyAsync(&info, flags_ + 0, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (info != 0) return false;            // a zero pivot (or a lost exchange): the entry point reports it
+    // P composed from the interchanges: (P S)[i] = S[perm(i)]
+    std::map<int64_t, int64_t> perm;
+    auto at = [&](int64_t i) { auto it = perm.find(i); return it == perm.end() ? i : it->second; };
+    for (int64_t j = 0; j < l; ++j) {
+      const int64_t r = piv[(size_t)j];
+      if (r < j || r >= n) return false;
+      if (r == j) continue;
+      const int64_t a = at(j), b = at(r);
+      perm[j] = b;
+      perm[r] = a;
+    }
+    std::vector<int64_t> mv;                // ascending (std::map order)
+    for (const auto& kv : perm)
+      if (kv.second != kv.first) mv.push_back(kv.first);
+    const int64_t nmv = (int64_t)mv.size(), ns = std::min<int64_t>(NSAMPLE, n - l), nchk = l + ns;
+    auto up8 = [](int64_t x) { return (x + 7) & ~(int64_t)7; };
+    // gathered rows (ld ldr, every block starting on an even row): [0, nmv) D = S[perm(mv)] - S[mv]; [o_chk, o_chk + nchk)
+    // (P S) of the check rows; [o_sm, o_sm + nmv) S[mv].  Padding rows are S[0] - S[0] = 0.
+    const int64_t o_chk = up8(nmv), o_sm = o_chk + up8(nchk), nr = o_sm + nmv, ldr = up8(std::max<int64_t>(nr, 1));
+    std::vector<int64_t> idx((size_t)(2 * ldr + nchk), 0);
+    int64_t* src = idx.data();
+    int64_t* sub = src + ldr;
+    int64_t* chk = sub + ldr;
+    for (int64_t k = 0; k < nmv; ++k) {
+      src[k] = at(mv[(size_t)k]); sub[k] = mv[(size_t)k];
+      src[o_sm + k] = mv[(size_t)k]; sub[o_sm + k] = -1;
+    }
+    uint64_t h = 0x9e3779b97f4a7c15ull;     // a fixed sample of the rows below the pivot block (splitmix64)
+    for (int64_t k = 0; k < nchk; ++k) {
+      int64_t i = k;
+      if (k >= l) {
+        h += 0x9e3779b97f4a7c15ull;
+        uint64_t z = h;
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        i = l + (int64_t)(z % (uint64_t)(n - l));
+      }
+      chk[k] = i;
+      src[o_chk + k] = at(i); sub[o_chk + k] = -1;
+    }
+    const size_t ll = (size_t)up8(l * l), Nl = (size_t)up8(N * l);
+    Scratch buf(this, 5 * ll + Nl + (size_t)ldr * (size_t)N + (size_t)ldr * (size_t)l + idx.size() + NPARTS);
+    double* X = buf.p;                      // U^-1
+    double* Mp = X + ll;                    // S[perm(0:l)] T
+    double* Lt = Mp + ll;                   // L11'
+    double* Vt = Lt + ll;                   // (L11')^-1
+    double* Uf = Vt + ll;                   // U = c L11^-1 Mp
+    double* C = Uf + ll;                    // c T U^-1
+    double* R = C + Nl;                     // the gathered rows
+    double* E = R + (size_t)ldr * N;        // rows [0, o_chk + nchk) of R times C
+    int64_t* idx_dev = reinterpret_cast<int64_t*>(E + (size_t)ldr * l);
+    double* part = reinterpret_cast<double*>(idx_dev + idx.size());
+    const int64_t me = o_chk + nchk;
+    size_t gmax = hipk::gemm_workspace_doubles(N, l, l);
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, N));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, l));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(me, l, N));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, N));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, nmv));
+    double* ws = gemm_ws(gmax + 64);
+    HIP_CHECK(hipMemcpyAsync(idx_dev, idx.data(), sizeof(int64_t) * idx.size(), hipMemcpyHostToDevice, st_));
+    hipk::lr_gather_rows(st_, Sm, lds, N, idx_dev, idx_dev + ldr, nr, R, ldr);
+    hipk::gemm_f64(st_, false, l, l, N, 1.0, R + o_chk, ldr, T, N, 0.0, Mp, l, ws);          // S[perm(0:l)] T
+    hipk::lr_l11_transpose(st_, L, ldl, l, Lt);
+    (void)hipk::tri_inverse(st_, Lt, l, Vt);                                                    // (L11^-1)'
+    hipk::gemm_f64(st_, true, l, l, l, c, Vt, l, Mp, l, 0.0, Uf, l, ws);                      // U = c L11^-1 Mp
+    (void)hipk::tri_inverse(st_, Uf, l, X);
+    hipk::gemm_f64(st_, false, N, l, l, c, T, N, X, l, 0.0, C, N, ws);                       // C = c T U^-1
+    hipk::gemm_f64(st_, false, me, l, N, 1.0, R, ldr, C, N, 0.0, E, ldr, ws);                // [D; (P S)_chk] C
+    hipk::lr_check_rows(st_, E + o_chk, ldr, L, ldl, idx_dev + 2 * ldr, nchk, l, part, NPARTS);
+    hipk::gemm_f64(st_, false, N, l, N, 1.0, G, N, C, N, 0.0, Tn, N, ws);                    // G C
+    if (nmv > 0) hipk::gemm_f64(st_, true, N, l, nmv, 1.0, R + o_sm, ldr, E, ldr, 1.0, Tn, N, ws);   // + S[mv]' (D C)
+    check_launch("lowrank_power_step");
+    double parts[NPARTS];
+    HIP_CHECK(hipMemcpyAsync(parts, part, sizeof(parts), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));   // (idx and parts live until here)
+    double mx = 0.0;
+    for (int p = 0; p < NPARTS; ++p) mx = std::max(mx, parts[p]);
+    if (trace) fprintf(stderr, "lowrank_power_step: n %lld N %lld l %lld, %lld moved rows, check max |(P S) C - L| = %.3e\n",
+                       (long long)n, (long long)N, (long long)l, (long long)nmv, mx);
+    return mx <= CHECK_MAX;
   }
   void svd_small(double* G, int64_t l, double* U, double* S) override {
     bind();

@@ -179,6 +179,15 @@ void mirror_upper(hipStream_t st, double* G, int64_t l);                        
 // second round's |Gm - I| test.  false: l > 384 (nothing queued)
 bool cq_gram_round(hipStream_t st, double* Gm, int64_t l, double* X, bool check, int32_t* flag);
 void tri_product(hipStream_t st, const double* R2, const double* R1, int64_t l, double* R);   // R = R2 R1 (upper triangular)
+// randsvd's power steps in sample space: X = R^-1 of an upper triangular R (false: l > 384, nothing queued); R (nr x N, ld
+// ldr) <- rows S[src[k]] - S[sub[k]] (S[src[k]] where sub[k] < 0); part[0 .. nparts) <- partial maxima of
+// |E[k, j] - L[rows[k], j]| over k < nchk, j < l (NaN: +inf)
+bool tri_inverse(hipStream_t st, const double* R, int64_t l, double* X);
+void lr_l11_transpose(hipStream_t st, const double* L, int64_t ldl, int64_t l, double* Lt);   // Lt = L[0:l, 0:l]' (unit upper)
+void lr_gather_rows(hipStream_t st, const double* S, int64_t lds, int64_t N, const int64_t* src, const int64_t* sub,
+                    int64_t nr, double* R, int64_t ldr);
+void lr_check_rows(hipStream_t st, const double* E, int64_t lde, const double* L, int64_t ldl, const int64_t* rows,
+                   int64_t nchk, int64_t l, double* part, int nparts);
 void scholqr3_factor(hipStream_t st, const double* Y, int64_t m, int64_t l, int64_t ld, double* T, int64_t ldt,
                      double* S, int64_t lds, double* small_ws, int32_t* flag, double* gemm_ws);
 void scholqr3_apply(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const double* S, int64_t lds,

@@ -713,7 +713,16 @@ static Buf rangefinder_rows(const Operator& A, const double* Omega_loc, int64_t 
 struct DeferredQ { const double* Q1 = nullptr; int64_t ldq = 0; Buf X2; };
 // `last` (randsvd of a LowRankCovMatrix on one rank, sample-space tail): the range finder stops in front of its last product
 // A*X and hands back X (n x l, ld n) -- the last LU'd panel, or Omega when q = 0 -- with everything before it as always.
-struct LastPanel { Buf own; const double* X = nullptr; int64_t ldx = 0; };
+// T (N x l, ld N), when set: S'X, formed by the last power step in sample space.
+struct LastPanel { Buf own; const double* X = nullptr; int64_t ldx = 0; Buf T; };
+static const double* sample_gram(const Operator& A);
+static bool lowrank_tail_applies(const Operator& A, int64_t l);
+// randsvd's power steps in sample space: wherever the tail may run; GSI_NO_LOWRANK_POWER=1 switches
+// off these alone (A/B), GSI_NO_LOWRANK_TAIL=1 both.
+static bool lowrank_power_applies(const Operator& A, int64_t l) {
+  static const bool off = (getenv("GSI_NO_LOWRANK_POWER") != nullptr);
+  return !off && lowrank_tail_applies(A, l);
+}
 static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer,
                             LastPanel* last = nullptr);
 Buf rangefinder(const Operator& A, const double* Omega, int64_t l, int64_t q) { return rangefinder_impl(A, Omega, l, q, nullptr); }
@@ -762,24 +771,75 @@ static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, i
   // a sketch panel comes out of A*X as row shards: factor it where it lies when the sharded LU is on (the all-gather
   // of the panel and the replicated factorization go away; A'*L only reads the local rows anyway)
   const bool shard_y = !single && use_sharded_lu(c, A, m, l);
+  // randsvd of a LowRankCovMatrix on one rank: every product A*L / A'*L after a panel LU is S (c T) with T = S'L formed in
+  // sample space from the T of the panel before, the LU's pivots and its L (Backend::lowrank_power_step).
+  // The first product and the panel LUs are the ones below; on a decline S'L is formed from the L in memory by the product
+  // op_mul runs, and the call stays on the direct path -- a decline at the first LU gives the bits of the direct path.
+  struct Power { bool on = false; const double* G = nullptr; Buf T, Tn; int32_t* ipiv = nullptr; } pw;
+  if (last != nullptr && single && lowrank_power_applies(A, l)) {
+    pw.on = true;
+    pw.T = Buf(be, (size_t)A.N * l);
+    pw.Tn = Buf(be, (size_t)A.N * l);
+  }
+  auto lu_panel_keep = [&](double* Y, int64_t rows) {      // single rank: lu_panel, keeping the pivots while pw.on
+    if (pw.on) {
+      ScopedPhase ph(be, PH_LU);
+      if (be->lu_L_keep(Y, rows, l, rows, &pw.ipiv)) return;
+      pw.on = false;                                        // (not available: nothing ran)
+    }
+    lu_panel(c, Y, rows, l);
+  };
+  // T <- S'L for the L just factored; false: the direct path from here on (the caller forms S'L)
+  auto power_step = [&](const double* Lp, int64_t ldl) -> bool {
+    if (!pw.on) return false;
+    if (pw.G == nullptr) pw.G = sample_gram(A);
+    bool ok = false;
+    if (pw.G != nullptr) {
+      ScopedPhase ph(be, PH_OTHER);                         // (not PH_GEMM_T / _N: bench.py's roofline counts those as tall products)
+      ok = be->lowrank_power_step(A.data.p, A.ld, A.mloc, A.N, pw.G, pw.T.p, pw.ipiv, Lp, ldl, l, 1.0 / (double)(A.N - 1),
+                                  pw.Tn.p);
+      if (!ok) c.lowrank_power_declines += 1;
+    }
+    if (!ok) { pw = Power(); return false; }
+    std::swap(pw.T, pw.Tn);
+    c.lowrank_power_steps += 1;
+    return true;
+  };
+  auto mul_T = [&](double* Yo, int64_t ldy) {               // Y = A*L = S (c T): op_mul's second product
+    ScopedPhase ph(be, PH_GEMM_N);
+    be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, pw.T.p, A.N, 0.0, Yo, ldy);
+  };
   auto lu_y = [&]() {
     if (shard_y) { lu_panel_sharded(c, yl, m, A.row0, A.mloc, l); return; }
     gather_rows(c, A, yl, ldyl, l, Yfull.p);
-    lu_panel(c, Yfull.p, m, l);
+    if (single) lu_panel_keep(Yfull.p, m);
+    else lu_panel(c, Yfull.p, m, l);
   };
-  op_mul(A, Omega, n, l, yl, ldyl);                         // Y = A*Omega            :55
+  if (pw.on) {                                              // Y = A*Omega            :55 (op_mul's products, T kept)
+    {
+      ScopedPhase ph(be, PH_GEMM_T);
+      be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, Omega + A.row0, n, 0.0, pw.T.p, A.N);
+    }
+    mul_T(yl, ldyl);
+  } else {
+    op_mul(A, Omega, n, l, yl, ldyl);                       // Y = A*Omega            :55
+  }
   lu_y();                                                   // Q = lu(Y).L            :60-61
   for (int64_t i = 1; i <= q; ++i) {                        //                        :66
-    if (shard_y) op_mul_t(A, yl, ldyl, l, Z.p, n);          // Q = A'*Q               :67
+    if (power_step(Yfull.p, m)) mul_T(Z.p, n);              // Q = A'*Q               :67 (in sample space)
+    else if (shard_y) op_mul_t(A, yl, ldyl, l, Z.p, n);
     else op_mul_t(A, Yfull.p + A.row0, m, l, Z.p, n);
-    lu_panel(c, Z.p, n, l);                                 // Q = lu(Q).L            :68-69 (Z is replicated by the all-reduce)
+    if (single) lu_panel_keep(Z.p, n);                      // Q = lu(Q).L            :68-69
+    else lu_panel(c, Z.p, n, l);                            //                        (Z is replicated by the all-reduce)
     if (i == q && last != nullptr && single) {              // the caller takes it from here (randsvd's sample-space tail)
+      if (power_step(Z.p, n)) last->T = std::move(pw.T);
       last->own = std::move(Z);
       last->X = last->own.p;
       last->ldx = n;
       return Buf();
     }
-    op_mul(A, Z.p, n, l, yl, ldyl);                         // Q = A*Q                :70
+    if (power_step(Z.p, n)) mul_T(yl, ldyl);                // Q = A*Q                :70 (in sample space)
+    else op_mul(A, Z.p, n, l, yl, ldyl);
     if (i < q) lu_y();                                      //                        :72-73
   }
   Z.reset();                                                // the QR below wants a panel of its own (512^3: each is tens of GB)
@@ -877,8 +937,9 @@ void randsvd(const Operator& A, const double* Omega, int64_t K, int64_t p, int64
   const bool tail = lowrank_tail_applies(A, l);
   Buf Q = rangefinder_impl(A, Omega, l, q, c.comm ? nullptr : &dq, tail ? &last : nullptr);   // Q = rangefinder(A, K+p, q)  :84
   if (last.X != nullptr) {
-    Buf T(be, (size_t)A.N * l);
-    {
+    Buf T = std::move(last.T);                              // S'L from the last power step in sample space, if it ran
+    if (T.p == nullptr) {
+      T = Buf(be, (size_t)A.N * l);
       ScopedPhase ph(be, PH_GEMM_T);
       be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, last.X, last.ldx, 0.0, T.p, A.N);        // T = S'L  (op_mul's first product)
     }

@@ -46,6 +46,8 @@ struct Context {
   int profile_level = 0;               // gsi_ctx_profile: 2 = skew barriers in front of collectives / sharded LUs (PH_COMM_WAIT)
   int64_t lu_timeouts_recovered = 0;   // entry points re-run transparently after a lost co-residency (api.cpp:with_retry)
   int64_t lowrank_tails = 0;           // randsvd steps of a LowRankCovMatrix that ran their tail in sample space (pipeline.cpp)
+  int64_t lowrank_power_steps = 0;     // range-finder power steps S'L formed in sample space (pipeline.cpp)
+  int64_t lowrank_power_declines = 0;  // ... and the ones the backend declined (that call took the direct path from there on)
   int rank() const { return comm ? comm->rank : 0; }
   int nranks() const { return comm ? comm->nranks : 1; }
 };
