@@ -544,7 +544,7 @@ class HipBackend : public Backend {
       static const int nb_env = getenv("GSI_LU_NB") ? atoi(getenv("GSI_LU_NB")) : 0;
       w2.nb = (nb_env == 32 || nb_env == 64) ? nb_env : hipk::LU2_NB;
       const size_t rec_bytes = sizeof(unsigned long long) * 2 * ((size_t)w2.grid + hipk::LU2_RES_COPIES) * hipk::LU2_REC_GRANULES;
-      const size_t u12_bytes = sizeof(double) * (size_t)w2.nb * (size_t)l;
+      const size_t u12_bytes = sizeof(double) * (size_t)l * (size_t)l;   // U12 of every block (left-looking between blocks)
       grow(ws_lu_, rec_bytes + u12_bytes + sizeof(int32_t) * (l + 4) + 256);
       char* base = (char*)ws_lu_.p;
       w2.recs = (unsigned long long*)base; base += rec_bytes;

@@ -79,7 +79,7 @@ constexpr int LU2_RES_COPIES = 8;     // copies of the per-step result record (o
 constexpr int LU2_REC_GRANULES = 64;  // one published record per workgroup and pivot step: 64 8-byte granules (512 B)
 struct Lu2Work {
   unsigned long long* recs;   // [2][grid][LU2_REC_GRANULES] candidate records, then [2][LU2_RES_COPIES][LU2_REC_GRANULES] results
-  double* u12;      // [nb * l]
+  double* u12;      // [l * l]: U12 of every block, block i at i * nb * l
   int32_t* ipiv;    // [l]
   int32_t* info;    // [1] first exactly-zero pivot (1-based); -1: the exchange between workgroups timed out
   int bs, rpt, grid, nb;

@@ -19,10 +19,14 @@
 //     sc1 payload -> vmcnt(0) -> sc1 flag, sc1 polls and loads; no fences, no atomics).  Two record sets by parity of
 //     the step: a workgroup can publish step s+2 only after it has seen every record of step s+1, which its owner
 //     wrote after it had read step s.
-//   * lu_u12_kernel + lu_rankk_kernel: the block's trailing update A22 -= L21 (L11^-1 A12) as a streaming kernel:
-//     a wave holds 32 rows' K = 64 multipliers as MFMA fragments in registers and walks the trailing columns,
-//     C tile in, 16 x K/4 MFMAs, C tile out (8 flop per byte of C: MFMA time = HBM time at K = 64).
-// Column passes at l = 320, NB = 64: 5 * 352 + 1536 = 3296 (26 GB at n = 10^6) against ~52 GB before.
+//   * lu_leftlook_kernel + lu_urows_kernel: LEFT-looking between the 64-column blocks too.  Block i's columns are left
+//     alone until block i is next; then one pass brings rows [64 i, m) of them up to date with all 64 i finished L columns
+//     to their left (C tile in registers, the earlier blocks' L fragments streamed once), and after its leaves the U rows
+//     of block i (64 rows of every trailing column) are brought up to date and solved into U12.
+//   * lu_u12_kernel + lu_rankk_kernel: the right-looking update (every trailing column re-read and rewritten after every
+//     block), kept for the row-sharded form, the bit-identity reference.
+// Column passes at l = 320, NB = 64: 5 * 352 + sum_b (64 b + 128) = 1760 + 1152 = 2912 (23.3 GB at n = 10^6) against 3296
+// right-looking and ~52 GB with per-column sweeps.
 #include "hip_common.hpp"
 #include <type_traits>
 #include <cstdio>
@@ -879,16 +883,33 @@ __global__ __launch_bounds__(BS) void lu_leaf_kernel(double* __restrict__ Y, int
 // Thread = one column; L11 in LDS (broadcast reads), the column in registers.
 // (256 threads bring L11 in -- K^2 / 256 loads each instead of K^2 / 64: the kernel sits between two blocks of the
 // factorization and is all latency -- then the first wave solves its 64 columns.)
+// (256 threads) L11 into LDS as [row][col]: a row's multipliers are contiguous
+template <int K>
+__device__ inline void u12_stage_L11(double* L11, const double* __restrict__ Y, int64_t ld, int64_t jb, int64_t jbrow) {
+#pragma unroll 8
+  for (int e = threadIdx.x; e < K * K; e += 256) {
+    const int r = e % K, c = e / K;
+    L11[r * K + c] = Y[(jbrow + r) + (jb + c) * ld];
+  }
+}
+// x <- L11^-1 x: the one scalar order (and fma contraction) every U12 of a factorization is solved in
+template <int K>
+__device__ inline void u12_solve(const double* L11, double (&x)[K]) {
+#pragma unroll
+  for (int r = 1; r < K; ++r) {
+    double v = x[r];
+#pragma unroll
+    for (int p = 0; p < r; ++p) v -= L11[r * K + p] * x[p];
+    x[r] = v;
+  }
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void lu_u12_kernel(const double* __restrict__ Y, int64_t ld, int64_t jb, int64_t jbrow,
                                                      int64_t c0, int64_t c1, double* __restrict__ out) {
   // jb: the block's first COLUMN (global); jbrow: the row of Y that holds global row jb (jb - row0 for a row shard)
   __shared__ double L11[K * K];
-#pragma unroll 8
-  for (int e = threadIdx.x; e < K * K; e += 256) {
-    const int r = e % K, c = e / K;
-    L11[r * K + c] = Y[(jbrow + r) + (jb + c) * ld];    // [row][col]: a row's multipliers are contiguous
-  }
+  u12_stage_L11<K>(L11, Y, ld, jb, jbrow);
   __syncthreads();
   if (threadIdx.x >= 64) return;
   const int64_t c = c0 + (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -897,13 +918,7 @@ __global__ __launch_bounds__(256) void lu_u12_kernel(const double* __restrict__ 
   const double* col = Y + jbrow + c * ld;
 #pragma unroll
   for (int r = 0; r < K; ++r) x[r] = col[r];
-#pragma unroll
-  for (int r = 1; r < K; ++r) {
-    double v = x[r];
-#pragma unroll
-    for (int p = 0; p < r; ++p) v -= L11[r * K + p] * x[p];
-    x[r] = v;
-  }
+  u12_solve<K>(L11, x);
   double* o = out + (c - c0) * K;
 #pragma unroll
   for (int r = 0; r < K; ++r) o[r] = x[r];
@@ -1012,6 +1027,213 @@ static void launch_rankk(hipStream_t st, unsigned grid, double* Y, int64_t ld, i
   else if (chunk == 64) launch_rankk_v<K, 1, 64>(st, grid, Y, ld, m, r_begin, jb, c0, t, U12);
   else if (depth == 2) launch_rankk_v<K, 2, 128>(st, grid, Y, ld, m, r_begin, jb, c0, t, U12);
   else launch_rankk_v<K, 1, 128>(st, grid, Y, ld, m, r_begin, jb, c0, t, U12);
+}
+
+// ---- left-looking order between blocks (the single-rank factorizations; the row-sharded form stays right-looking) ----------
+// Block i's columns are left alone until block i is next; then ONE pass brings rows [jb, m) of them up to date with every
+// finished block to their left, and after its leaves the U rows of block i (rows [jb, jb + NB) of all trailing columns) are
+// brought up to date the same way and solved.  U12 of every block is kept: U12(i, k, c) = U12[i ldu + c NB + k], ldu = NB l.
+// Every element sees the MFMAs of lu_rankk_kernel -- operands -U12 (A) and L (B) in its lane mapping, k in groups of four,
+// blocks in ascending order -- on an accumulator that stays in registers instead of crossing HBM between the blocks (an fp64
+// store + reload is exact), and the U rows are solved by lu_u12_kernel's own u12_solve: the factors are bit for bit the
+// right-looking ones (the row-sharded form is the reference).  Passes over the panel per block update: 64 i (L) + 128 (C).
+constexpr int LL_WAVES = 12;                                   // 12 waves x 16 rows: three waves per SIMD, one workgroup per CU
+constexpr int LL_BS = 64 * LL_WAVES;
+constexpr size_t LL_LDS = (size_t)4 * 64 * 66 * sizeof(double);   // -U12 images of up to four earlier 64-column blocks (132 KB)
+template <int NB>
+constexpr int ll_group() { return (int)(LL_LDS / ((size_t)NB * (NB + 2) * sizeof(double))); }
+
+// a uniform pointer the compiler may not re-derive from its start: one 64-bit SGPR pair walks the columns instead of one
+// hoisted base per column (32 of them ran the kernel out of SGPRs and into spills)
+__device__ __forceinline__ char* ll_advance(char* p, int64_t step) {
+  p += step;
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+// A[jb:m, jb:jb+tc] -= sum over the earlier blocks ip0 <= q < ip1 of L[jb:m, q NB:(q+1) NB] U12(q, :, jb:jb+tc).
+// Persistent: the workgroup stages the -U12 images once (LDS [(q NB + c) KP + k], KP / 2 odd as in lu_rankk_kernel), then
+// every wave walks 16-row chunks on its own, no barrier: C tile (16 rows x NB columns) in registers for the whole chunk, the
+// L fragments of block q + 1 in flight behind the NB / 16 x NB / 4 MFMAs of block q (64 cycles each: one LDS read per MFMA is
+// far below the LDS rate).  Addressing: a 32-bit per-lane offset (row, and kk columns over) set once per chunk + one walking
+// uniform column pointer -- no vector address arithmetic between the MFMAs.
+// WIDE: panels whose 3 ld * 8 bytes do not fit that offset (ld > 1.7e8 rows) take 64-bit per-lane offsets.
+template <int NB, bool WIDE>
+__global__ __launch_bounds__(LL_BS) void lu_leftlook_kernel(double* __restrict__ Y, int64_t ld, int64_t m, int64_t jb, int tc,
+                                                            int ip0, int ip1, const double* __restrict__ U12, int64_t ldu) {
+  typedef double double4_t __attribute__((ext_vector_type(4)));
+  typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type off_t;
+  constexpr int KP = NB + 2, NT = NB / 16, NS = NB / 4;
+  extern __shared__ double us[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int jl = lane & 15, kk = lane >> 4;
+  const int nbk = ip1 - ip0;
+  for (int e = tid; e < nbk * NB * NB; e += LL_BS) {
+    const int k = e % NB, c = (e / NB) % NB, q = e / (NB * NB);
+    us[(q * NB + c) * KP + k] = (c < tc) ? -U12[(int64_t)(ip0 + q) * ldu + (jb + c) * NB + k] : 0.0;
+  }
+  __syncthreads();
+  const int lb = jl * KP + kk;                      // this lane's fb: -U12(q, 4 s + kk, 16 tt + jl)
+  const int64_t nch = (m - jb + 15) / 16;
+  const int64_t cs = ld * (int64_t)sizeof(double);  // bytes per column
+  for (int64_t ch = (int64_t)blockIdx.x * LL_WAVES + wave; ch < nch; ch += (int64_t)gridDim.x * LL_WAVES) {
+    const int64_t rb = jb + ch * 16;
+    // lane (jl, kk): row rb + jl (rows beyond m read row m - 1 and are never stored), column kk further on
+    const int64_t r = (rb + jl < m) ? rb + jl : m - 1;
+    const off_t vo = (off_t)((r - rb) * (int64_t)sizeof(double) + kk * cs);
+    auto at = [&](char* colp) -> double* { return reinterpret_cast<double*>(colp + vo); };
+    char* const cbase = reinterpret_cast<char*>(Y + rb + jb * ld);
+    double4_t acc[NT];                              // C column jb + 16 tt + 4 reg + kk
+    {
+      char* p = cbase;
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          acc[tt][reg] = (16 * tt + 4 * reg + kk < tc) ? *at(p) : 0.0;
+          p = ll_advance(p, 4 * cs);
+        }
+    }
+    double fa[NS], fn[NS];
+    char* pf = reinterpret_cast<char*>(Y + rb + (int64_t)ip0 * NB * ld);   // walks the L columns, block after block
+    auto load_frag = [&](double (&f)[NS]) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        f[s] = *at(pf);
+        pf = ll_advance(pf, 4 * cs);
+      }
+    };
+    auto run = [&](const double (&f)[NS], int q) {
+      const double* ub = us + (q - ip0) * NB * KP + lb;
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt)
+          acc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(ub[16 * tt * KP + 4 * s], f[s], acc[tt], 0, 0, 0);
+    };
+    load_frag(fa);
+    int q = ip0;
+    for (; q + 1 < ip1; ++q) {                      // (the last block peeled: the prefetch is unconditional in the loop)
+      load_frag(fn);
+      run(fa, q);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) fa[s] = fn[s];
+    }
+    run(fa, q);
+    const bool live = rb + jl < m;
+    char* p = cbase;
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        if (live && 16 * tt + 4 * reg + kk < tc) *at(p) = acc[tt][reg];
+        p = ll_advance(p, 4 * cs);
+      }
+  }
+}
+
+// The U rows of block i = jb / K: rows [jb, jb + K) of the trailing columns [c0, c1) brought up to date with the K-column
+// blocks 0 .. i - 1 (the sequence above, -U12 read from L2: a few MB per factorization), then solved by u12_solve as in
+// lu_u12_kernel: out[k + (c - c0) K].  Workgroup = 64 columns; waves 0 .. K / 16 - 1 hold 16 rows x 64 columns each.
+template <int K>
+__global__ __launch_bounds__(256) void lu_urows_kernel(const double* __restrict__ Y, int64_t ld, int64_t jb, int nprev,
+                                                       int64_t c0, int64_t c1, const double* __restrict__ U12, int64_t ldu,
+                                                       double* __restrict__ out) {
+  typedef double double4_t __attribute__((ext_vector_type(4)));
+  constexpr int TP = K + 1;                    // [col][row] image of the updated rows, padded
+  __shared__ double L11[K * K];
+  __shared__ double T[64 * TP];
+  u12_stage_L11<K>(L11, Y, ld, jb, jb);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int jl = lane & 15, kk = lane >> 4;
+  const int64_t cb = c0 + (int64_t)blockIdx.x * 64;
+  if (wave < K / 16) {
+    const int64_t row = jb + 16 * wave + jl;
+    double4_t acc[4];
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t c = cb + 16 * tt + kk + 4 * reg;
+        acc[tt][reg] = (c < c1) ? Y[row + c * ld] : 0.0;
+      }
+    for (int q = 0; q < nprev; ++q) {
+      const double* ub = U12 + (int64_t)q * ldu;
+#pragma unroll
+      for (int s = 0; s < K / 4; ++s) {
+        const double fa = Y[row + ((int64_t)q * K + 4 * s + kk) * ld];
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+          const int64_t c = cb + 16 * tt + jl;
+          const double fb = (c < c1) ? -ub[c * K + 4 * s + kk] : 0.0;
+          acc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb, fa, acc[tt], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) T[(16 * tt + kk + 4 * reg) * TP + 16 * wave + jl] = acc[tt][reg];
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  const int64_t c = cb + tid;
+  if (c >= c1) return;
+  double x[K];
+#pragma unroll
+  for (int r = 0; r < K; ++r) x[r] = T[tid * TP + r];
+  u12_solve<K>(L11, x);
+  double* o = out + (c - c0) * K;
+#pragma unroll
+  for (int r = 0; r < K; ++r) o[r] = x[r];
+}
+
+template <int NB, bool WIDE>
+static void launch_leftlook_v(hipStream_t st, unsigned grid, double* Y, int64_t ld, int64_t m, int64_t jb, int tc,
+                              const double* U12, int64_t ldu) {
+  static std::atomic<uint64_t> attr_mask{0};
+  if (first_use_on_this_device(attr_mask))
+    (void)hipFuncSetAttribute((const void*)lu_leftlook_kernel<NB, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LL_LDS);
+  const int nprev = (int)(jb / NB);
+  for (int ip0 = 0; ip0 < nprev; ip0 += ll_group<NB>()) {      // (more than four 64-column blocks: one launch per four)
+    const int ip1 = std::min(nprev, ip0 + ll_group<NB>());
+    const size_t shmem = (size_t)(ip1 - ip0) * NB * (NB + 2) * sizeof(double);
+    hipLaunchKernelGGL((lu_leftlook_kernel<NB, WIDE>), dim3(grid), dim3(LL_BS), shmem, st, Y, ld, m, jb, tc, ip0, ip1, U12, ldu);
+  }
+}
+// Step 1 of block [jb, jb + b) (jb > 0): its columns, rows [jb, m), brought up to date with every block to their left.
+static void lu_ll_update(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, int64_t jb, int b, int nb,
+                         const double* u12) {
+  if (jb == 0 || m <= jb) return;
+  int dev = 0, ncu = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
+  const int64_t chunks = (m - jb + 15) / 16;
+  const unsigned grid = (unsigned)std::min<int64_t>((chunks + LL_WAVES - 1) / LL_WAVES, ncu);   // one workgroup per CU
+  const bool wide = (3 * ld + 32) * (int64_t)sizeof(double) >= ((int64_t)1 << 32);
+  const int64_t ldu = (int64_t)nb * l;
+  if (nb == 64) {
+    if (wide) launch_leftlook_v<64, true>(st, grid, Y, ld, m, jb, b, u12, ldu);
+    else launch_leftlook_v<64, false>(st, grid, Y, ld, m, jb, b, u12, ldu);
+  } else {
+    if (wide) launch_leftlook_v<32, true>(st, grid, Y, ld, m, jb, b, u12, ldu);
+    else launch_leftlook_v<32, false>(st, grid, Y, ld, m, jb, b, u12, ldu);
+  }
+}
+// Step 3 of the full block at jb (after its leaves): U12 of the block for every trailing column [jb + nb, l).
+static void lu_ll_urows(hipStream_t st, const double* Y, int64_t ld, int64_t l, int64_t jb, int nb, double* u12) {
+  const int64_t c0 = jb + nb, ldu = (int64_t)nb * l;
+  if (c0 >= l) return;
+  const unsigned gu = (unsigned)((l - c0 + 63) / 64);
+  double* out = u12 + (jb / nb) * ldu + c0 * nb;
+  if (nb == 64) {
+    if (jb == 0) hipLaunchKernelGGL(lu_u12_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, out);
+    else hipLaunchKernelGGL(lu_urows_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, (int)(jb / nb), c0, l, u12, ldu, out);
+  } else {
+    if (jb == 0) hipLaunchKernelGGL(lu_u12_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, out);
+    else hipLaunchKernelGGL(lu_urows_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, (int)(jb / nb), c0, l, u12, ldu, out);
+  }
 }
 
 // top l x l: unit diagonal, zero strict upper triangle (what Julia's F.L returns)
@@ -1376,6 +1598,7 @@ void lu2_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const Lu
   const int nb = w.nb;
   for (int64_t jb = 0; jb < l; jb += nb) {
     const int b = (int)((l - jb < nb) ? (l - jb) : nb);
+    lu_ll_update(st, Y, ld, m, l, jb, b, nb, w.u12);       // left-looking: this block's columns, once, before its leaves
     for (int64_t j0 = jb; j0 < jb + b; j0 += LW) {
       const int wd = (int)((jb + b - j0 < LW) ? (jb + b - j0) : LW);
       // every leaf keeps the same grid: workgroups whose rows lie beyond m still take part in the exchange
@@ -1385,19 +1608,7 @@ void lu2_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const Lu
       else launch_leaf<512, 8>(st, w.grid, Y, ld, m, l, jb, j0, wd, w, epoch);
       epoch += (uint32_t)LW;            // a narrow last leaf still runs (gated) 8 steps
     }
-    const int64_t c0 = jb + b, t = l - c0;
-    if (t > 0) {                               // only full blocks have columns to their right
-      const int64_t mr = m - c0;
-      const unsigned gu = (unsigned)((t + 63) / 64);
-      const unsigned gr = (unsigned)((mr + 127) / 128);
-      if (b == 64) {
-        hipLaunchKernelGGL(lu_u12_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, w.u12);
-        if (mr > 0) launch_rankk<64>(st, gr, Y, ld, m, c0, jb, c0, t, w.u12);
-      } else {
-        hipLaunchKernelGGL(lu_u12_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, w.u12);
-        if (mr > 0) launch_rankk<32>(st, gr, Y, ld, m, c0, jb, c0, t, w.u12);
-      }
-    }
+    lu_ll_urows(st, Y, ld, l, jb, nb, w.u12);              // only full blocks have columns to their right
   }
   int eb = (int)((l * l + 255) / 256);
   if (eb > 1024) eb = 1024;
@@ -1775,7 +1986,7 @@ static int lu3_grid(int64_t rows) {
 }  // namespace
 
 size_t lu3_work_bytes(int64_t l) {
-  return sizeof(double) * T_MAXWG + sizeof(int64_t) * T_MAXWG + sizeof(Lu3State) + sizeof(double) * (size_t)LU2_NB * (size_t)l +
+  return sizeof(double) * T_MAXWG + sizeof(int64_t) * T_MAXWG + sizeof(Lu3State) + sizeof(double) * (size_t)l * (size_t)l +
          sizeof(int32_t) * (size_t)(l + 4) + 512;
 }
 
@@ -1784,13 +1995,14 @@ void lu3_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, void* wo
   double* pval = (double*)base; base += sizeof(double) * T_MAXWG;
   int64_t* pidx = (int64_t*)base; base += sizeof(int64_t) * T_MAXWG;
   Lu3State* stt = (Lu3State*)base; base += sizeof(Lu3State);
-  double* u12 = (double*)base; base += sizeof(double) * (size_t)LU2_NB * (size_t)l;
+  double* u12 = (double*)base; base += sizeof(double) * (size_t)l * (size_t)l;   // U12 of every block (lu_ll_urows)
   int32_t* ipiv = (int32_t*)base;
   *ipiv_out = ipiv;
   const int nb = LU2_NB;
   static const bool fuse = !(getenv("GSI_LU_TALL_NOFUSE") != nullptr);     // A/B: every leaf closed by a pass of its own
   for (int64_t jb = 0; jb < l; jb += nb) {
     const int b = (int)((l - jb < nb) ? (l - jb) : nb);
+    lu_ll_update(st, Y, ld, m, l, jb, b, nb, u12);         // the register-resident path's own block order
     for (int64_t j0 = jb; j0 < jb + b; j0 += LW) {
       const int wd = (int)((jb + b - j0 < LW) ? (jb + b - j0) : LW);
       Lu3Step p{Y, ld, m, (int32_t)l, (int32_t)j0, 0, wd, pval, pidx, stt, ipiv, info};
@@ -1817,14 +2029,7 @@ void lu3_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, void* wo
       if (m > j0 + wd && !next_opens)
         hipLaunchKernelGGL(lu3_close_kernel, dim3(lu3_grid(m - j0 - wd)), dim3(T_BS), 0, st, Y, ld, m, (int32_t)j0, wd, stt);
     }
-    const int64_t c0 = jb + b, t = l - c0;
-    if (t > 0) {                               // the register-resident path's own block update
-      const int64_t mr = m - c0;
-      const unsigned gu = (unsigned)((t + 63) / 64);
-      const unsigned gr = (unsigned)((mr + 127) / 128);
-      hipLaunchKernelGGL(lu_u12_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, u12);
-      if (mr > 0) launch_rankk<64>(st, gr, Y, ld, m, c0, jb, c0, t, u12);
-    }
+    lu_ll_urows(st, Y, ld, l, jb, nb, u12);
   }
   int eb = (int)((l * l + 255) / 256);
   if (eb > 1024) eb = 1024;

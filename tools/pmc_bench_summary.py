@@ -50,7 +50,8 @@ def phase(prefixes, count_name, per_unit):
             "algorithmic_bytes": 16.0 * n * l,
             "traffic_over_one_read_plus_write": ((fb + wb) / units / (16.0 * n * l)) if units else None}
 
-res["lu"] = phase(["lu_leaf_kernel", "lu_rankk_kernel", "lu_u12_kernel", "lu2_extract"], "lu_leaf_kernel", l // 8)
+LU_KERNELS = ["lu_leaf_kernel", "lu_leftlook_kernel", "lu_urows_kernel", "lu_rankk_kernel", "lu_u12_kernel", "lu2_extract"]
+res["lu"] = phase(LU_KERNELS, "lu_leaf_kernel", l // 8)
 
 def per_kernel(prefixes, units):
     """HBM bytes per factorization, kernel by kernel (sum over that kernel's launches / factorizations)."""
@@ -68,19 +69,20 @@ def per_kernel(prefixes, units):
 
 if res["lu"]["factorizations"]:
     # What the blocking MUST move, in passes over one 8 MB column of the panel: a leaf reads its 8 columns and
-    # the kp = 0, 8, .., 56 finished columns of its 64-column block and writes its 8 (352 per block); the rank-64 update of
-    # block b reads the block's 64 columns of L and reads + writes the t trailing columns (64 + 2 t).
+    # the kp = 0, 8, .., 56 finished columns of its 64-column block and writes its 8 (352 per block); left-looking between the
+    # blocks, block b >= 1 is brought up to date once before its leaves: it reads the 64 b finished columns of L to its left and
+    # reads + writes its own 64 (64 b + 128).
     col = 8.0 * n
     nblk = (l + 63) // 64
     leaf_r = sum(8 + 8 * i for b in range(nblk) for i in range(min(8, (l - 64 * b + 7) // 8)))
     leaf_w = 8 * ((l + 7) // 8)
-    rk_r = sum(64 + max(l - 64 * (b + 1), 0) for b in range(nblk) if l - 64 * (b + 1) > 0)
-    rk_w = sum(max(l - 64 * (b + 1), 0) for b in range(nblk))
-    res["lu"]["per_kernel"] = per_kernel(["lu_leaf_kernel", "lu_rankk_kernel", "lu_u12_kernel", "lu2_extract"], res["lu"]["factorizations"])
+    up_r = sum(64 * b + min(64, l - 64 * b) for b in range(1, nblk))
+    up_w = sum(min(64, l - 64 * b) for b in range(1, nblk))
+    res["lu"]["per_kernel"] = per_kernel(LU_KERNELS, res["lu"]["factorizations"])
     res["lu"]["minimum_of_this_blocking"] = {
-        "column_passes": {"leaves_read": leaf_r, "leaves_write": leaf_w, "rank64_read": rk_r, "rank64_write": rk_w},
-        "bytes": {"leaves": (leaf_r + leaf_w) * col, "rank64_updates": (rk_r + rk_w) * col, "total": (leaf_r + leaf_w + rk_r + rk_w) * col},
-        "note": "64-column blocks, 8-column register-resident leaves, left-looking inside a block, one rank-64 update per block"}
+        "column_passes": {"leaves_read": leaf_r, "leaves_write": leaf_w, "block_update_read": up_r, "block_update_write": up_w},
+        "bytes": {"leaves": (leaf_r + leaf_w) * col, "block_updates": (up_r + up_w) * col, "total": (leaf_r + leaf_w + up_r + up_w) * col},
+        "note": "64-column blocks, 8-column register-resident leaves, left-looking inside a block and between the blocks"}
     res["lu"]["traffic_over_minimum_of_this_blocking"] = res["lu"]["hbm_bytes_per_factorization"] / res["lu"]["minimum_of_this_blocking"]["bytes"]["total"]
 # CholeskyQR2: two Gram matrices (sy_kernel: the panel is read once per half) + two triangular products per factorization;
 # the thin-SVD factorization's second product runs in the general kernel and is not counted here

@@ -11,7 +11,8 @@ import statistics
 import sys
 
 FAMILIES = [
-    ("lu", ("lu_leaf_kernel", "lu_rankk_kernel", "lu_u12_kernel", "lu2_extract_L_kernel", "lu3_")),
+    ("lu", ("lu_leaf_kernel", "lu_leftlook_kernel", "lu_urows_kernel", "lu_rankk_kernel", "lu_u12_kernel", "lu2_extract_L_kernel",
+            "lu3_")),
     ("svd", ("jacobi_",)),
     ("qr_small", ("cq_", "sy_reduce_kernel", "splitk_reduce_kernel")),
     ("qr_tall", ("sy_kernel", "tr_kernel")),
