@@ -260,6 +260,42 @@ def fft_powerlaw_operator(ctx, Ns, beta, fftrf=False):
     return Operator(ctx, h)
 
 
+def fft_gridcov_operator(ctx, Ns, kind="exponential", ell=1.0, theta=0.0, sigma2=1.0, nugget=0.0, table=None,
+                         table_mirror=None):
+    """A covariance function on a regular grid as the matrix-free FFT operator (`gsi_op_fft_gridcov[_table]`):
+    A[i, j] = sigma2 * k(r) + nugget * [i == j], r^2 = sum_a (u_a / ell[a])^2, u = the lag i - j per axis (in 2-D rotated by
+    `theta`), k by name through `POINTCOV_KINDS`; unit grid spacing, points in Julia's vec() order, `Ns` = 1 to 3 axes of at
+    most 4096 points.  `ell`: one length (isotropic) or one per axis.  `table` (array of shape Ns, table[t0, t1, t2] = c(t) for
+    t >= 0) replaces kind / ell / theta / sigma2 by any kernel that is even along every axis; in 2-D `table_mirror`
+    (table_mirror[t0, t1] = c(t0, -t1)) makes it any centrally symmetric one.  For Ns = (ny, nx) it is the matrix of
+    `gridcov_implicit_operator(nx, ny, ...)` in the same point order (its `table` is this one's transposed: table.T), at
+    O(n log n) per column instead of O(n^2)."""
+    Ns = [int(v) for v in Ns]
+    arr = (C.c_int64 * len(Ns))(*Ns)
+    h = C.c_void_p()
+    if table is not None:
+        def lags(t, name):
+            t = np.asarray(t, dtype=np.float64)
+            if t.shape != tuple(Ns):
+                raise ValueError(f"{name} must have the shape of the grid, {tuple(Ns)}")
+            return np.asfortranarray(t)          # table[t0 + N0 (t1 + N1 t2)]
+        t = lags(table, "table")
+        tm = lags(table_mirror, "table_mirror") if table_mirror is not None else None
+        L.check(ctx.lib.gsi_op_fft_gridcov_table(ctx.h, C.byref(h), len(Ns), arr, t.ctypes.data_as(L.c_dp),
+                                                 tm.ctypes.data_as(L.c_dp) if tm is not None else None, float(nugget)), ctx.lib)
+        return Operator(ctx, h)
+    if table_mirror is not None:
+        raise ValueError("table_mirror needs table")
+    k = POINTCOV_KINDS[kind] if isinstance(kind, str) else int(kind)
+    ells = [float(ell)] * len(Ns) if np.ndim(ell) == 0 else [float(v) for v in ell]
+    if len(ells) != len(Ns):
+        raise ValueError("ell must be one length or one per axis")
+    earr = (C.c_double * len(ells))(*ells)
+    L.check(ctx.lib.gsi_op_fft_gridcov(ctx.h, C.byref(h), len(Ns), arr, k, earr, float(theta), float(sigma2), float(nugget)),
+            ctx.lib)
+    return Operator(ctx, h)
+
+
 class DeviceMatrix(_Handle):
     """Column-major Float64 matrix resident in HBM (`gsi_mat`)."""
     _destroy = "gsi_mat_destroy"

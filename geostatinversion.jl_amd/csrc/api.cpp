@@ -414,6 +414,70 @@ int gsi_op_fft_powerlaw_fftrf(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_
   return guarded([&] { make_fft_powerlaw(ctx, op, ndims, N, beta, 1); });
 }
 
+// The FFT operator for a covariance function (kind / ell / theta / sigma2) or a table of lags (table / table_mirror) on the
+// grid: OP_FFT_COV with another plan (Backend::fftcov_create_lags).  The arguments are checked here; the limit on the embedded
+// points (2^31) is the backend's, as for the power-law plans: refused before it allocates anything.
+static void make_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, int kind, const double* ell, double theta,
+                             double sigma2, double nugget, const double* table, const double* table_mirror, bool from_table) {
+  REQUIRE(ctx && op && N, "NULL argument");
+  *op = nullptr;
+  REQUIRE(ndims >= 1 && ndims <= 3, "fft covariance: 1, 2 or 3 grid dimensions");
+  int64_t N3[3] = {1, 1, 1};
+  int64_t n = 1;
+  for (int a = 0; a < ndims; ++a) {
+    REQUIRE(N[a] >= 1, "fft covariance: grid dimensions must be >= 1");
+    // (the backend's limit and message, repeated here because the tables below are read with n = prod N[a] entries first)
+    REQUIRE(N[a] <= 4096, "fft covariance: at most 4096 grid points per axis (a line must fit LDS)");
+    N3[a] = N[a];
+    n *= N[a];
+  }
+  REQUIRE(n >= 2, "fft covariance: need at least two grid points");
+  REQUIRE(std::isfinite(nugget) && nugget >= 0.0, "fft grid covariance: nugget must be finite and >= 0");
+  double ell3[3] = {1.0, 1.0, 1.0};
+  if (from_table) {
+    REQUIRE(table, "fft grid covariance: table is NULL");
+    REQUIRE(table_mirror == nullptr || ndims == 2, "fft grid covariance: table_mirror is for 2-D grids only");
+    for (int64_t e = 0; e < n; ++e) REQUIRE(std::isfinite(table[e]), "fft grid covariance: table entries must be finite");
+    if (table_mirror) {
+      for (int64_t e = 0; e < n; ++e)
+        REQUIRE(std::isfinite(table_mirror[e]), "fft grid covariance: table_mirror entries must be finite");
+      // c(t0, -t1) = c(t0, t1) where t0 == 0 (central symmetry) or t1 == 0 (the same lag)
+      auto agree = [](double a, double b) { return std::fabs(a - b) <= 1e-12 * std::max(std::fabs(a), std::fabs(b)); };
+      for (int64_t t0 = 0; t0 < N3[0]; ++t0)
+        REQUIRE(agree(table[t0], table_mirror[t0]), "fft grid covariance: table_mirror must agree with table where t1 == 0");
+      for (int64_t t1 = 0; t1 < N3[1]; ++t1)
+        REQUIRE(agree(table[t1 * N3[0]], table_mirror[t1 * N3[0]]),
+                "fft grid covariance: table_mirror must agree with table where t0 == 0 (c(-t) = c(t))");
+    }
+  } else {
+    REQUIRE(kind >= 0 && kind < pointcov::NUM_KINDS, "fft grid covariance: kind 0 Gaussian, 1 exponential, 2 Matern 3/2, 3 Matern 5/2");
+    REQUIRE(ell, "fft grid covariance: ell is NULL");
+    for (int a = 0; a < ndims; ++a) {
+      REQUIRE(std::isfinite(ell[a]) && ell[a] > 0.0, "fft grid covariance: every ell[a] must be finite and > 0");
+      ell3[a] = ell[a];
+    }
+    REQUIRE(std::isfinite(sigma2) && sigma2 > 0.0, "fft grid covariance: sigma2 must be finite and > 0");
+    REQUIRE(std::isfinite(theta), "fft grid covariance: theta must be finite");
+    REQUIRE(theta == 0.0 || ndims == 2, "fft grid covariance: theta (a rotation) is for 2-D grids only");
+  }
+  std::unique_ptr<gsi_op> o(new gsi_op());
+  Operator& A = o->op;
+  A.ctx = &ctx->c; A.kind = OP_FFT_COV; A.m = n; A.n = n; A.ld = 0;
+  default_shard(n, ctx->c.nranks(), ctx->c.rank(), &A.row0, &A.mloc);     // as make_fft_powerlaw: the plan is replicated
+  A.plan = ctx->c.be->fftcov_create_lags(N3, kind, ell3, theta, sigma2, nugget, table, table_mirror);
+  *op = o.release();
+}
+
+int gsi_op_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, int kind, const double* ell, double theta,
+                       double sigma2, double nugget) {
+  return guarded([&] { make_fft_gridcov(ctx, op, ndims, N, kind, ell, theta, sigma2, nugget, nullptr, nullptr, false); });
+}
+
+int gsi_op_fft_gridcov_table(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, const double* table,
+                             const double* table_mirror, double nugget) {
+  return guarded([&] { make_fft_gridcov(ctx, op, ndims, N, 0, nullptr, 0.0, 1.0, nugget, table, table_mirror, true); });
+}
+
 int gsi_op_destroy(gsi_op* op) {
   return guarded([&] { delete op; });
 }

@@ -91,6 +91,16 @@ class Backend {
   // embedding: A = R F^-1 diag(lambda) F R', lambda(k) = |k|^beta, unit diagonal (fft_cov.hip).  Opaque plan.
   // fftrf != 0: FFTRF.jl's own convention -- embedding of exactly 2 N[a] points, integer wavenumbers (FFTRF.jl:83-90)
   virtual void* fftcov_create(const int64_t N[3], double beta, int fftrf) = 0;
+  // The same plan type for a covariance FUNCTION on the grid (gsi_op_fft_gridcov[_table] in include/gsi_hip.h):
+  // A(i, j) = c(i - j) + nugget [i == j], c = sigma2 k(r) with pointcov.hpp's kinds, per-axis lengths ell[3] and the 2-D
+  // rotation theta -- or, if table != null (host pointers), c(t) = table[t0 + N0 (t1 + N1 t2)] for t_a >= 0 and, for a
+  // centrally symmetric 2-D kernel, table_mirror[t0 + N0 t1] = c(t0, -t1) (null: even along every axis).  Arguments are
+  // validated by the caller.  Applied and destroyed like any other plan.
+  virtual void* fftcov_create_lags(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2,
+                                   double nugget, const double* table, const double* table_mirror) {
+    (void)N; (void)kind; (void)ell; (void)theta; (void)sigma2; (void)nugget; (void)table; (void)table_mirror;
+    throw Error(1 /* GSI_ERR_ARG */, "fft covariance from a covariance function or table: not supported by this backend");
+  }
   virtual void fftcov_destroy(void* plan) = 0;
   // Y (n x l, ld ldy) = A X (n x l, ld ldx)
   virtual void fftcov_apply(void* plan, int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy) = 0;

@@ -517,7 +517,7 @@ size_t fft_plan_doubles(const int64_t M[3]) { return (size_t)(M[0] * M[1] * M[2]
 
 void fft_spectrum(hipStream_t st, double* lam, double* part64, const int64_t M[3], double beta, int fftrf) {
   const int64_t Mtot = M[0] * M[1] * M[2];
-  hipLaunchKernelGGL(fft_twiddle_kernel, dim3(FFT_TW_LEN / 2 / 256), dim3(256), 0, st, reinterpret_cast<double2*>(lam + Mtot + 64));
+  fft_plan_twiddles(st, lam, M);
   const int64_t mlast = (M[2] > 1) ? M[2] : ((M[1] > 1) ? M[1] : Mtot);      // d = 1: one line, natural order
   hipLaunchKernelGGL(fft_spectrum_kernel, dim3(grid_for(Mtot, 4096)), dim3(256), 0, st, lam, Mtot, M[0], M[1], M[2], beta, fftrf,
                      Mtot / mlast, mlast);
@@ -564,10 +564,15 @@ void fft_spectrum_natural(hipStream_t st, double* lam, const int64_t M[3], doubl
   hipLaunchKernelGGL(fft_spectrum_kernel, dim3(grid_for(Mtot, 4096)), dim3(256), 0, st, lam, Mtot, M[0], M[1], M[2], beta, fftrf,
                      (int64_t)1, Mtot);
 }
+// the twiddle table alone, where fft_spectrum / fft_finish_plan leave it (plans finished elsewhere: fft_gridcov_plan.hip)
+void fft_plan_twiddles(hipStream_t st, double* lam, const int64_t M[3]) {
+  const int64_t Mtot = M[0] * M[1] * M[2];
+  hipLaunchKernelGGL(fft_twiddle_kernel, dim3(FFT_TW_LEN / 2 / 256), dim3(256), 0, st, reinterpret_cast<double2*>(lam + Mtot + 64));
+}
 // lam[0, Mtot) *= 1 / sum (unit diagonal); twiddle table behind the 64 scratch doubles, as fft_spectrum leaves them
 void fft_finish_plan(hipStream_t st, double* lam, double* part64, const int64_t M[3]) {
   const int64_t Mtot = M[0] * M[1] * M[2];
-  hipLaunchKernelGGL(fft_twiddle_kernel, dim3(FFT_TW_LEN / 2 / 256), dim3(256), 0, st, reinterpret_cast<double2*>(lam + Mtot + 64));
+  fft_plan_twiddles(st, lam, M);
   hipLaunchKernelGGL(fft_sum_kernel, dim3(64), dim3(256), 0, st, lam, Mtot, part64);
   hipLaunchKernelGGL(fft_normalise_kernel, dim3(grid_for(Mtot, 4096)), dim3(256), 0, st, lam, Mtot, part64, 64);
 }

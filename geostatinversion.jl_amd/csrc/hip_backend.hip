@@ -401,18 +401,22 @@ class HipBackend : public Backend {
 
   // ---- matrix-free FFT covariance ----
   struct FftCov { int64_t N[3], M[3]; double* lam; double* W; int nb_max; };
-  void* fftcov_create(const int64_t N[3], double beta, int fftrf) override {
-    bind();
+  // every temporary of a plan's construction goes back to the block cache on every exit path (a throwing HIP_CHECK
+  // or allocation between alloc and release leaked pooled blocks)
+  struct Hold { HipBackend* be; double* p; ~Hold() { if (p) be->release(p); } };
+  // the grid squeezed of its singleton axes, its embedding, the limits, and the plan's two arrays (spectrum, work array);
+  // *reembed: FFTRF's exact 2 N embedding is not a power of two on some axis
+  std::unique_ptr<FftCov> fftcov_new_plan(const int64_t N[3], int fftrf, bool* reembed, int* dims) {
     std::unique_ptr<FftCov> p(new FftCov());
     int64_t Mtot = 1;
     int d = 0;
     for (int a = 0; a < 3; ++a) { p->N[a] = 1; p->M[a] = 1; }
-    bool reembed = false;                // FFTRF's exact 2 N embedding is not a power of two on some axis
+    *reembed = false;
     for (int a = 0; a < 3; ++a) {        // squeeze singleton axes: vec() of a 1 x 50 field is a 50-point line
       if (N[a] < 1) throw Error(GSI_ERR_ARG, "fft covariance: grid dimensions must be >= 1");
       if (N[a] == 1) continue;
       p->N[d] = N[a]; p->M[d] = hipk::fft_embed_size(N[a]);
-      if (fftrf && p->M[d] != 2 * N[a]) reembed = true;
+      if (fftrf && p->M[d] != 2 * N[a]) *reembed = true;
       if (p->M[d] > 8192) throw Error(GSI_ERR_ARG, "fft covariance: at most 4096 grid points per axis (a line must fit LDS)");
       Mtot *= p->M[d];
       ++d;
@@ -432,6 +436,50 @@ class HipBackend : public Backend {
     p->nb_max = (int)std::max<int64_t>(1, std::min<int64_t>(nb, 64));
     p->lam = alloc(hipk::fft_plan_doubles(p->M));
     try { p->W = alloc((size_t)2 * Mtot * p->nb_max); } catch (...) { release(p->lam); throw; }
+    *dims = d;
+    return p;
+  }
+  // One per-axis factor of the re-embedding, applied to the FASTEST axis of the array in bufh (dimensions cur, tot elements,
+  // d real axes) as cur' = cur^T B (the contraction kernel's A'B form: the array as a k x rest matrix), which also rotates
+  // that axis to the back: d applications restore the natural order.
+  enum FftFactor { FFT_F_COS = 0, FFT_F_COS_WEIGHTED = 1, FFT_F_SIN_WEIGHTED = 2 };
+  void fft_rotate_apply(Hold& bufh, int64_t cur[3], int64_t& tot, int d, int64_t rows_out, int64_t period, FftFactor f) {
+    double*& buf = bufh.p;
+    // cur = (k, rest) column-major; B = k x rows_out; result (rest x rows_out) = the array with axis 0 replaced and last
+    const int64_t k = cur[0], rest = (tot / k);
+    Hold Bh{this, alloc((size_t)k * rows_out)};
+    double* B = Bh.p;
+    // B[kk + t k] : weighted (the D and S factors) is indexed [t = row of the INPUT, k' = output]; unweighted [k, t]
+    if (f == FFT_F_COS) hipk::fft_cos_matrix(st_, B, k, rows_out, period, false);              // C_a^T: B[k, t]
+    else if (f == FFT_F_COS_WEIGHTED) hipk::fft_cos_matrix(st_, B, k, rows_out, period, true);  // D_a^T: B[t, k'] = w_t cos(.)
+    else hipk::fft_sin_matrix(st_, B, k, rows_out, period);                                   // S_a^T: B[t, k'] = w_t sin(.)
+    Hold outh{this, alloc((size_t)rest * rows_out)};
+    double* out = outh.p;
+    double* ws = gemm_ws(hipk::gemm_workspace_doubles(rest, rows_out, k));
+    hipk::gemm_f64(st_, true, rest, rows_out, k, 1.0, buf, k, B, k, 0.0, out, rest, ws);
+    check_launch("fft re-embedding product");
+    release(buf);
+    buf = out;
+    outh.p = nullptr;
+    tot = rest * rows_out;
+    // rotate the dimension list: (k, c1, c2) -> (c1, c2, rows_out) over the d real axes
+    int64_t nd[3] = {1, 1, 1};
+    for (int a = 0; a + 1 < d; ++a) nd[a] = cur[a + 1];
+    nd[d - 1] = rows_out;
+    for (int a = 0; a < 3; ++a) cur[a] = nd[a];
+  }
+  // The second half of the re-embedding, shared by the power-law and the covariance-function plans: the lags of a kernel over
+  // the box (bufh: N[0] x N[1] x N[2], natural order) -> (x_a D_a) c on the power-of-two embedding M, natural order; with
+  // sine = true (x_a S_a) c, the odd-odd part of a centrally symmetric 2-D kernel.
+  void fftcov_lags_to_spectrum(Hold& bufh, int64_t cur[3], int64_t& tot, const FftCov* p, int d, bool sine) {
+    for (int a = 0; a < d; ++a) fft_rotate_apply(bufh, cur, tot, d, p->M[a], p->M[a], sine ? FFT_F_SIN_WEIGHTED : FFT_F_COS_WEIGHTED);
+  }
+  void* fftcov_create(const int64_t N[3], double beta, int fftrf) override {
+    bind();
+    bool reembed = false;
+    int d = 0;
+    std::unique_ptr<FftCov> p = fftcov_new_plan(N, fftrf, &reembed, &d);
+    const int64_t Mtot = p->M[0] * p->M[1] * p->M[2];
     if (!reembed) {
       hipk::fft_spectrum(st_, p->lam, p->lam + Mtot, p->M, beta, fftrf);
       check_launch("fft_spectrum");
@@ -441,48 +489,62 @@ class HipBackend : public Backend {
     // through the power-of-two passes with a re-embedded spectrum (fft_cov.hip, "FFTRF's convention on a grid ...").
     //   c  = (x_a C_a) lambda_{2N}    C_a[t, k]  = cos(2 pi t k / 2 N_a),            t < N_a, k < 2 N_a     (lags 0 .. N_a - 1)
     //   l' = (x_a D_a) c              D_a[k', t] = w_t cos(2 pi t k' / M'_a), w_0 = 1, w_t = 2              (c' even, 0 beyond)
-    // Each factor is applied to the FASTEST axis as cur' = cur^T B (the contraction kernel's A'B form: the array as a
-    // k x rest matrix), which also rotates that axis to the back: d applications restore the natural order.
     try {
       int64_t cur[3] = {1, 1, 1};
       for (int a = 0; a < d; ++a) cur[a] = 2 * p->N[a];
       int64_t tot = cur[0] * cur[1] * cur[2];
-      // every temporary of the re-embedding goes back to the block cache on every exit path (a throwing HIP_CHECK
-      // or allocation between alloc and release leaked pooled blocks)
-      struct Hold { HipBackend* be; double* p; ~Hold() { if (p) be->release(p); } } bufh{this, nullptr};
+      Hold bufh{this, nullptr};
       bufh.p = alloc((size_t)tot);
-      double*& buf = bufh.p;
-      hipk::fft_spectrum_natural(st_, buf, cur, beta, 1);
-      auto rotate_apply = [&](int64_t rows_out, int64_t period, bool weighted) {
-        // cur = (k, rest) column-major; B = k x rows_out; result (rest x rows_out) = the array with axis 0 replaced and last
-        const int64_t k = cur[0], rest = (tot / k);
-        Hold Bh{this, alloc((size_t)k * rows_out)};
-        double* B = Bh.p;
-        // B[kk + t k] : weighted (the D factors) is indexed [t = row of the INPUT, k' = output]; unweighted [k, t]
-        if (!weighted) hipk::fft_cos_matrix(st_, B, k, rows_out, period, false);          // C_a^T: B[k, t]
-        else hipk::fft_cos_matrix(st_, B, k, rows_out, period, true);                     // D_a^T: B[t, k'] = w_t cos(.)
-        Hold outh{this, alloc((size_t)rest * rows_out)};
-        double* out = outh.p;
-        double* ws = gemm_ws(hipk::gemm_workspace_doubles(rest, rows_out, k));
-        hipk::gemm_f64(st_, true, rest, rows_out, k, 1.0, buf, k, B, k, 0.0, out, rest, ws);
-        check_launch("fft re-embedding product");
-        release(buf);
-        buf = out;
-        outh.p = nullptr;
-        tot = rest * rows_out;
-        // rotate the dimension list: (k, c1, c2) -> (c1, c2, rows_out) over the d real axes
-        int64_t nd[3] = {1, 1, 1};
-        for (int a = 0; a + 1 < d; ++a) nd[a] = cur[a + 1];
-        nd[d - 1] = rows_out;
-        for (int a = 0; a < 3; ++a) cur[a] = nd[a];
-      };
-      for (int a = 0; a < d; ++a) rotate_apply(p->N[a], 2 * p->N[a], false);   // lags 0 .. N_a - 1 of c
-      for (int a = 0; a < d; ++a) rotate_apply(p->M[a], p->M[a], true);        // the spectrum of the re-embedded kernel
-      hipk::fft_lines_layout(st_, buf, p->lam, p->M);
+      hipk::fft_spectrum_natural(st_, bufh.p, cur, beta, 1);
+      for (int a = 0; a < d; ++a) fft_rotate_apply(bufh, cur, tot, d, p->N[a], 2 * p->N[a], FFT_F_COS);   // lags 0 .. N_a - 1 of c
+      fftcov_lags_to_spectrum(bufh, cur, tot, p.get(), d, false);              // the spectrum of the re-embedded kernel
+      hipk::fft_lines_layout(st_, bufh.p, p->lam, p->M);
       hipk::fft_finish_plan(st_, p->lam, p->lam + Mtot, p->M);
       check_launch("fft re-embedded spectrum");
-      release(buf);
-      buf = nullptr;                                          // (bufh's destructor must not release it a second time)
+    } catch (...) {
+      release(p->W); release(p->lam);
+      throw;
+    }
+    return p.release();
+  }
+  // The same operator type for a covariance FUNCTION of the grid lags (gsi_op_fft_gridcov[_table]):
+  //   lambda' = (x_a D_a) c                              kernels even along every axis
+  //   lambda' = (D_0 x D_1) c_ee - (S_0 x S_1) c_oo      centrally symmetric 2-D kernels (cos(a + b) = cos a cos b - sin a sin b;
+  //                                                      c_ee, c_oo = half the sum / difference of the lags (t0, t1), (t0, -t1))
+  // stored as (lambda' + nugget) / Mtot: no unit diagonal, and nugget * I on the box exactly.
+  void* fftcov_create_lags(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, double nugget,
+                           const double* table, const double* table_mirror) override {
+    bind();
+    bool reembed = false;
+    int d = 0;
+    std::unique_ptr<FftCov> p = fftcov_new_plan(N, 0, &reembed, &d);
+    try {
+      int64_t cur[3] = {p->N[0], p->N[1], p->N[2]};      // singleton axes do not move an element of the lag table
+      int64_t tot = cur[0] * cur[1] * cur[2];
+      // a second quadrant only where it differs from the first: both axes of a 2-D grid longer than one point
+      const bool mirrored = (table ? table_mirror != nullptr : theta != 0.0) && d == 2 && N[2] == 1;
+      Hold cp{this, nullptr}, cm{this, nullptr};
+      cp.p = alloc((size_t)tot);
+      if (mirrored) cm.p = alloc((size_t)tot);
+      if (table) {
+        upload2d(cp.p, tot, table, tot, tot, 1);
+        if (mirrored) upload2d(cm.p, tot, table_mirror, tot, tot, 1);
+      } else {
+        const double inv_ell[3] = {1.0 / ell[0], 1.0 / ell[1], 1.0 / ell[2]};
+        hipk::fft_lag_table(st_, cp.p, cm.p, N, kind, inv_ell, std::cos(theta), std::sin(theta), sigma2);
+        check_launch("fft_lag_table");
+      }
+      if (mirrored) {
+        hipk::fft_even_odd_split(st_, cp.p, cm.p, tot);
+        int64_t cur_s[3] = {cur[0], cur[1], cur[2]};
+        int64_t tot_s = tot;
+        fftcov_lags_to_spectrum(cm, cur_s, tot_s, p.get(), d, true);
+      }
+      fftcov_lags_to_spectrum(cp, cur, tot, p.get(), d, false);
+      if (mirrored) hipk::fft_subtract(st_, cp.p, cm.p, tot);
+      hipk::fft_lines_layout(st_, cp.p, p->lam, p->M);
+      hipk::fft_finish_plan_lags(st_, p->lam, p->M, nugget);
+      check_launch("fft covariance-function spectrum");
     } catch (...) {
       release(p->W); release(p->lam);
       throw;

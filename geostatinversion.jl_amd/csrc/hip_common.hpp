@@ -69,6 +69,16 @@ void fft_cos_matrix(hipStream_t st, double* out, int64_t rows, int64_t cols, int
 void fft_lines_layout(hipStream_t st, const double* nat, double* out, const int64_t M[3]);
 void fft_spectrum_natural(hipStream_t st, double* lam, const int64_t M[3], double beta, int fftrf);
 void fft_finish_plan(hipStream_t st, double* lam, double* part64, const int64_t M[3]);
+void fft_plan_twiddles(hipStream_t st, double* lam, const int64_t M[3]);   // the twiddle table of a plan, nothing else
+// ---- fft_gridcov_plan.hip: plans whose lags come from a covariance function or the caller's table ----
+// cp (and cm = the lags (t0, -t1) of a rotated 2-D kernel, or null) <- sigma2 k(r) over the box N, pointcov::kernel's kinds
+void fft_lag_table(hipStream_t st, double* cp, double* cm, const int64_t N[3], int kind, const double inv_ell[3], double cs,
+                   double sn, double sigma2);
+void fft_even_odd_split(hipStream_t st, double* cp, double* cm, int64_t total);   // -> ((c+ + c-) / 2, (c+ - c-) / 2)
+void fft_sin_matrix(hipStream_t st, double* out, int64_t rows, int64_t cols, int64_t period);   // w_r sin(2 pi r c / period)
+void fft_subtract(hipStream_t st, double* a, const double* b, int64_t total);     // a -= b
+// lam (line-by-line layout) <- (lam + nugget) / Mtot, twiddles behind it: no normalisation to a unit diagonal
+void fft_finish_plan_lags(hipStream_t st, double* lam, const int64_t M[3], double nugget);
 void fft_cov_apply(hipStream_t st, const int64_t N[3], const int64_t M[3], const double* lam, double2* W, int nb_max,
                    int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy);
 

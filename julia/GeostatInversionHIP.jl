@@ -231,6 +231,43 @@ function FFTPowerlawCovariance(Ns::Vector{Int}, beta::Float64; c::Context=ctx())
 	return op
 end
 
+"A covariance function on a regular grid as the matrix-free FFT operator (`gsi_op_fft_gridcov`):
+`A[i, j] = sigma2 * k(r) + nugget * (i == j)`, `r^2 = sum_a (u_a / ell[a])^2`, `u` = the lag `i - j` per axis (rotated by
+`theta` in 2-D), unit grid spacing, `kind` in `:gaussian`, `:exponential`, `:matern32`, `:matern52`.  Acts on `vec(field)`.
+For `Ns = [ny, nx]` it is the matrix of `GridCovImplicit(nx, ny, ...)` in the same point order, at O(n log n) per column."
+function FFTGridCovariance(Ns::Vector{Int}, kind::Symbol=:exponential; ell::Union{Float64,Vector{Float64}}=1.0,
+		theta::Float64=0.0, sigma2::Float64=1.0, nugget::Float64=0.0, c::Context=ctx())
+	k = Dict(:gaussian=>0, :exponential=>1, :matern32=>2, :matern52=>3)[kind]
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	N64 = Int64.(Ns)
+	ells = ell isa Float64 ? fill(ell, length(Ns)) : ell
+	length(ells) == length(Ns) || error("FFTGridCovariance: ell must be one length or one per axis")
+	check(ccall((:gsi_op_fft_gridcov, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Cint, Ptr{Int64}, Cint, Ptr{Float64}, Cdouble, Cdouble, Cdouble),
+		c.h, r, length(N64), N64, k, ells, theta, sigma2, nugget))
+	n = prod(Ns)
+	op = DeviceOperator(r[], c, n, n)
+	finalizer(finalize_op!, op)
+	return op
+end
+"The same operator for any stationary kernel given by its lags (`gsi_op_fft_gridcov_table`): `table[t0 + 1, t1 + 1, ...] =
+c(t)` for `t >= 0`, an array of the grid's own shape, even along every axis; in 2-D `mirror[t0 + 1, t1 + 1] = c(t0, -t1)`
+makes it any centrally symmetric kernel (rotated anisotropy, nested structures)."
+function FFTGridCovariance(table::Array{Float64}; mirror::Union{Nothing,Matrix{Float64}}=nothing, nugget::Float64=0.0,
+		c::Context=ctx())
+	(1 <= ndims(table) <= 3) || error("FFTGridCovariance: the table has 1 to 3 axes")
+	(mirror === nothing || size(mirror) == size(table)) || error("FFTGridCovariance: mirror must have the shape of table")
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	N64 = Int64[size(table)...]
+	check(ccall((:gsi_op_fft_gridcov_table, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Cint, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Cdouble),
+		c.h, r, length(N64), N64, table, mirror === nothing ? C_NULL : mirror, nugget))
+	n = length(table)
+	op = DeviceOperator(r[], c, n, n)
+	finalizer(finalize_op!, op)
+	return op
+end
+
 Base.size(A::DeviceOperator) = (A.m, A.n)
 function Base.size(A::DeviceOperator, i::Int)
 	(i == 1 || i == 2) || error("there is no $i-th dimension in a DeviceOperator")   # lowrank.jl:58
