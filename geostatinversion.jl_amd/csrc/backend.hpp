@@ -199,7 +199,7 @@ class Backend {
   // likewise, and svd(B) comes from the l x l factors; Z (n x l, ld ldz) = S C with C = N_s x K coefficients, its last l - K
   // columns zero, and Sv (l) the singular values.  false (declines, Z and Sv untouched): a Cholesky broke down, a second
   // round's Gram matrix was not near the identity, l > N - 1 (centred samples span N - 1 dimensions), or a shape it does not
-  // cover; the caller then forms Y = S (c T) and runs the ordinary path.
+  // cover; pipeline.cpp:randsvd_lowrank_single then forms Y = S (c T) and runs the ordinary deferred-Q ending.
   virtual bool lowrank_tail(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
                             int64_t K, double c, double* Z, int64_t ldz, double* Sv) {
     (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)l; (void)K; (void)c; (void)Z; (void)ldz; (void)Sv;
@@ -211,7 +211,7 @@ class Backend {
   //   T_next = S'L = G C + S[mv]' ((S[perm(mv)] - S[mv]) C)          (mv: the at most 2 l rows the interchanges move)
   // (N x l, ld N) with no n x l product.  false (declines; T_next undefined): (P S) C differs from the L in memory by more
   // than 1e-8 on the l pivot rows or a fixed sample of the others, the factorization flagged a zero pivot, or a shape it
-  // does not cover; the caller then forms S'L from L.
+  // does not cover; randsvd_lowrank_single then forms S'L from L, for this panel and the rest of the call.
   virtual bool lowrank_power_step(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T,
                                   const int32_t* ipiv, const double* L, int64_t ldl, int64_t l, double c, double* T_next) {
     (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)ipiv; (void)L; (void)ldl; (void)l; (void)c; (void)T_next;

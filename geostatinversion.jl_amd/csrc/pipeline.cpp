@@ -62,6 +62,29 @@ struct CommPhase {
 };
 static bool is_implicit(const Operator& A) { return A.kind == OP_GRIDCOV_IMPLICIT || A.kind == OP_POINTCOV; }
 
+// LowRankCovMatrix: A*X = S (S'X) / (N-1)   (lowrank.jl:115-121 as two tall-skinny products; adjoint(A) === A, :38-40).
+// T (N x l, ld N) = S'X from this rank's rows Xloc of X (ld ldx), summed over the ranks; a rank without rows adds zeros
+static void lowrank_StX(const Operator& A, const double* Xloc, int64_t ldx, int64_t l, double* T) {
+  Context& c = *A.ctx;
+  Backend* be = c.be.get();
+  {
+    ScopedPhase ph(be, PH_GEMM_T);
+    if (A.mloc > 0) be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, Xloc, ldx, 0.0, T, A.N);
+    else be->fill_zero(T, (size_t)A.N * l);
+  }
+  if (c.comm) {
+    CommPhase ph(c);
+    c.comm->allreduce_sum(T, (size_t)A.N * l);
+  }
+}
+// Yloc (mloc x l, ld ldy) = S (c T), c = 1 / (N - 1): this rank's rows of A*X
+static void lowrank_ScT(const Operator& A, const double* T, int64_t l, double* Yloc, int64_t ldy) {
+  if (A.mloc == 0) return;
+  Backend* be = A.ctx->be.get();
+  ScopedPhase ph(be, PH_GEMM_N);
+  be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T, A.N, 0.0, Yloc, ldy);
+}
+
 void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Yloc, int64_t ldy) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
@@ -111,43 +134,35 @@ void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* 
     implicit_mul(be, A, A.mloc, l, A.n, A.row0, 0, X, ldx, Yloc, ldy);
     return;
   }
-  // LowRankCovMatrix: A*X = S (S'X) / (N-1)   (lowrank.jl:115-121 as two tall-skinny products)
   Buf T(be, (size_t)A.N * l);
-  {
-    ScopedPhase ph(be, PH_GEMM_T);
-    if (A.mloc > 0) be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, X + A.row0, ldx, 0.0, T.p, A.N);
-    else be->fill_zero(T.p, (size_t)A.N * l);
-  }
-  if (c.comm) {
-    CommPhase ph(c);
-    c.comm->allreduce_sum(T.p, (size_t)A.N * l);
-  }
-  if (A.mloc > 0) {
-    ScopedPhase ph(be, PH_GEMM_N);
-    be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T.p, A.N, 0.0, Yloc, ldy);
-  }
+  lowrank_StX(A, X + A.row0, ldx, l, T.p);
+  lowrank_ScT(A, T.p, l, Yloc, ldy);
 }
 
-void gather_rows(Context& c, const Operator& A, const double* Yloc, int64_t ldy, int64_t l, double* Yfull) {
+// Y (m x l, ld m, replicated) <- the ranks' row shards of default_shard(m), this rank's being Yloc (mloc x l, ld ldy)
+static void gather_rows(Context& c, int64_t m, int64_t mloc, const double* Yloc, int64_t ldy, int64_t l, double* Yfull) {
   Backend* be = c.be.get();
   if (!c.comm) {
-    if (Yloc != Yfull) be->copy2d(Yfull, A.m, Yloc, ldy, A.m, l);
+    if (Yloc != Yfull) be->copy2d(Yfull, m, Yloc, ldy, m, l);
     return;
   }
   const int G = c.nranks();
-  const int64_t pad = (A.m + G - 1) / G;
+  const int64_t pad = (m + G - 1) / G;
   Buf send(be, (size_t)pad * l), recv(be, (size_t)pad * l * G);
-  if (A.mloc < pad) be->fill_zero(send.p, (size_t)pad * l);
-  be->copy2d(send.p, pad, Yloc, ldy, A.mloc, l);
+  if (mloc < pad) be->fill_zero(send.p, (size_t)pad * l);
+  be->copy2d(send.p, pad, Yloc, ldy, mloc, l);
   {
     CommPhase ph(c);
     c.comm->allgather(send.p, recv.p, (size_t)pad * l);
   }
   for (int g = 0; g < G; ++g) {
     int64_t r0, ml;
-    default_shard(A.m, G, g, &r0, &ml);
-    be->copy2d(Yfull + r0, A.m, recv.p + (size_t)g * pad * l, pad, ml, l);
+    default_shard(m, G, g, &r0, &ml);
+    be->copy2d(Yfull + r0, m, recv.p + (size_t)g * pad * l, pad, ml, l);
   }
+}
+void gather_rows(Context& c, const Operator& A, const double* Yloc, int64_t ldy, int64_t l, double* Yfull) {
+  gather_rows(c, A.m, A.mloc, Yloc, ldy, l, Yfull);
 }
 
 // ---- panel layouts over the ranks --------------------------------------------------------------------------------------
@@ -308,24 +323,13 @@ void op_mul_t(const Operator& A, const double* Xloc, int64_t ldx, int64_t l, dou
   }
   // adjoint(A::LowRankCovMatrix) === A  (lowrank.jl:38-40): A'*X = A*X, rows then gathered
   Buf T(be, (size_t)A.N * l);
-  {
-    ScopedPhase ph(be, PH_GEMM_T);
-    be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, Xloc, ldx, 0.0, T.p, A.N);
-  }
-  if (c.comm) {
-    CommPhase ph(c);
-    c.comm->allreduce_sum(T.p, (size_t)A.N * l);
-  }
+  lowrank_StX(A, Xloc, ldx, l, T.p);
   if (!c.comm && ldz == A.m) {
-    ScopedPhase ph(be, PH_GEMM_N);
-    be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T.p, A.N, 0.0, Z, ldz);
+    lowrank_ScT(A, T.p, l, Z, ldz);
     return;
   }
   Buf Yloc(be, (size_t)std::max<int64_t>(A.mloc, 1) * l);
-  {
-    ScopedPhase ph(be, PH_GEMM_N);
-    be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T.p, A.N, 0.0, Yloc.p, A.mloc);
-  }
+  lowrank_ScT(A, T.p, l, Yloc.p, A.mloc);
   if (ldz != A.m) throw Error(GSI_ERR_INTERNAL, "op_mul_t: strided output for a sharded LowRankCovMatrix");
   gather_rows(c, A, Yloc.p, A.mloc, l, Z);
 }
@@ -341,17 +345,9 @@ static Buf op_mul_t_sharded(const Operator& A, const double* Xloc, int64_t ldx, 
   const int64_t n = A.n, pad = (n + G - 1) / G;
   if (A.kind == OP_LOWRANK) {
     Buf T(be, (size_t)A.N * l);
-    {
-      ScopedPhase ph(be, PH_GEMM_T);
-      be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, Xloc, ldx, 0.0, T.p, A.N);
-    }
-    {
-      CommPhase ph(c);
-      c.comm->allreduce_sum(T.p, (size_t)A.N * l);
-    }
+    lowrank_StX(A, Xloc, ldx, l, T.p);
     Buf Wloc(be, (size_t)std::max<int64_t>(A.mloc, 1) * l);
-    ScopedPhase ph(be, PH_GEMM_N);
-    be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T.p, A.N, 0.0, Wloc.p, A.mloc);
+    lowrank_ScT(A, T.p, l, Wloc.p, A.mloc);
     return Wloc;
   }
   if (A.kind == OP_FFT_COV) {              // symmetric, row shards in and out: nothing n x l exists on any rank
@@ -640,10 +636,8 @@ static void tsqr(Context& c, int64_t m, int64_t row0, int64_t mloc, Buf& Yloc, i
     return;
   }
   if (!all_shards_tall(m, G, l)) {  // a shard shorter than the sketch width: factor the gathered panel everywhere
-    Operator shape;
-    shape.m = m; shape.row0 = row0; shape.mloc = mloc;
     Buf Yfull(be, (size_t)m * l);
-    gather_rows(c, shape, Yloc.p, mloc, l, Yfull.p);
+    gather_rows(c, m, mloc, Yloc.p, mloc, l, Yfull.p);
     {
       ScopedPhase ph(be, PH_QR);
       be->qr_thinQ(Yfull.p, m, l, m, Rout, true);
@@ -711,21 +705,6 @@ static Buf rangefinder_rows(const Operator& A, const double* Omega_loc, int64_t 
 // `defer` (randsvd on one rank): the final thin Q may come back one tall product short -- Q = Q1 X2 with Q1 in backend
 // workspace (Backend::qr_thinQ_deferred); the returned Buf is then empty and defer->Q1 / ldq / X2 are set.
 struct DeferredQ { const double* Q1 = nullptr; int64_t ldq = 0; Buf X2; };
-// `last` (randsvd of a LowRankCovMatrix on one rank, sample-space tail): the range finder stops in front of its last product
-// A*X and hands back X (n x l, ld n) -- the last LU'd panel, or Omega when q = 0 -- with everything before it as always.
-// T (N x l, ld N), when set: S'X, formed by the last power step in sample space.
-struct LastPanel { Buf own; const double* X = nullptr; int64_t ldx = 0; Buf T; };
-static const double* sample_gram(const Operator& A);
-static bool lowrank_tail_applies(const Operator& A, int64_t l);
-// randsvd's power steps in sample space: wherever the tail may run; GSI_NO_LOWRANK_POWER=1 switches
-// off these alone (A/B), GSI_NO_LOWRANK_TAIL=1 both.
-static bool lowrank_power_applies(const Operator& A, int64_t l) {
-  static const bool off = (getenv("GSI_NO_LOWRANK_POWER") != nullptr);
-  return !off && lowrank_tail_applies(A, l);
-}
-static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer,
-                            LastPanel* last = nullptr);
-Buf rangefinder(const Operator& A, const double* Omega, int64_t l, int64_t q) { return rangefinder_impl(A, Omega, l, q, nullptr); }
 
 // the single-rank end of the range finder: the thin Q of Y (m x l, ld m), deferred into defer when it can be
 static Buf final_q_single(const Operator& A, Buf& Y, int64_t l, DeferredQ* defer) {
@@ -742,17 +721,20 @@ static Buf final_q_single(const Operator& A, Buf& Y, int64_t l, DeferredQ* defer
   return std::move(Y);
 }
 
-static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer, LastPanel* last) {
-  Context& c = *A.ctx;
-  Backend* be = c.be.get();
+static void check_rangefinder_args(const Operator& A, int64_t l, int64_t q) {
   if (q < 0)   // RandMatFact.jl:62-64
     throw Error(GSI_ERR_NEG_ITERS,
                 "parameter numiterations should be positive, but numiterations=" + std::to_string(q));
   if (l < 1 || l > A.m || l > A.n) throw Error(GSI_ERR_ARG, "rangefinder: need 1 <= l <= min(size(A))");
+}
+
+static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, int64_t q, DeferredQ* defer) {
+  Context& c = *A.ctx;
+  Backend* be = c.be.get();
+  check_rangefinder_args(A, l, q);
   const bool single = (c.nranks() == 1);
   const int64_t m = A.m, n = A.n;
   if (q == 0) {
-    if (last != nullptr && single) { last->X = Omega; last->ldx = n; return Buf(); }
     Buf Yloc(be, (size_t)std::max<int64_t>(A.mloc, 1) * l);
     op_mul(A, Omega, n, l, Yloc.p, A.mloc);                 // Y = A*Omega            :55
     if (single) return final_q_single(A, Yloc, l, defer);
@@ -771,75 +753,18 @@ static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, i
   // a sketch panel comes out of A*X as row shards: factor it where it lies when the sharded LU is on (the all-gather
   // of the panel and the replicated factorization go away; A'*L only reads the local rows anyway)
   const bool shard_y = !single && use_sharded_lu(c, A, m, l);
-  // randsvd of a LowRankCovMatrix on one rank: every product A*L / A'*L after a panel LU is S (c T) with T = S'L formed in
-  // sample space from the T of the panel before, the LU's pivots and its L (Backend::lowrank_power_step).
-  // The first product and the panel LUs are the ones below; on a decline S'L is formed from the L in memory by the product
-  // op_mul runs, and the call stays on the direct path -- a decline at the first LU gives the bits of the direct path.
-  struct Power { bool on = false; const double* G = nullptr; Buf T, Tn; int32_t* ipiv = nullptr; } pw;
-  if (last != nullptr && single && lowrank_power_applies(A, l)) {
-    pw.on = true;
-    pw.T = Buf(be, (size_t)A.N * l);
-    pw.Tn = Buf(be, (size_t)A.N * l);
-  }
-  auto lu_panel_keep = [&](double* Y, int64_t rows) {      // single rank: lu_panel, keeping the pivots while pw.on
-    if (pw.on) {
-      ScopedPhase ph(be, PH_LU);
-      if (be->lu_L_keep(Y, rows, l, rows, &pw.ipiv)) return;
-      pw.on = false;                                        // (not available: nothing ran)
-    }
-    lu_panel(c, Y, rows, l);
-  };
-  // T <- S'L for the L just factored; false: the direct path from here on (the caller forms S'L)
-  auto power_step = [&](const double* Lp, int64_t ldl) -> bool {
-    if (!pw.on) return false;
-    if (pw.G == nullptr) pw.G = sample_gram(A);
-    bool ok = false;
-    if (pw.G != nullptr) {
-      ScopedPhase ph(be, PH_OTHER);                         // (not PH_GEMM_T / _N: bench.py's roofline counts those as tall products)
-      ok = be->lowrank_power_step(A.data.p, A.ld, A.mloc, A.N, pw.G, pw.T.p, pw.ipiv, Lp, ldl, l, 1.0 / (double)(A.N - 1),
-                                  pw.Tn.p);
-      if (!ok) c.lowrank_power_declines += 1;
-    }
-    if (!ok) { pw = Power(); return false; }
-    std::swap(pw.T, pw.Tn);
-    c.lowrank_power_steps += 1;
-    return true;
-  };
-  auto mul_T = [&](double* Yo, int64_t ldy) {               // Y = A*L = S (c T): op_mul's second product
-    ScopedPhase ph(be, PH_GEMM_N);
-    be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, pw.T.p, A.N, 0.0, Yo, ldy);
-  };
   auto lu_y = [&]() {
     if (shard_y) { lu_panel_sharded(c, yl, m, A.row0, A.mloc, l); return; }
     gather_rows(c, A, yl, ldyl, l, Yfull.p);
-    if (single) lu_panel_keep(Yfull.p, m);
-    else lu_panel(c, Yfull.p, m, l);
+    lu_panel(c, Yfull.p, m, l);
   };
-  if (pw.on) {                                              // Y = A*Omega            :55 (op_mul's products, T kept)
-    {
-      ScopedPhase ph(be, PH_GEMM_T);
-      be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, Omega + A.row0, n, 0.0, pw.T.p, A.N);
-    }
-    mul_T(yl, ldyl);
-  } else {
-    op_mul(A, Omega, n, l, yl, ldyl);                       // Y = A*Omega            :55
-  }
+  op_mul(A, Omega, n, l, yl, ldyl);                         // Y = A*Omega            :55
   lu_y();                                                   // Q = lu(Y).L            :60-61
   for (int64_t i = 1; i <= q; ++i) {                        //                        :66
-    if (power_step(Yfull.p, m)) mul_T(Z.p, n);              // Q = A'*Q               :67 (in sample space)
-    else if (shard_y) op_mul_t(A, yl, ldyl, l, Z.p, n);
+    if (shard_y) op_mul_t(A, yl, ldyl, l, Z.p, n);          // Q = A'*Q               :67
     else op_mul_t(A, Yfull.p + A.row0, m, l, Z.p, n);
-    if (single) lu_panel_keep(Z.p, n);                      // Q = lu(Q).L            :68-69
-    else lu_panel(c, Z.p, n, l);                            //                        (Z is replicated by the all-reduce)
-    if (i == q && last != nullptr && single) {              // the caller takes it from here (randsvd's sample-space tail)
-      if (power_step(Z.p, n)) last->T = std::move(pw.T);
-      last->own = std::move(Z);
-      last->X = last->own.p;
-      last->ldx = n;
-      return Buf();
-    }
-    if (power_step(Z.p, n)) mul_T(yl, ldyl);                // Q = A*Q                :70 (in sample space)
-    else op_mul(A, Z.p, n, l, yl, ldyl);
+    lu_panel(c, Z.p, n, l);                                 // Q = lu(Q).L            :68-69 (Z is replicated by the all-reduce)
+    op_mul(A, Z.p, n, l, yl, ldyl);                         // Q = A*Q                :70
     if (i < q) lu_y();                                      //                        :72-73
   }
   Z.reset();                                                // the QR below wants a panel of its own (512^3: each is tens of GB)
@@ -848,6 +773,7 @@ static Buf rangefinder_impl(const Operator& A, const double* Omega, int64_t l, i
   tsqr(c, A, Yloc, l);
   return Yloc;
 }
+Buf rangefinder(const Operator& A, const double* Omega, int64_t l, int64_t q) { return rangefinder_impl(A, Omega, l, q, nullptr); }
 
 void svd_tall(Context& c, double* W, int64_t n, int64_t l, int64_t K_scale, double* V, double* S, const double* Xr) {
   Backend* be = c.be.get();
@@ -902,6 +828,21 @@ static void svd_rows(const Operator& A, Buf& Q, int64_t K, int64_t l, double* Zl
   if (lz < l) be->fill_zero(Zloc + (size_t)lz * ldz, (size_t)(l - lz) * ldz);
 }
 
+// randsvd from the thin Q on (RandMatFact.jl:85-88) where B' = A'Q is held replicated: Q whole, or -- one rank, no
+// communicator -- deferred (dq.Q1 set): Q = Q1 X2, W = A'Q1, svd(W X2), the last tall product of the thin Q never run.
+static void randsvd_from_q(const Operator& A, Buf& Q, const DeferredQ& dq, int64_t K, int64_t l, double* Z, double* S) {
+  Context& c = *A.ctx;
+  Buf W(c.be.get(), (size_t)A.n * l);
+  if (dq.Q1 != nullptr) {
+    op_mul_t(A, dq.Q1, dq.ldq, l, W.p, A.n);                // B = Q'*A  (held as A'Q1; X2 follows in svd_tall)   :85
+    svd_tall(c, W.p, A.n, l, K, Z, S, dq.X2.p);             // (), S, V = svd(B); Z = V*Sh    :86-88
+    return;
+  }
+  op_mul_t(A, Q.p, A.mloc, l, W.p, A.n);                    // B = Q'*A  (held as B' = A'Q)   :85
+  Q.reset();
+  svd_tall(c, W.p, A.n, l, K, Z, S);                        // (), S, V = svd(B); Z = V*Sh    :86-88
+}
+
 // The sample Gram matrix of a LowRankCovMatrix, made on first use (Operator::gram); null when the backend has none.
 static const double* sample_gram(const Operator& A) {
   Backend* be = A.ctx->be.get();
@@ -915,11 +856,71 @@ static const double* sample_gram(const Operator& A) {
   return A.gram.p;
 }
 
-// randsvd's sample-space tail: one rank, a LowRankCovMatrix of at most 4096 samples, and a sketch
+// randsvd in sample space (DESIGN.md sections 4.10, 4.11): one rank, a LowRankCovMatrix of at most 4096 samples, and a sketch
 // narrower than the N - 1 dimensions the centred samples span.  GSI_NO_LOWRANK_TAIL=1 switches it off (A/B, tests).
 static bool lowrank_tail_applies(const Operator& A, int64_t l) {
   static const bool off = (getenv("GSI_NO_LOWRANK_TAIL") != nullptr);
   return !off && A.kind == OP_LOWRANK && !A.ctx->comm && A.m == A.n && A.mloc == A.m && A.N <= 4096 && l <= A.N - 1;
+}
+
+// randsvd of a LowRankCovMatrix on one rank (lowrank_tail_applies).  Every panel the range finder factors is P = S (c T) with
+// T (N x l) = S'X of the panel X before it, so T is what goes from step to step:
+//   T = S'Omega;   2q times:  P = S (c T), L = lu(P).L, T = S'L;   finish from T.
+// T = S'L is formed in sample space from the T before, the LU's pivots and L (Backend::lowrank_power_step, section 4.11), and
+// the finish runs in the coordinates of range(S) (Backend::lowrank_tail, section 4.10).  Where a power step declines, S'L is
+// the product from the L in memory, for this panel and the rest of the call (GSI_NO_LOWRANK_POWER=1: for all of them; a
+// decline at the first LU gives the bits of that leg); where the tail declines, Y = S (c T) and the ordinary deferred-Q
+// ending follow.  Both are the products and factorizations the general range finder runs, bit for bit.
+static void randsvd_lowrank_single(const Operator& A, const double* Omega, int64_t K, int64_t l, int64_t q, double* Z, double* S) {
+  Context& c = *A.ctx;
+  Backend* be = c.be.get();
+  check_rangefinder_args(A, l, q);
+  static const bool power_off = (getenv("GSI_NO_LOWRANK_POWER") != nullptr);
+  bool power = !power_off && q > 0;                         // power steps still on
+  const int64_t n = A.n;
+  const double cN = 1.0 / (double)(A.N - 1);
+  Buf T(be, (size_t)A.N * l), Tn, P;                        // P: the one n x l panel, each S (c T) overwrites the L before
+  if (power) Tn = Buf(be, (size_t)A.N * l);
+  int32_t* ipiv = nullptr;                                  // the pivots lu_L_keep left in backend workspace
+  lowrank_StX(A, Omega, n, l, T.p);                         // Y = A*Omega            :55
+  for (int64_t step = 0; step < 2 * q; ++step) {            // :60-61, then :67-69 and :70-73 per iteration
+    if (P.p == nullptr) P = Buf(be, (size_t)n * l);
+    lowrank_ScT(A, T.p, l, P.p, n);
+    if (power) {
+      ScopedPhase ph(be, PH_LU);
+      power = be->lu_L_keep(P.p, n, l, n, &ipiv);           // (false: not available, nothing ran)
+    }
+    if (!power) lu_panel(c, P.p, n, l);
+    if (power) {                                            // T <- S'L in sample space
+      const double* G = sample_gram(A);                     // (made at the operator's first power step)
+      power = false;
+      if (G != nullptr) {
+        ScopedPhase ph(be, PH_OTHER);                       // (not PH_GEMM_T / _N: bench.py's roofline counts those as tall products)
+        power = be->lowrank_power_step(A.data.p, A.ld, A.mloc, A.N, G, T.p, ipiv, P.p, n, l, cN, Tn.p);
+        if (!power) c.lowrank_power_declines += 1;
+      }
+    }
+    if (power) {
+      std::swap(T, Tn);
+      c.lowrank_power_steps += 1;
+    } else {                                                // off, unavailable or declined: from the L in memory
+      Tn.reset();
+      lowrank_StX(A, P.p, n, l, T.p);
+    }
+  }
+  Tn.reset();
+  const double* G = sample_gram(A);
+  if (G != nullptr && be->lowrank_tail(A.data.p, A.ld, n, A.N, G, T.p, l, K, cN, Z, n, S)) {
+    c.lowrank_tails += 1;
+    return;
+  }
+  if (P.p == nullptr) P = Buf(be, (size_t)n * l);
+  lowrank_ScT(A, T.p, l, P.p, n);                           // Y = A*L                :70 (q = 0: Y = A*Omega, :55)
+  T.reset();
+  DeferredQ dq;
+  Buf Q = final_q_single(A, P, l, &dq);
+  P.reset();                                                // (deferred: Q1 is in backend workspace, Y has served)
+  randsvd_from_q(A, Q, dq, K, l, Z, S);
 }
 
 void randsvd(const Operator& A, const double* Omega, int64_t K, int64_t p, int64_t q, double* Z, double* S) {
@@ -927,57 +928,21 @@ void randsvd(const Operator& A, const double* Omega, int64_t K, int64_t p, int64
   Backend* be = c.be.get();
   if (K < 0 || p < 0 || K + p < 1) throw Error(GSI_ERR_ARG, "randsvd: need K >= 0, p >= 0, K + p >= 1");
   const int64_t l = K + p;
+  if (lowrank_tail_applies(A, l)) { randsvd_lowrank_single(A, Omega, K, l, q, Z, S); return; }
   // One rank, no communicator: the thin Q is only ever used as B = Q'A (:85), so its last tall product is deferred into the
   // l x l factor of svd(B) -- Q = Q1 X2, W = A'Q1, svd(W X2) -- when CholeskyQR2 applies (the usual case).
   DeferredQ dq;
-  // A LowRankCovMatrix on one rank goes further: after the last panel LU L nothing needs a tall panel but Z, so the range
-  // finder hands back L, T = S'L is formed, and the backend finishes in the coordinates of range(S) (Backend::lowrank_tail).
-  // Where it declines, Y = S T / (N - 1) is formed with the products op_mul runs and the ordinary path follows, bit for bit.
-  LastPanel last;
-  const bool tail = lowrank_tail_applies(A, l);
-  Buf Q = rangefinder_impl(A, Omega, l, q, c.comm ? nullptr : &dq, tail ? &last : nullptr);   // Q = rangefinder(A, K+p, q)  :84
-  if (last.X != nullptr) {
-    Buf T = std::move(last.T);                              // S'L from the last power step in sample space, if it ran
-    if (T.p == nullptr) {
-      T = Buf(be, (size_t)A.N * l);
-      ScopedPhase ph(be, PH_GEMM_T);
-      be->gemm_tn(A.N, l, A.mloc, 1.0, A.data.p, A.ld, last.X, last.ldx, 0.0, T.p, A.N);        // T = S'L  (op_mul's first product)
-    }
-    const double* G = sample_gram(A);
-    if (G != nullptr && be->lowrank_tail(A.data.p, A.ld, A.n, A.N, G, T.p, l, K, 1.0 / (double)(A.N - 1), Z, A.n, S)) {
-      c.lowrank_tails += 1;
-      return;
-    }
-    Buf Y(be, (size_t)A.m * l);
-    {
-      ScopedPhase ph(be, PH_GEMM_N);
-      be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T.p, A.N, 0.0, Y.p, A.m);   // Y = A*L   :70
-    }
-    T.reset();
-    last.own.reset();
-    Q = final_q_single(A, Y, l, &dq);
-  }
-  if (dq.Q1 != nullptr) {
-    Buf W(be, (size_t)A.n * l);
-    op_mul_t(A, dq.Q1, dq.ldq, l, W.p, A.n);                // B = Q'*A  (held as A'Q1; X2 follows in svd_tall)   :85
-    svd_tall(c, W.p, A.n, l, K, Z, S, dq.X2.p);             // (), S, V = svd(B); Z = V*Sh    :86-88
-    return;
-  }
+  Buf Q = rangefinder_impl(A, Omega, l, q, c.comm ? nullptr : &dq);   // Q = rangefinder(A, K+p, q)  :84
   const int G = c.nranks();
   if (c.comm && all_shards_tall(A.n, G, l) && (A.kind != OP_LOWRANK || A.m == A.n)) {   // any communicator, also 1 rank
     int64_t r0n, nloc;
     default_shard(A.n, G, c.rank(), &r0n, &nloc);
     Buf Zloc(be, (size_t)std::max<int64_t>(nloc, 1) * l);
     svd_rows(A, Q, K, l, Zloc.p, S);
-    Operator shape;
-    shape.m = A.n; shape.row0 = r0n; shape.mloc = nloc;
-    gather_rows(c, shape, Zloc.p, std::max<int64_t>(nloc, 1), l, Z);
+    gather_rows(c, A.n, nloc, Zloc.p, std::max<int64_t>(nloc, 1), l, Z);
     return;
   }
-  Buf W(be, (size_t)A.n * l);
-  op_mul_t(A, Q.p, A.mloc, l, W.p, A.n);                    // B = Q'*A  (held as B' = A'Q)   :85
-  Q.reset();
-  svd_tall(c, W.p, A.n, l, K, Z, S);                        // (), S, V = svd(B); Z = V*Sh    :86-88
+  randsvd_from_q(A, Q, dq, K, l, Z, S);
 }
 
 // randsvd with Omega given and Z returned as ROW SHARDS (this rank's rows of default_shard(n); ld = max(nloc, 1)): the
@@ -991,9 +956,7 @@ void randsvd_rows(const Operator& A, const double* Omega_loc, int64_t K, int64_t
   if (K < 0 || p < 0 || K + p < 1) throw Error(GSI_ERR_ARG, "randsvd: need K >= 0, p >= 0, K + p >= 1");
   const int64_t l = K + p, n = A.n;
   if (!c.comm) { randsvd(A, Omega_loc, K, p, q, Zloc, S); return; }
-  if (q < 0)
-    throw Error(GSI_ERR_NEG_ITERS, "parameter numiterations should be positive, but numiterations=" + std::to_string(q));
-  if (l > A.m || l > A.n) throw Error(GSI_ERR_ARG, "rangefinder: need 1 <= l <= min(size(A))");
+  check_rangefinder_args(A, l, q);
   const int G = c.nranks();
   if (!all_shards_tall(n, G, l))
     throw Error(GSI_ERR_ARG, "randsvd_rows: every rank's row block must be at least K + p rows tall");
@@ -1004,9 +967,7 @@ void randsvd_rows(const Operator& A, const double* Omega_loc, int64_t K, int64_t
     Q = rangefinder_rows(A, Omega_loc, std::max<int64_t>(nloc, 1), l, q);
   } else {
     Buf Om(be, (size_t)n * l);
-    Operator shape;
-    shape.m = n; shape.row0 = r0n; shape.mloc = nloc;
-    gather_rows(c, shape, Omega_loc, std::max<int64_t>(nloc, 1), l, Om.p);
+    gather_rows(c, n, nloc, Omega_loc, std::max<int64_t>(nloc, 1), l, Om.p);
     Q = rangefinder(A, Om.p, l, q);
   }
   svd_rows(A, Q, K, l, Zloc, S);

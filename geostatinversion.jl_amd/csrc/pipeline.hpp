@@ -45,8 +45,8 @@ struct Context {
   int64_t ranks_seen = 1;              // sum over the communicator of one per rank, taken when it was created
   int profile_level = 0;               // gsi_ctx_profile: 2 = skew barriers in front of collectives / sharded LUs (PH_COMM_WAIT)
   int64_t lu_timeouts_recovered = 0;   // entry points re-run transparently after a lost co-residency (api.cpp:with_retry)
-  int64_t lowrank_tails = 0;           // randsvd steps of a LowRankCovMatrix that ran their tail in sample space (pipeline.cpp)
-  int64_t lowrank_power_steps = 0;     // range-finder power steps S'L formed in sample space (pipeline.cpp)
+  int64_t lowrank_tails = 0;           // randsvd steps of a LowRankCovMatrix that ran their tail in sample space (randsvd_lowrank_single)
+  int64_t lowrank_power_steps = 0;     // power steps S'L formed in sample space (randsvd_lowrank_single)
   int64_t lowrank_power_declines = 0;  // ... and the ones the backend declined (that call took the direct path from there on)
   int rank() const { return comm ? comm->rank : 0; }
   int nranks() const { return comm ? comm->nranks : 1; }
@@ -73,8 +73,8 @@ struct Operator {
   // other exit path.  Null everywhere else.
   mutable void* pending_upload = nullptr;
   mutable int64_t pending_block_rows = 0;
-  // OP_LOWRANK, one rank: the sample Gram matrix G = S'S (N x N), made by the first randsvd that runs its tail in sample space
-  // (pipeline.cpp:sample_gram) and freed with the operator.  Nothing writes `data` after creation, so it cannot go stale.
+  // OP_LOWRANK, one rank: the sample Gram matrix G = S'S (N x N), made by the first randsvd that runs a step in sample space
+  // (pipeline.cpp:randsvd_lowrank_single through sample_gram) and freed with the operator.  Nothing writes `data` after creation, so it cannot go stale.
   mutable Buf gram;
   Operator() = default;
   Operator(const Operator&) = delete;

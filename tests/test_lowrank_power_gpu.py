@@ -1,6 +1,7 @@
 """randsvd of a LowRankCovMatrix with the range finder's power steps in sample space.
 
-After each panel LU of Y = c S T, one-rank randsvd forms T_next = S'L = G C + S[mv]'((S[perm(mv)] - S[mv]) C) with
+After each panel LU of Y = c S T, one-rank randsvd (pipeline.cpp: randsvd_lowrank_single) forms
+T_next = S'L = G C + S[mv]'((S[perm(mv)] - S[mv]) C) with
 C = c T U^-1 (Backend::lowrank_power_step) instead of the n x l product S'L; the check of (P S) C against the L in memory
 declines where the coefficients no longer reproduce L, and that call goes on with the direct path.
 

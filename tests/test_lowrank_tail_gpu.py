@@ -1,8 +1,8 @@
 """randsvd of a LowRankCovMatrix with its tail in sample space.
 
-After the last panel LU L, one-rank randsvd of A = S S' / (N - 1) forms T = S'L and finishes on N x l coefficient matrices
-(Backend::lowrank_tail): CholeskyQR2 of Y = A L and of W = A'Q through M'(G M) with the sample Gram matrix G = S'S cached on
-the operator, the l x l SVD, and one tall product Z = S C.  Where it declines (a Cholesky breakdown, a failed orthogonality
+After the last panel LU L, one-rank randsvd of A = S S' / (N - 1) (pipeline.cpp: randsvd_lowrank_single) has T = S'L and
+finishes on N x l coefficient matrices (Backend::lowrank_tail): CholeskyQR2 of Y = A L and of W = A'Q through M'(G M) with
+the sample Gram matrix G = S'S cached on the operator, the l x l SVD, and one tall product Z = S C.  Where it declines (a Cholesky breakdown, a failed orthogonality
 check, l > N - 1) the ordinary path runs from the same T, bit for bit.
 
 Each comparison runs the sample-space path and the GSI_NO_LOWRANK_TAIL=1 path in child processes (the switch is read once
