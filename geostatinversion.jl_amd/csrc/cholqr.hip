@@ -761,17 +761,6 @@ __global__ __launch_bounds__(256) void lr_check_rows_kernel(const double* __rest
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
-// Lt (l x l, ld l) <- L11' for the unit lower triangle L11 on top of L (ld ldl): unit upper triangular
-__global__ __launch_bounds__(256) void lr_l11_transpose_kernel(const double* __restrict__ L, int64_t ldl, int64_t l,
-                                                               double* __restrict__ Lt) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < l * l; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = e % l, j = e / l;
-    Lt[e] = (i < j) ? L[j + i * ldl] : (i == j ? 1.0 : 0.0);
-  }
-}
-void lr_l11_transpose(hipStream_t st, const double* L, int64_t ldl, int64_t l, double* Lt) {
-  hipLaunchKernelGGL(lr_l11_transpose_kernel, dim3(grid_for(l * l, 512)), dim3(256), 0, st, L, ldl, l, Lt);
-}
 // X = R^-1 (l x l, ld l) of an upper triangular R: the inverse half of the fused Cholesky kernel.  false: l beyond it
 bool tri_inverse(hipStream_t st, const double* R, int64_t l64, double* X) {
   const int l = (int)l64;

@@ -97,6 +97,7 @@ class HipBackend : public Backend {
     for (auto& r : records_) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     hipFree(flags_);
     hipFree(scal_);
+    if (pin_power_) hipHostFree(pin_power_);
     if (mr_recs_) hipFree(mr_recs_);
     hipStreamDestroy(st_);
   }
@@ -1117,10 +1118,14 @@ class HipBackend : public Backend {
   // One power step of the range finder in sample space (Backend::lowrank_power_step).  The LU of
   // Y = c S T gives L = P Y U^-1 = (P S) C, C = c T U^-1, so S'L = S'P S C = G C + S'(P - I) S C, and P - I is non-zero on
   // the <= 2 l rows the interchanges move.  The factorization keeps its U12 blocks in a workspace, so U is re-formed from the
-  // l pivot rows: U = L11^-1 (P Y)[0:l] = c L11^-1 S[perm(0:l)] T.  Launches: one gather (the moved rows, their differences,
-  // the check rows -- the pivot rows first), S_piv T (l x l x N), L11', its inverse, U, U^-1 (the inverses one workgroup
-  // each), C (N x l x l), E = [D; S_chk] C, the check, G C (N x l x N), S[mv]' E (N x l x 2l).  Two host syncs: the pivots,
-  // and the check's verdict.  Fixed shapes and orders, no atomics: repeated calls give the same bits.
+  // l pivot rows: U = L11^-1 (P Y)[0:l] = c L11^-1 S[perm(0:l)] T.  Launches: the interchanges composed into the index lists
+  // (one workgroup, lowrank_power.hip), one gather (the moved rows' differences D, the check rows -- the pivot rows first --,
+  // S[mv]), S_piv T (l x l x N), the forward solve for U against the L11 on top of the panel, the solve C U = c T, E =
+  // [D; S_chk] C, the check, G C (N x l x N), S[mv]' E (N x l x 2l).  The host never sees the pivots: the blocks of moved rows
+  // are padded to 2 l rows with zero rows, so every offset and launch shape follows from (n, N, l).  One host sync, at the end:
+  // the check's partial maxima, the LU's info and the invalid-pivot flag in one copy (the caller overwrites the panel that
+  // holds L after a `true`, so the verdict has to be known).  Fixed shapes and orders, no atomics: repeated calls give the
+  // same bits.
   bool lowrank_power_step(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T,
                           const int32_t* ipiv, const double* L, int64_t ldl, int64_t l, double c, double* Tn) override {
     bind();
@@ -1129,94 +1134,54 @@ class HipBackend : public Backend {
     constexpr int NPARTS = 128;             // workgroups of the check (partial maxima)
     constexpr double CHECK_MAX = 1e-8;      // |(P S) C - L|max above this: the coefficients no longer reproduce L (declined)
     if (l < 1 || l > 384 || N < 1 || N > 4096 || n < 2 * l || n >= ((int64_t)1 << 31)) return false;
-    std::vector<int32_t> piv((size_t)l);
-    int32_t info = 0;
-    HIP_CHECK(hipMemcpyAsync(piv.data(), ipiv, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipMemcpyAsync(&info, flags_ + 0, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (info != 0) return false;            // a zero pivot (or a lost exchange): the entry point reports it
-    // P composed from the interchanges: (P S)[i] = S[perm(i)]
-    std::map<int64_t, int64_t> perm;
-    auto at = [&](int64_t i) { auto it = perm.find(i); return it == perm.end() ? i : it->second; };
-    for (int64_t j = 0; j < l; ++j) {
-      const int64_t r = piv[(size_t)j];
-      if (r < j || r >= n) return false;
-      if (r == j) continue;
-      const int64_t a = at(j), b = at(r);
-      perm[j] = b;
-      perm[r] = a;
-    }
-    std::vector<int64_t> mv;                // ascending (std::map order)
-    for (const auto& kv : perm)
-      if (kv.second != kv.first) mv.push_back(kv.first);
-    const int64_t nmv = (int64_t)mv.size(), ns = std::min<int64_t>(NSAMPLE, n - l), nchk = l + ns;
+    const int64_t ns = std::min<int64_t>(NSAMPLE, n - l), nchk = l + ns;
     auto up8 = [](int64_t x) { return (x + 7) & ~(int64_t)7; };
-    // gathered rows (ld ldr, every block starting on an even row): [0, nmv) D = S[perm(mv)] - S[mv]; [o_chk, o_chk + nchk)
-    // (P S) of the check rows; [o_sm, o_sm + nmv) S[mv].  Padding rows are S[0] - S[0] = 0.
-    const int64_t o_chk = up8(nmv), o_sm = o_chk + up8(nchk), nr = o_sm + nmv, ldr = up8(std::max<int64_t>(nr, 1));
-    std::vector<int64_t> idx((size_t)(2 * ldr + nchk), 0);
-    int64_t* src = idx.data();
-    int64_t* sub = src + ldr;
-    int64_t* chk = sub + ldr;
-    for (int64_t k = 0; k < nmv; ++k) {
-      src[k] = at(mv[(size_t)k]); sub[k] = mv[(size_t)k];
-      src[o_sm + k] = mv[(size_t)k]; sub[o_sm + k] = -1;
-    }
-    uint64_t h = 0x9e3779b97f4a7c15ull;     // a fixed sample of the rows below the pivot block (splitmix64)
-    for (int64_t k = 0; k < nchk; ++k) {
-      int64_t i = k;
-      if (k >= l) {
-        h += 0x9e3779b97f4a7c15ull;
-        uint64_t z = h;
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        z ^= z >> 31;
-        i = l + (int64_t)(z % (uint64_t)(n - l));
-      }
-      chk[k] = i;
-      src[o_chk + k] = at(i); sub[o_chk + k] = -1;
-    }
+    // gathered rows (ld ldr, every block starting on an even row): [0, 2l) D = S[perm(mv)] - S[mv]; [o_chk, o_chk + nchk)
+    // (P S) of the check rows; [o_sm, o_sm + 2l) S[mv].  Rows past the nmv moved ones, and padding rows, are S[0] - S[0] = 0.
+    const int64_t o_chk = up8(2 * l), o_sm = o_chk + up8(nchk), nr = o_sm + 2 * l, ldr = up8(nr);
+    const size_t nidx = (size_t)(2 * ldr + nchk);
     const size_t ll = (size_t)up8(l * l), Nl = (size_t)up8(N * l);
-    Scratch buf(this, 5 * ll + Nl + (size_t)ldr * (size_t)N + (size_t)ldr * (size_t)l + idx.size() + NPARTS);
-    double* X = buf.p;                      // U^-1
-    double* Mp = X + ll;                    // S[perm(0:l)] T
-    double* Lt = Mp + ll;                   // L11'
-    double* Vt = Lt + ll;                   // (L11')^-1
-    double* Uf = Vt + ll;                   // U = c L11^-1 Mp
-    double* C = Uf + ll;                    // c T U^-1
+    Scratch buf(this, 2 * ll + Nl + (size_t)ldr * (size_t)N + (size_t)ldr * (size_t)l + nidx + NPARTS + 2);
+    double* Mp = buf.p;                     // S[perm(0:l)] T
+    double* Ut = Mp + ll;                   // U' = (c L11^-1 Mp)', on and below its diagonal
+    double* C = Ut + ll;                    // c T U^-1
     double* R = C + Nl;                     // the gathered rows
     double* E = R + (size_t)ldr * N;        // rows [0, o_chk + nchk) of R times C
-    int64_t* idx_dev = reinterpret_cast<int64_t*>(E + (size_t)ldr * l);
-    double* part = reinterpret_cast<double*>(idx_dev + idx.size());
+    int64_t* idx_dev = reinterpret_cast<int64_t*>(E + (size_t)ldr * l);   // src, sub (ldr each), chk
+    double* part = reinterpret_cast<double*>(idx_dev + nidx);
+    int32_t* verdict = reinterpret_cast<int32_t*>(part + NPARTS);         // LU info, invalid pivot, nmv, 0
     const int64_t me = o_chk + nchk;
-    size_t gmax = hipk::gemm_workspace_doubles(N, l, l);
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, N));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, l));
+    size_t gmax = hipk::gemm_workspace_doubles(l, l, N);
     gmax = std::max(gmax, hipk::gemm_workspace_doubles(me, l, N));
     gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, N));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, nmv));
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, 2 * l));
     double* ws = gemm_ws(gmax + 64);
-    HIP_CHECK(hipMemcpyAsync(idx_dev, idx.data(), sizeof(int64_t) * idx.size(), hipMemcpyHostToDevice, st_));
+    struct Verdict { double parts[NPARTS]; int32_t v[4]; };
+    if (pin_power_ == nullptr) HIP_CHECK(hipHostMalloc(&pin_power_, sizeof(Verdict), hipHostMallocDefault));
+    hipk::lr_compose(st_, ipiv, flags_ + 0, n, l, nchk, o_chk, o_sm, ldr, idx_dev, idx_dev + ldr, idx_dev + 2 * ldr, verdict);
     hipk::lr_gather_rows(st_, Sm, lds, N, idx_dev, idx_dev + ldr, nr, R, ldr);
     hipk::gemm_f64(st_, false, l, l, N, 1.0, R + o_chk, ldr, T, N, 0.0, Mp, l, ws);          // S[perm(0:l)] T
-    hipk::lr_l11_transpose(st_, L, ldl, l, Lt);
-    (void)hipk::tri_inverse(st_, Lt, l, Vt);                                                    // (L11^-1)'
-    hipk::gemm_f64(st_, true, l, l, l, c, Vt, l, Mp, l, 0.0, Uf, l, ws);                      // U = c L11^-1 Mp
-    (void)hipk::tri_inverse(st_, Uf, l, X);
-    hipk::gemm_f64(st_, false, N, l, l, c, T, N, X, l, 0.0, C, N, ws);                       // C = c T U^-1
+    hipk::lr_solve_u(st_, L, ldl, Mp, l, c, Ut);                                               // U = c L11^-1 Mp
+    hipk::lr_solve_c(st_, Ut, l, T, N, c, C);                                                  // C U = c T
     hipk::gemm_f64(st_, false, me, l, N, 1.0, R, ldr, C, N, 0.0, E, ldr, ws);                // [D; (P S)_chk] C
     hipk::lr_check_rows(st_, E + o_chk, ldr, L, ldl, idx_dev + 2 * ldr, nchk, l, part, NPARTS);
     hipk::gemm_f64(st_, false, N, l, N, 1.0, G, N, C, N, 0.0, Tn, N, ws);                    // G C
-    if (nmv > 0) hipk::gemm_f64(st_, true, N, l, nmv, 1.0, R + o_sm, ldr, E, ldr, 1.0, Tn, N, ws);   // + S[mv]' (D C)
+    hipk::gemm_f64(st_, true, N, l, 2 * l, 1.0, R + o_sm, ldr, E, ldr, 1.0, Tn, N, ws);      // + S[mv]' (D C)
     check_launch("lowrank_power_step");
-    double parts[NPARTS];
-    HIP_CHECK(hipMemcpyAsync(parts, part, sizeof(parts), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));   // (idx and parts live until here)
+    const Verdict* h = static_cast<const Verdict*>(pin_power_);
+    HIP_CHECK(hipMemcpyAsync(pin_power_, part, sizeof(Verdict), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
     double mx = 0.0;
-    for (int p = 0; p < NPARTS; ++p) mx = std::max(mx, parts[p]);
+    bool finite = true;
+    for (int p = 0; p < NPARTS; ++p) {
+      if (!std::isfinite(h->parts[p])) finite = false;
+      else mx = std::max(mx, h->parts[p]);
+    }
+    if (!finite) mx = INFINITY;
     if (trace) fprintf(stderr, "lowrank_power_step: n %lld N %lld l %lld, %lld moved rows, check max |(P S) C - L| = %.3e\n",
-                       (long long)n, (long long)N, (long long)l, (long long)nmv, mx);
-    return mx <= CHECK_MAX;
+                       (long long)n, (long long)N, (long long)l, (long long)h->v[2], mx);
+    if (h->v[0] != 0 || h->v[1] != 0) return false;   // a zero pivot (or a lost exchange): the entry point reports it
+    return finite && mx <= CHECK_MAX;
   }
   void svd_small(double* G, int64_t l, double* U, double* S) override {
     bind();
@@ -1543,6 +1508,7 @@ class HipBackend : public Backend {
   hipEvent_t ev_stage_ = nullptr;
   int32_t* flags_ = nullptr;  // [0] lu info, [1] chol info, [8] jacobi rotation counter
   double* scal_ = nullptr;
+  void* pin_power_ = nullptr; // pinned: the verdict of a power step (lowrank_power_step)
   DevBuf ws_gemm_, ws_lu_, ws_qr_, ws_svd_, ws_blas2_, ws_lus_, ws_svdf_, ws_qr_hh_;
   std::mutex mu_;
   std::vector<DevBuf> sizes_;

@@ -189,11 +189,10 @@ void mirror_upper(hipStream_t st, double* G, int64_t l);                        
 // second round's |Gm - I| test.  false: l > 384 (nothing queued)
 bool cq_gram_round(hipStream_t st, double* Gm, int64_t l, double* X, bool check, int32_t* flag);
 void tri_product(hipStream_t st, const double* R2, const double* R1, int64_t l, double* R);   // R = R2 R1 (upper triangular)
-// randsvd's power steps in sample space: X = R^-1 of an upper triangular R (false: l > 384, nothing queued); R (nr x N, ld
-// ldr) <- rows S[src[k]] - S[sub[k]] (S[src[k]] where sub[k] < 0); part[0 .. nparts) <- partial maxima of
-// |E[k, j] - L[rows[k], j]| over k < nchk, j < l (NaN: +inf)
+// X = R^-1 of an upper triangular R by the inverse half of the fused Cholesky kernel (false: l > 384, nothing queued)
 bool tri_inverse(hipStream_t st, const double* R, int64_t l, double* X);
-void lr_l11_transpose(hipStream_t st, const double* L, int64_t ldl, int64_t l, double* Lt);   // Lt = L[0:l, 0:l]' (unit upper)
+// randsvd's power steps in sample space (with lowrank_power.hip): R (nr x N, ld ldr) <- rows S[src[k]] - S[sub[k]] (S[src[k]]
+// where sub[k] < 0); part[0 .. nparts) <- partial maxima of |E[k, j] - L[rows[k], j]| over k < nchk, j < l (NaN: +inf)
 void lr_gather_rows(hipStream_t st, const double* S, int64_t lds, int64_t N, const int64_t* src, const int64_t* sub,
                     int64_t nr, double* R, int64_t ldr);
 void lr_check_rows(hipStream_t st, const double* E, int64_t lde, const double* L, int64_t ldl, const int64_t* rows,
@@ -203,6 +202,14 @@ void scholqr3_factor(hipStream_t st, const double* Y, int64_t m, int64_t l, int6
 void scholqr3_apply(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const double* S, int64_t lds,
                     double* R, double* small_ws, double* gemm_ws);
 
+// ---- lowrank_power.hip ----
+// The LU's interchanges piv[0:l) composed on the device into the index lists of lr_gather_rows / lr_check_rows (blocks of 2 l,
+// nchk and 2 l rows at 0, o_chk and o_sm; unused rows S[0] - S[0]); verdict[0:4) <- *info, invalid pivot seen, moved rows, 0
+void lr_compose(hipStream_t st, const int32_t* piv, const int32_t* info, int64_t n, int64_t l, int64_t nchk, int64_t o_chk,
+                int64_t o_sm, int64_t ldr, int64_t* src, int64_t* sub, int64_t* chk, int32_t* verdict);
+// Ut (l x l) <- (c L11^-1 Mp)' on and below the diagonal, L11 the unit lower triangle on top of L;  C (N x l) <- c T U^-1
+void lr_solve_u(hipStream_t st, const double* L, int64_t ldl, const double* Mp, int64_t l, double c, double* Ut);
+void lr_solve_c(hipStream_t st, const double* Ut, int64_t l, const double* T, int64_t N, double c, double* C);
 // ---- jacobi_svd.hip ----
 struct SvdWork {
   int32_t* rotcount;  // [1]
