@@ -1398,7 +1398,7 @@ def _dense_pointcov(P, kind, ell, sigma2, nugget):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,d,kind,l", [(300, 2, "exponential", 7), (1000, 3, "gaussian", 48), (777, 1, "matern32", 33),
                                          (2500, 2, "matern52", 160), (4097, 2, "exponential", 320),
-                                         # the 64-row x 320-column kernel (pointcov_gemm.hip: 160 < l): ragged widths, three
+                                         # the 96-row x 320-column kernel (pointcov_gemm.hip: 160 < l): ragged widths, three
                                          # dimensions, fewer rows than one tile, two column chunks, an even leading dimension
                                          (1500, 3, "matern52", 250), (3000, 2, "gaussian", 400), (50, 2, "exponential", 170),
                                          (5000, 1, "matern32", 192), (2048, 3, "exponential", 320),
@@ -1587,7 +1587,7 @@ def run_rank(rank, world, ctx, exchange, out):
     X = rng.standard_normal((333, 4))
     out["pointcov_mul"] = float(np.abs(pop.matmul(X) - Ap @ X).max())
     out["pointcov_mul_t"] = float(np.abs(pop.rmatmul_t(X) - Ap @ X).max())
-    Xw = rng.standard_normal((333, 200))                       # 160 < l: the 64 x 320-tile kernel with row / reduction offsets
+    Xw = rng.standard_normal((333, 200))                       # 160 < l: the 96 x 320-tile kernel with row / reduction offsets
     out["pointcov_wide_mul"] = float(np.abs(pop.matmul(Xw) - Ap @ Xw).max())
     out["pointcov_wide_mul_t"] = float(np.abs(pop.rmatmul_t(Xw) - Ap @ Xw).max())
     Om = rng.standard_normal((333, 24))
