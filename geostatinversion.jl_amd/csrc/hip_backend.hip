@@ -577,8 +577,8 @@ class HipBackend : public Backend {
   }
   void lu_L_impl(double* Y, int64_t m, int64_t l, int64_t ld, int32_t* ipiv_host, int32_t** ipiv_dev_out) {
     bind();
-    // Panels of up to 4096 rows per CU: leaves held in registers, left-looking blocks, streaming rank-64 updates
-    // (panel_lu_leaf.hip).  Everything else takes the streamed leaves below.
+    // Panels of up to 4096 rows per CU: leaves held in registers (panel_lu_leaf.hip), left-looking updates between the
+    // blocks (panel_lu_blocks.hip).  Everything else takes the streamed leaves below (panel_lu_streamed.hip).
     hipk::Lu2Work w2;
     static const bool tall_first = (getenv("GSI_LU_TALL") != nullptr && getenv("GSI_LU_TALL")[0] == '1');
     // Panels taller than the register file holds (up to GSI_LU_OV_MAX rows, default 5 x 2^20): the resident kernel on all
@@ -598,6 +598,7 @@ class HipBackend : public Backend {
         if ((int64_t)lu2_ov_resident_ * ncus_ >= g) { w2.bs = 512; w2.rpt = 8; w2.grid = g; w2.ov = true; fits = true; }
       }
     }
+    int32_t* ipiv_dev = nullptr;
     if (fits) {
       // test / A-B knobs, read per call: GSI_LU_POLL_LIMIT (polls before a workgroup gives up), GSI_LU_TEST_MUTE_EPOCH
       // (one workgroup stays silent at that pivot step: exercises the info = -1 path), GSI_LU_COOPERATIVE=1
@@ -606,33 +607,23 @@ class HipBackend : public Backend {
       if (const char* e = getenv("GSI_LU_COOPERATIVE")) w2.cooperative = (e[0] == '1');
       static const int nb_env = getenv("GSI_LU_NB") ? atoi(getenv("GSI_LU_NB")) : 0;
       w2.nb = (nb_env == 32 || nb_env == 64) ? nb_env : hipk::LU2_NB;
-      const size_t rec_bytes = sizeof(unsigned long long) * 2 * ((size_t)w2.grid + hipk::LU2_RES_COPIES) * hipk::LU2_REC_GRANULES;
-      const size_t u12_bytes = sizeof(double) * (size_t)l * (size_t)l;   // U12 of every block (left-looking between blocks)
-      grow(ws_lu_, rec_bytes + u12_bytes + sizeof(int32_t) * (l + 4) + 256);
-      char* base = (char*)ws_lu_.p;
-      w2.recs = (unsigned long long*)base; base += rec_bytes;
-      w2.u12 = (double*)base; base += u12_bytes;
-      w2.ipiv = (int32_t*)base;
+      grow(ws_lu_, hipk::lu2_work_bytes(l, w2.grid));
+      hipk::lu2_carve(w2, l, ws_lu_.p);
       w2.info = flags_ + 0;
       hipk::lu2_L(st_, Y, m, l, ld, w2);
       check_launch("lu2_L");
-      if (ipiv_dev_out) *ipiv_dev_out = w2.ipiv;
-      if (ipiv_host) {
-        HIP_CHECK(hipMemcpyAsync(ipiv_host, w2.ipiv, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-      }
-      return;
+      ipiv_dev = w2.ipiv;
+    } else {
+      // Everything the resident kernel does not take -- panels the register file cannot hold (more than 4096 rows per CU), a
+      // context that lost co-residency once, a leaf grid that does not fit the chip: streamed leaves with lazily evaluated
+      // candidates (same blocks, pivots and arithmetic; no spin-waits between workgroups).  GSI_LU_TALL=1 forces it for any
+      // height (tests: bit-identical to the resident kernel).  (Round 1's per-column sweeps, the fall-back behind these through
+      // round 4, are kept as tools/rejected_kernels/panel_lu_round1_sweeps.hip.txt.)
+      if (m >= ((int64_t)1 << 31)) throw Error(GSI_ERR_ARG, "lu: panels of 2^31 rows and more are not supported");
+      grow(ws_lu_, hipk::lu3_work_bytes(l));
+      hipk::lu3_L(st_, Y, m, l, ld, ws_lu_.p, flags_ + 0, &ipiv_dev);
+      check_launch("lu3_L");
     }
-    // Everything the resident kernel does not take -- panels the register file cannot hold (more than 4096 rows per CU), a
-    // context that lost co-residency once, a leaf grid that does not fit the chip: streamed leaves with lazily evaluated
-    // candidates (same blocks, pivots and arithmetic; no spin-waits between workgroups).  GSI_LU_TALL=1 forces it for any
-    // height (tests: bit-identical to the resident kernel).  (Round 1's per-column sweeps, the fall-back behind these through
-    // round 4, are kept as tools/rejected_kernels/panel_lu_round1_sweeps.hip.txt.)
-    if (m >= ((int64_t)1 << 31)) throw Error(GSI_ERR_ARG, "lu: panels of 2^31 rows and more are not supported");
-    grow(ws_lu_, hipk::lu3_work_bytes(l));
-    int32_t* ipiv_dev = nullptr;
-    hipk::lu3_L(st_, Y, m, l, ld, ws_lu_.p, flags_ + 0, &ipiv_dev);
-    check_launch("lu3_L");
     if (ipiv_dev_out) *ipiv_dev_out = ipiv_dev;
     if (ipiv_host) {
       HIP_CHECK(hipMemcpyAsync(ipiv_host, ipiv_dev, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));

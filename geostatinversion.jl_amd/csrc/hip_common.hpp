@@ -82,7 +82,8 @@ void fft_finish_plan_lags(hipStream_t st, double* lam, const int64_t M[3], doubl
 void fft_cov_apply(hipStream_t st, const int64_t N[3], const int64_t M[3], const double* lam, double2* W, int nb_max,
                    int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy);
 
-// ---- panel_lu_leaf.hip: register-resident leaves + streaming rank-K updates (panels of <= 4096 rows per CU) ----
+// ---- panel_lu_leaf.hip: register-resident leaves (panels of <= 4096 rows per CU, a little more with overflow rows); the
+//      updates between the blocks are panel_lu_blocks.hip's ----
 constexpr int LU2_LEAF = 8;           // leaf width: columns a thread keeps in registers
 constexpr int LU2_NB = 64;            // widest block (left-looking leaves inside, one rank-NB update per block)
 constexpr int LU2_RES_COPIES = 8;     // copies of the per-step result record (one per group of pollers)
@@ -101,7 +102,8 @@ struct Lu2Work {
 int lu2_resident_per_cu_ov();
 // workgroups of the (bs, rpt) leaf kernel that fit one CU (occupancy query); 0 if the query fails
 int lu2_resident_per_cu(int bs, int rpt);
-// the same leaf kernel across RANKS (one launch per rank, records written into every rank's peer-mapped buffer)
+// the same leaf kernel across RANKS (one launch per rank, records written into every rank's peer-mapped buffer); the
+// interchanges across ranks that follow a leaf (lus_swap_*) are panel_lu_sharded.hip's
 constexpr int LU2_MAX_RANKS = 16;
 constexpr int LU2_MR_MAXL = 8192;        // widest panel of the multi-rank persistent-leaf path (row boxes)
 struct Lu2MrWork {
@@ -127,13 +129,18 @@ void lus_swap_apply(hipStream_t st, double* Y, int64_t ld, int64_t mloc, int64_t
                     const int32_t* ipiv, const double* table);
 // launch geometry for an m-row panel on a chip with `ncus` CUs; false: the panel does not fit the register file
 bool lu2_config(int64_t m, int ncus, int* bs, int* rpt, int* grid);
+// the workspace of lu2_L for w.grid workgroups, and w.recs / w.u12 / w.ipiv laid into it
+size_t lu2_work_bytes(int64_t l, int grid);
+void lu2_carve(Lu2Work& w, int64_t l, void* work);
 void lu2_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const Lu2Work& w);
 
-// panels taller than the register file: streamed leaves, lazily evaluated (no spin-waits); `work` = lu3_work_bytes(l) bytes
+// ---- panel_lu_streamed.hip: panels taller than the register file: streamed leaves, lazily evaluated (no spin-waits);
+//      `work` = lu3_work_bytes(l) bytes ----
 size_t lu3_work_bytes(int64_t l);
 void lu3_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, void* work, int32_t* info, int32_t** ipiv_out);
 
-// row-sharded form (the exchange between ranks is pipeline.cpp's): primitives on this rank's rows [row0, row0 + mloc)
+// ---- panel_lu_sharded.hip: row-sharded form (the exchange between ranks is pipeline.cpp's): primitives on this rank's rows
+//      [row0, row0 + mloc); lus_u12_block and lus_rankk, the right-looking block update, are panel_lu_blocks.hip's ----
 int lus_grid(int64_t mloc);
 void lus_candidate(hipStream_t st, const double* Y, int64_t ld, int64_t mloc, int64_t row0, int64_t l, int64_t j, double* rec,
                    double* pval, int64_t* pidx, bool partials_ready);

@@ -1226,7 +1226,7 @@ def test_lu_headline_height_matches_lapack(gsi, ctx, m, l, ties):
 
 
 # ---- panels taller than the register-resident path holds (> 4096 rows per CU = 1 048 576 rows): streamed leaves with lazily
-#      evaluated candidates (panel_lu_leaf.hip: lu3_*).  (a) Forced onto panels the resident kernel also takes
+#      evaluated candidates (panel_lu_streamed.hip: lu3_*).  (a) Forced onto panels the resident kernel also takes
 #      (GSI_LU_TALL=1): the factors must be BIT-identical to the resident kernel's and the pivots dgetrf's -- ties, several
 #      64-column blocks, a ragged last leaf, tiny panels; (b) a panel that only this path takes, against dgetrf. ------------
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""The single-rank LU updates its 64-column blocks LEFT-looking (panel_lu_leaf.hip: lu_leftlook_kernel, lu_urows_kernel):
+"""The single-rank LU updates its 64-column blocks LEFT-looking (panel_lu_blocks.hip: lu_leftlook_kernel, lu_urows_kernel):
 block i's columns are brought up to date once, before its leaves, with every finished block to their left.  The factors must
 be bit for bit those of the right-looking row-sharded form (lus_u12_block / lus_rankk, the reference) and the pivots dgetrf's.
 Shapes here: the headline panel (five full blocks) with ties, several full blocks plus a ragged last block, an overflow-row
