@@ -272,6 +272,64 @@ int gsi_op_lowrank_synthetic(gsi_ctx* ctx, gsi_op** op, int64_t n, int64_t N, ui
   });
 }
 
+// The limits of the device sampler (fftrf_sample.hip: a line of at most 8192 points in LDS); -> n, Mtot.  Throws before
+// anything is allocated.
+static void check_fftrf_grid(int ndims, const int64_t* N, double k0, double dk, double beta, int64_t* n_out, int64_t* mtot_out) {
+  REQUIRE(ndims == 2 || ndims == 3, "FFTRF fields: unsupported dimension (ndims must be 2 or 3)");
+  REQUIRE(N != nullptr, "N is NULL");
+  int64_t n = 1, mtot = 1;
+  for (int a = 0; a < ndims; ++a) {
+    REQUIRE(N[a] >= 1, "FFTRF fields: grid dimensions must be >= 1");
+    const int64_t L = 2 * N[a];
+    if ((L & (L - 1)) == 0)
+      REQUIRE(N[a] <= 4096, "FFTRF fields: at most 4096 points per axis where 2 N is a power of two (a line of 8192 points)");
+    else
+      REQUIRE(N[a] <= 2730, "FFTRF fields: at most 2730 points per axis where 2 N is not a power of two (Bluestein's "
+                            "convolution of 3 N - 1 points must fit a line of 8192)");
+    n *= N[a];
+    mtot *= L;
+    REQUIRE(mtot < ((int64_t)1 << 31), "FFTRF fields: the doubled grid must have fewer than 2^31 points");
+  }
+  REQUIRE(n >= 2, "FFTRF fields: a field needs n >= 2 points (the corrected std divides by n - 1)");
+  REQUIRE(std::isfinite(k0) && std::isfinite(dk) && std::isfinite(beta), "FFTRF fields: k0, dk and beta must be finite");
+  *n_out = n;
+  *mtot_out = mtot;
+}
+
+int gsi_fftrf_fields(gsi_ctx* ctx, gsi_mat* fields, int ndims, const int64_t* N, double k0, double dk, double beta,
+                     const double* phi, int64_t ldphi, uint64_t seed, int64_t field0) {
+  return guarded([&] {
+    REQUIRE(ctx && fields && fields->ctx == ctx, "bad argument");
+    int64_t n = 0, mtot = 0;
+    check_fftrf_grid(ndims, N, k0, dk, beta, &n, &mtot);
+    REQUIRE(fields->rows == n, "FFTRF fields: the matrix must have n = prod(N) rows");
+    REQUIRE(phi == nullptr || ldphi >= mtot, "FFTRF fields: ldphi must be at least Mtot = 2^ndims n");
+    REQUIRE(phi != nullptr || field0 >= 0, "FFTRF fields: field0 must be >= 0");
+    ctx->c.be->fftrf_fields(fields->buf.p, fields->rows, 0, n, fields->cols, ndims, N, k0, dk, beta, phi, ldphi, seed, field0);
+  });
+}
+
+int gsi_op_lowrank_fftrf(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, double k0, double dk, double beta,
+                         int64_t numfields, uint64_t seed, int64_t row0, int64_t n_local) {
+  return guarded([&] {
+    REQUIRE(ctx && op, "NULL argument");
+    *op = nullptr;
+    int64_t n = 0, mtot = 0;
+    check_fftrf_grid(ndims, N, k0, dk, beta, &n, &mtot);
+    REQUIRE(numfields >= 2, "LowRankCovMatrix needs numfields >= 2 sample fields");
+    check_shard(ctx->c, n, row0, n_local);
+    std::unique_ptr<gsi_op> o(new gsi_op());
+    Operator& A = o->op;
+    A.ctx = &ctx->c; A.kind = OP_LOWRANK; A.m = n; A.n = n; A.row0 = row0; A.mloc = n_local; A.N = numfields;
+    A.ld = n_local > 0 ? ((n_local + 15) / 16) * 16 : 16;
+    A.data = Buf(ctx->c.be.get(), (size_t)A.ld * numfields);
+    // the sampler's normalising write goes straight into the operator's padded buffer
+    ctx->c.be->fftrf_fields(A.data.p, A.ld, row0, n_local, numfields, ndims, N, k0, dk, beta, nullptr, 0, seed, 0);
+    ctx->c.be->center_rows(A.data.p, n_local, numfields, A.ld);   // lowrank.jl:17-27
+    *op = o.release();
+  });
+}
+
 int gsi_op_lowrank_samples(gsi_ctx* ctx, const gsi_op* op, double* samples_out, int64_t ld) {
   return guarded([&] {
     REQUIRE(ctx && op && samples_out, "NULL argument");

@@ -238,6 +238,17 @@ class Backend {
   // by the global index (identical for every rank layout)
   virtual void fill_lowrank_samples(double* S, int64_t ld, int64_t nloc, int64_t N, int64_t row0, uint64_t seed,
                                     double decay) = 0;
+  // FFTRF.powerlaw_structuredgrid(N, k0, dk, beta) (FFTRF.jl:83-100) for fields field0 .. field0 + nf - 1, sampled on the
+  // device (fftrf_sample.hip): rows [row0, row0 + nloc) of field c go to dst[(r - row0) + c ldd].  phi (HOST, or null): column
+  // c = vec() of mulbyphi's randn(size(S)) for field c, leading dimension ldphi; null: field f draws randn(..., seed + f).
+  // Arguments are validated by the caller.
+  virtual void fftrf_fields(double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf, int ndims, const int64_t* N,
+                            double k0, double dk, double beta, const double* phi, int64_t ldphi, uint64_t seed,
+                            int64_t field0) {
+    (void)dst; (void)ldd; (void)row0; (void)nloc; (void)nf; (void)ndims; (void)N; (void)k0; (void)dk; (void)beta; (void)phi;
+    (void)ldphi; (void)seed; (void)field0;
+    throw Error(1 /* GSI_ERR_ARG */, "FFTRF fields sampled on the device: not available on this backend");
+  }
   // column norms of Y (m x c) -> host array
   virtual void colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) = 0;
   // y <- y - Q (Q' y) for Q m x j (classical Gram-Schmidt step of Alg 4.2), y length m

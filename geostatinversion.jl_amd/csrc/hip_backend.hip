@@ -1222,6 +1222,37 @@ class HipBackend : public Backend {
     hipk::fill_lowrank_samples(st_, S, ld, nloc, N, row0, seed, decay);
     check_launch("fill_lowrank_samples");
   }
+  // Batches of fields: phi and the intermediate array of a batch stay within 2 GiB of workspace (GSI_FFTRF_BATCH=<b>, read
+  // at every call, overrides the batch size).  Nothing a field computes depends on the batch it rides in.
+  void fftrf_fields(double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf, int ndims, const int64_t* N, double k0,
+                    double dk, double beta, const double* phi, int64_t ldphi, uint64_t seed, int64_t field0) override {
+    bind();
+    if (nf <= 0) return;
+    hipk::FftrfGeom g;
+    hipk::fftrf_geometry(ndims, N, &g);
+    int64_t fs = (int64_t)hipk::fftrf_field_doubles(g);
+    fs += fs & 1;                                     // the complex array of every field 16-byte aligned
+    int64_t nb = (((int64_t)2 << 30) / (int64_t)sizeof(double)) / fs;
+    if (const char* e = getenv("GSI_FFTRF_BATCH")) { if (atoll(e) >= 1) nb = atoll(e); }
+    if (nb > 4096) nb = 4096;
+    if (nb > nf) nb = nf;
+    if (nb < 1) nb = 1;
+    Hold plan{this, nullptr}, ws{this, nullptr};
+    plan.p = alloc(hipk::fftrf_plan_doubles(g));
+    ws.p = alloc((size_t)(fs * nb));
+    hipk::fftrf_plan(st_, g, plan.p);
+    for (int64_t f0 = 0; f0 < nf; f0 += nb) {
+      const int b = (int)((nf - f0 < nb) ? (nf - f0) : nb);
+      if (phi) {
+        if (f0 > 0) HIP_CHECK(hipStreamSynchronize(st_));      // the previous batch still reads the workspace
+        upload2d(ws.p, fs, phi + f0 * ldphi, ldphi, g.Mtot, b);
+      } else {
+        for (int i = 0; i < b; ++i) hipk::randn_fill(st_, ws.p + (int64_t)i * fs, (size_t)g.Mtot, seed + (uint64_t)(field0 + f0 + i));
+      }
+      hipk::fftrf_sample(st_, g, plan.p, ws.p, fs, b, k0, dk, beta, dst + f0 * ldd, ldd, row0, nloc);
+      check_launch("fftrf_sample");
+    }
+  }
   void colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) override {
     bind();
     if (c > 64) throw Error(GSI_ERR_ARG, "colnorms: at most 64 columns at a time");

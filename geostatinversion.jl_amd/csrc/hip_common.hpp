@@ -82,6 +82,18 @@ void fft_finish_plan_lags(hipStream_t st, double* lam, const int64_t M[3], doubl
 void fft_cov_apply(hipStream_t st, const int64_t N[3], const int64_t M[3], const double* lam, double2* W, int nb_max,
                    int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy);
 
+// ---- fftrf_sample.hip: FFTRF.powerlaw_structuredgrid fields on the device ----
+// The grid as the sampler sees it: A = (N[1], N[0], N[2]) the half lengths along the ARRAY axes (the reference's axis swap),
+// L = 2 A the doubled grid, per axis Bluestein (2 A not a power of two) with convolution length P (P = L on a direct axis).
+struct FftrfGeom { int d; int64_t A[3], L[3], P[3]; int blue[3]; int64_t Mtot, n; };
+void fftrf_geometry(int ndims, const int64_t* N, FftrfGeom* g);
+size_t fftrf_plan_doubles(const FftrfGeom& g);     // twiddles + per Bluestein axis the chirp and its spectrum
+size_t fftrf_field_doubles(const FftrfGeom& g);    // workspace of one field of a batch: phi | W | raw field | partial sums
+void fftrf_plan(hipStream_t st, const FftrfGeom& g, double* plan);
+// nb fields whose phi sits at ws + b fs (fs even, >= fftrf_field_doubles): dst[(r - row0) + b ldd] for r in [row0, row0 + nloc)
+void fftrf_sample(hipStream_t st, const FftrfGeom& g, const double* plan, double* ws, int64_t fs, int nb, double k0, double dk,
+                  double beta, double* dst, int64_t ldd, int64_t row0, int64_t nloc);
+
 // ---- panel_lu_leaf.hip: register-resident leaves (panels of <= 4096 rows per CU, a little more with overflow rows); the
 //      updates between the blocks are panel_lu_blocks.hip's ----
 constexpr int LU2_LEAF = 8;           // leaf width: columns a thread keeps in registers

@@ -73,3 +73,19 @@ def getxis_device(Q, numxis, p, q=3, seed=None, *, Omega=None, ctx=None, precisi
     finally:
         if owned:
             op.close()
+
+
+def getxis_fftrf(Ns, k0, dk, beta, numfields, numxis, p, q=3, seed=None, *, field_seed=0, Omega=None, ctx=None, device=False):
+    """`getxis(() -> FFTRF.powerlaw_structuredgrid(Ns, k0, dk, beta), numfields, numxis, p, q, seed)` with the fields sampled
+    on the device and never leaving HBM (`gsi_op_lowrank_fftrf`; field f draws the device stream `field_seed + f`).  `seed`
+    governs Omega exactly as in `getxis`.  Returns the list of xi-vectors, or with `device=True` a `DeviceBasis`."""
+    from .context import default_context
+    from .fftrf import lowrank_fftrf_operator
+    op = lowrank_fftrf_operator(ctx or default_context(), Ns, k0, dk, beta, numfields, seed=field_seed)
+    try:
+        if device:
+            return getxis_device(op, numxis, p, q, seed, Omega=Omega)
+        Z = randsvdwithseed(op, numxis, p, q, seed, Omega=Omega)
+        return [np.ascontiguousarray(Z[:, i]) for i in range(numxis)]
+    finally:
+        op.close()

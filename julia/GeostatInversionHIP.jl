@@ -143,6 +143,43 @@ function samples(A::DeviceOperator, N::Int)
 	return [S[:, i] for i = 1:N]
 end
 
+"`numfields` fields of `FFTRF.powerlaw_structuredgrid(Ns, k0, dk, beta)` (FFTRF.jl:83-100) sampled on the device
+(`gsi_fftrf_fields`): an n x numfields `DeviceMatrix`, column c = `vec` of field `field0 + c`.  `phi` (Mtot x numfields,
+column c = `vec(randn(size(S)))` of `mulbyphi`, FFTRF.jl:75, for field c) reproduces the reference's field for the same
+random numbers; without it field f draws the device stream `seed + f`."
+function fftrf_fields(Ns::Vector{Int}, k0::Float64, dk::Float64, beta::Float64, numfields::Int;
+		phi::Union{Nothing,Matrix{Float64}}=nothing, seed::Integer=0, field0::Int=0, c::Context=ctx())
+	N64 = Int64.(Ns)
+	F = DeviceMatrix(prod(Ns), numfields; c=c)
+	if phi === nothing
+		check(ccall((:gsi_fftrf_fields, libgsi), Cint,
+			(Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Int64, UInt64, Int64),
+			c.h, F.h, length(N64), N64, k0, dk, beta, C_NULL, 0, UInt64(seed), field0))
+	else
+		size(phi, 2) == numfields || error("phi must have one column per field")
+		GC.@preserve phi check(ccall((:gsi_fftrf_fields, libgsi), Cint,
+			(Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Int64, UInt64, Int64),
+			c.h, F.h, length(N64), N64, k0, dk, beta, phi, stride(phi, 2), UInt64(0), 0))
+	end
+	return F
+end
+
+"`LowRankCovMatrix` over `numfields` device-sampled FFTRF fields (`gsi_op_lowrank_fftrf`): what
+`getxis(() -> FFTRF.powerlaw_structuredgrid(Ns, k0, dk, beta), numfields, ...)` builds, with the fields generated, centred
+(lowrank.jl:17-27) and kept in HBM."
+function lowrank_fftrf_operator(Ns::Vector{Int}, k0::Float64, dk::Float64, beta::Float64, numfields::Int;
+		seed::Integer=0, c::Context=ctx())
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	N64 = Int64.(Ns)
+	n = prod(Ns)
+	check(ccall((:gsi_op_lowrank_fftrf, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Cint, Ptr{Int64}, Cdouble, Cdouble, Cdouble, Int64, UInt64, Int64, Int64),
+		c.h, r, length(N64), N64, k0, dk, beta, numfields, UInt64(seed), 0, n))
+	op = DeviceOperator(r[], c, n, n)
+	finalizer(finalize_op!, op)
+	return op
+end
+
 "Gaussian covariance exp(-d^2/(2 ell^2)) of an nx x ny unit grid as a matrix-free operator: entries are regenerated
 inside the product kernel, nothing of size n^2 is stored (`gsi_op_gridcov_implicit`).  Usable wherever a Matrix is."
 function GridCovImplicit(nx::Int, ny::Int, ell::Float64; c::Context=ctx())
