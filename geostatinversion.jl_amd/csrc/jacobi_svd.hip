@@ -15,6 +15,7 @@
 #include "../../include/gsi_hip.h"
 #include "hip_common.hpp"
 #include "backend.hpp"
+#include "jacobi_sched.hpp"
 #include <array>
 #include <atomic>
 #include <cstdlib>
@@ -24,15 +25,6 @@
 namespace gsi { namespace hipk {
 
 constexpr int SVD_THREADS = 256;   // 4 waves; a 16-lane quarter wave per column pair of an inner round
-
-// round-robin ("circle") tournament on n (even) players: pair q of round r
-__device__ __host__ inline void rr_pair(int n, int r, int q, int* a, int* b) {
-  if (q == 0) { *a = n - 1; *b = r % (n - 1); }
-  else {
-    *a = (r + q) % (n - 1);
-    *b = ((r - q) % (n - 1) + (n - 1)) % (n - 1);
-  }
-}
 
 __device__ inline double wave_allsum(double v) {
 #pragma unroll
@@ -364,6 +356,7 @@ static int svd_small_impl(hipStream_t st, double* G, int l, double* U, double* S
       if (first_use_on_this_device(attr_mask2))
         (void)hipFuncSetAttribute((const void*)jacobi_activity_kernel<SVD_W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
       std::vector<int32_t> flags((size_t)npairs, 1), sched;
+      std::vector<int> round_sizes;
       int32_t* d_flags = w.pairs;
       int32_t* d_sched = w.pairs + npairs;
       bool sparse = false;
@@ -374,48 +367,17 @@ static int svd_small_impl(hipStream_t st, double* G, int l, double* U, double* S
             hipLaunchKernelGGL(jacobi_block_kernel<SVD_W>, dim3(nblk / 2), dim3(SVD_THREADS), shmem, st, G, l, lp, nblk,
                                r, tol2, w.rotcount, 1, r == 0 ? 0 : 1, (const int32_t*)nullptr);
         } else {
-          // active cross pairs -> rounds of disjoint block pairs (greedy); a block whose own (diagonal) pair is active gets
-          // its intra-block sweep with the first entry it appears in (cross_only = 0 sweeps both blocks and the cross pairs)
-          std::vector<char> diag((size_t)nblk, 0);
-          std::vector<std::array<int32_t, 3>> edges;
-          for (int ba = 0, pi = 0; ba < nblk; ++ba)
-            for (int bb = ba; bb < nblk; ++bb, ++pi) {
-              if (!flags[(size_t)pi]) continue;
-              if (ba == bb) diag[(size_t)ba] = 1;
-              else edges.push_back({ba, bb, 1});
-            }
-          std::vector<char> touched((size_t)nblk, 0);
-          for (auto& e : edges) { touched[(size_t)e[0]] = 1; touched[(size_t)e[1]] = 1; }
-          for (int b = 0; b < nblk; ++b)
-            if (diag[(size_t)b] && !touched[(size_t)b]) {        // a block that is only active within itself: any partner
-              int partner = -1;
-              for (int c = 0; c < nblk && partner < 0; ++c)
-                if (c != b && diag[(size_t)c] && !touched[(size_t)c]) partner = c;
-              if (partner < 0) partner = (b + 1) % nblk;
-              edges.push_back({std::min(b, partner), std::max(b, partner), 1});
-              touched[(size_t)b] = 1; touched[(size_t)partner] = 1;
-            }
-          std::vector<std::vector<std::array<int32_t, 3>>> rounds;
-          std::vector<std::vector<char>> used;
-          for (auto& e : edges) {
-            size_t r = 0;
-            for (; r < rounds.size(); ++r)
-              if (!used[r][(size_t)e[0]] && !used[r][(size_t)e[1]]) break;
-            if (r == rounds.size()) { rounds.emplace_back(); used.emplace_back((size_t)nblk, 0); }
-            if (diag[(size_t)e[0]] || diag[(size_t)e[1]]) { e[2] = 0; diag[(size_t)e[0]] = 0; diag[(size_t)e[1]] = 0; }
-            rounds[r].push_back(e);
-            used[r][(size_t)e[0]] = 1; used[r][(size_t)e[1]] = 1;
-          }
-          sched.clear();
-          for (auto& rd : rounds) for (auto& e : rd) { sched.push_back(e[0]); sched.push_back(e[1]); sched.push_back(e[2]); }
+          // active cross pairs -> rounds of disjoint block pairs (greedy), each active block's own sweep with one of its
+          // entries (jacobi_sched.hpp)
+          jacobi_sparse_schedule(flags, nblk, sched, round_sizes);
           if ((int)sched.size() > 3 * npairs) throw Error(GSI_ERR_INTERNAL, "svd_small: schedule overflow");
           hipMemcpyAsync(d_sched, sched.data(), sizeof(int32_t) * sched.size(), hipMemcpyHostToDevice, st);
           hipStreamSynchronize(st);          // (pageable source: the copy must be over before `sched` is rebuilt)
           size_t off = 0;
-          for (auto& rd : rounds) {
-            hipLaunchKernelGGL(jacobi_block_kernel<SVD_W>, dim3((unsigned)rd.size()), dim3(SVD_THREADS), shmem, st, G, l, lp, nblk,
+          for (int rs : round_sizes) {
+            hipLaunchKernelGGL(jacobi_block_kernel<SVD_W>, dim3((unsigned)rs), dim3(SVD_THREADS), shmem, st, G, l, lp, nblk,
                                0, tol2, w.rotcount, 1, 1, (const int32_t*)(d_sched + off));
-            off += 3 * rd.size();
+            off += 3 * (size_t)rs;
           }
         }
         ++sweeps;
@@ -471,6 +433,7 @@ int svd_small(hipStream_t st, double* G, int64_t l64, double* U, double* S, cons
   if (forced == 16 && l <= 600) return svd_small_impl<16>(st, G, l, U, S, w);
   if (forced == 8 && l <= 1200) return svd_small_impl<8>(st, G, l, U, S, w);
   if (forced == 4 && l <= 2500) return svd_small_impl<4>(st, G, l, U, S, w);
+  if (forced == 2) return svd_small_impl<2>(st, G, l, U, S, w);
   if (l <= 600) return svd_small_impl<16>(st, G, l, U, S, w);
   if (l <= 1200) return svd_small_impl<8>(st, G, l, U, S, w);
   if (l <= 2500) return svd_small_impl<4>(st, G, l, U, S, w);

@@ -3,7 +3,8 @@
 The reference is Julia and cannot run in this image, and it ships no fixtures of its own, so these
 vectors come from oracle/oracle.py (same LAPACK routines, explicit Omega).  They freeze the oracle:
 tests compare oracle-now, the C restatement and the HIP path against them.
-Run:  python tests/golden/make_golden.py
+Run:  python tests/golden/make_golden.py            (everything)
+      python tests/golden/make_golden.py jacobi     (only jacobi_graded.npz: long-double Jacobi references, minutes)
 """
 import os
 import sys
@@ -17,7 +18,26 @@ from oracle import oracle as orc                      # noqa: E402
 from helpers import gaussian_cov, exponential_cov, powerlaw_fields   # noqa: E402
 
 
+JACOBI_GRADED = [(520, 256), (650, 320), (1210, 601)]
+
+
+def jacobi_graded():
+    """Singular values of the wide graded inputs of tests/test_jacobi_svd_gpu.py by the long-double Jacobi of
+    tests/jacobi_svd_model.py (svd_ref), rounded to float64, and each input's correctly rounded sum (math.fsum: the
+    same in any order) as a checksum of the regenerated input.  l = 601 takes a few minutes."""
+    import jacobi_svd_model as jm
+    out = {}
+    for n, l in JACOBI_GRADED:
+        W = jm.graded(n, l)
+        out[f"S_{n}_{l}"] = jm.svd_ref(W).astype(np.float64)
+        out[f"sum_{n}_{l}"] = np.float64(jm.exact_sum(W))
+    np.savez_compressed(os.path.join(HERE, "jacobi_graded.npz"), **out)
+
+
 def main():
+    if sys.argv[1:] == ["jacobi"]:
+        jacobi_graded()
+        return
     rng = np.random.default_rng(20261004)
     # case 1: dense Gaussian covariance, q = 2
     A = gaussian_cov(16, 12, 3.0)                       # n = 192
@@ -45,6 +65,7 @@ def main():
     # case 4: Nystrom KAT of test/testrmf.jl:21-29 (closed form)
     np.savez_compressed(os.path.join(HERE, "nystrom_kat.npz"), A=np.array([[2.0, -1, 0], [-1, 2, -1], [0, -1, 2]]),
                         eigenvalues=np.array([2 + np.sqrt(2), 2.0, 2 - np.sqrt(2)]))
+    jacobi_graded()
     print("wrote", sorted(f for f in os.listdir(HERE) if f.endswith(".npz")))
 
 
