@@ -985,6 +985,41 @@ int gsi_gemm(gsi_ctx* ctx, int trans, int64_t m, int64_t l, int64_t k, double al
   });
 }
 
+int gsi_gemm_view(gsi_ctx* ctx, int form, int trans, int64_t m, int64_t l, int64_t k, double alpha, double beta,
+                  const double* A, int64_t lda, int64_t a_off, const double* B, int64_t ldb, int64_t b_off, double* C,
+                  int64_t ldc, int64_t c_off, int64_t m_full, int64_t r0, int64_t* plan_out) {
+  return guarded([&] {
+    REQUIRE(ctx && A && C && plan_out, "NULL argument");
+    REQUIRE(form >= 0 && form <= 3, "gemm_view: form is 0 (gemm), 1 (syrk upper), 2 (trmm upper) or 3 (NN row block)");
+    REQUIRE(m >= 1 && l >= 1 && k >= 1, "bad shape");
+    REQUIRE(form == 1 || B, "NULL argument");
+    REQUIRE(form == 0 || (alpha == 1.0 && beta == 0.0), "gemm_view: forms 1 to 3 compute C = op(A) B (alpha 1, beta 0)");
+    REQUIRE(form == 0 || !trans, "gemm_view: trans belongs to form 0");
+    REQUIRE(form != 1 || m == l, "gemm_view: form 1 is the l x l product A'A (m == l)");
+    REQUIRE(form != 3 || (r0 >= 0 && r0 + m <= m_full), "gemm_view: row block outside the full product");
+    // the operands as they lie on the device: A ar x ac, B k x l, C crows x l
+    const bool tn = trans || form == 1;
+    const int64_t ar = (form == 3) ? m_full : (tn ? k : m), ac = tn ? m : k;
+    const int64_t crows = (form == 3) ? m_full : m;
+    REQUIRE(lda >= ar && ldc >= crows && (form == 1 || ldb >= k), "leading dimension too small");
+    REQUIRE(a_off >= 0 && b_off >= 0 && c_off >= 0, "negative offset");
+    Backend* be = ctx->c.be.get();
+    const size_t na = (size_t)a_off + (size_t)lda * (size_t)ac, nc = (size_t)c_off + (size_t)ldc * (size_t)l;
+    const size_t nb = (form == 1) ? 1 : (size_t)b_off + (size_t)ldb * (size_t)l;
+    Buf Ad(be, na), Bd(be, nb), Cd(be, nc);
+    // whatever the views do not cover is NaN (all bytes 0xFF): a read of the padding poisons the result
+    be->fill_bytes(Ad.p, 0xFF, na);
+    be->fill_bytes(Bd.p, 0xFF, nb);
+    be->upload2d(Ad.p + a_off, lda, A, ar, ar, ac);
+    if (form != 1) be->upload2d(Bd.p + b_off, ldb, B, k, k, l);
+    be->upload2d(Cd.p, (int64_t)nc, C, (int64_t)nc, (int64_t)nc, 1);          // C: the whole image, there and back
+    be->gemm_view(form, trans != 0, m, l, k, alpha, Ad.p + a_off, lda, Bd.p + b_off, ldb, beta, Cd.p + c_off, ldc, m_full, r0,
+                  plan_out);
+    be->download2d(C, (int64_t)nc, Cd.p, (int64_t)nc, (int64_t)nc, 1);
+    check_async_errors(ctx->c);
+  });
+}
+
 // ---- consumers -----------------------------------------------------------------------
 namespace {
 void pcga_params_impl(Context& c, const double* Zdev, int64_t n, int64_t K, const double* s, const double* X,

@@ -73,6 +73,23 @@ class Backend {
   virtual void gemm_tn(int64_t m, int64_t l, int64_t k, double alpha, const double* A, int64_t lda,
                        const double* B, int64_t ldb, double beta, double* C, int64_t ldc) = 0;
 
+  // The contraction's host launchers run directly on views the caller laid out (gsi_gemm_view, the kernel tests): form 0 =
+  // gemm_nn / gemm_tn by `trans`, 1 = C (l x l) = A'A upper-triangle tiles (A k x l), 2 = C = A B with B (k x l) upper
+  // triangular, 3 = rows [r0, r0 + m) of the m_full-row NN product (A, C: element (0, 0) of the full matrices).  plan8: the
+  // launcher's own decisions -- nt, column chunks, xmode, wide, K splits launched, persistent, grid.x, output tiles.
+  virtual void gemm_view(int form, bool trans, int64_t m, int64_t l, int64_t k, double alpha, const double* A, int64_t lda,
+                         const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int64_t m_full, int64_t r0,
+                         int64_t* plan8) {
+    (void)form; (void)trans; (void)m; (void)l; (void)k; (void)alpha; (void)A; (void)lda; (void)B; (void)ldb; (void)beta;
+    (void)C; (void)ldc; (void)m_full; (void)r0; (void)plan8;
+    throw Error(1 /* GSI_ERR_ARG */, "gemm_view: not available on this backend");
+  }
+  // every byte of p[0, count) <- `byte`
+  virtual void fill_bytes(double* p, int byte, size_t count) {
+    (void)p; (void)byte; (void)count;
+    throw Error(1 /* GSI_ERR_ARG */, "fill_bytes: not available on this backend");
+  }
+
   // C(m x l) = G * B(k x l) for a stationary grid covariance G(i, j) = tab[|x_i - x_j| * ny + |y_i - y_j|],
   // grid point i = (i / ny, i % ny), rows roff.., reduction indices koff..; tab = the nx * ny table of the kernel over
   // grid offsets.  G is generated, never stored (the "implicit" operator).

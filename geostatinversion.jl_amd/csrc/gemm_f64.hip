@@ -129,7 +129,7 @@ static int gemm_chunk_tiles(int) { return NTMAX; }
 
 static void gemm_launch(hipStream_t st, bool transA, const GenA* gen, int64_t M, int64_t L, int64_t K, double alpha,
                         const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
-                        int64_t ldc, double* ws, int tri = 0, int gen_mode = 1, int force_nsplit = 0) {
+                        int64_t ldc, double* ws, int tri = 0, int gen_mode = 1, int force_nsplit = 0, GemmPlan* plan = nullptr) {
   if (M <= 0 || L <= 0) return;
   // The kernel addresses a tile with one uniform 64-bit base per operand plus per-thread byte offsets spanning up to
   // 160 columns of B, 128 rows of a transposed A or 32 columns of a plain A: 32 bits reach panels of ~3.3 million
@@ -175,6 +175,7 @@ static void gemm_launch(hipStream_t st, bool transA, const GenA* gen, int64_t M,
     nitems = active;
     grid.x = (unsigned)ncus;
   }
+  if (plan != nullptr) *plan = {nt, nchunks, xmode, wide, ns_eff, nitems > 0 ? 1 : 0, (int64_t)grid.x, active};
   const GenA none = {nullptr, 1, 0, 0, 0, 0.0, 0.0, 0.0};
   if (gen != nullptr && gen_mode == 2)
     launch_dispatch<false, 2>(nt, grid, st, M, L, K, A, lda, B, ldb, C, ldc, alpha, beta, slabs, kchunk, (int)nchunks, wide, xmode, tri, *gen, nitems);
@@ -202,8 +203,8 @@ void gemm_splitk_reduce(hipStream_t st, int64_t M, int64_t L, int nsplit, const 
 
 // Host launchers. `ws` must hold gemm_workspace_doubles(M, L, K) doubles (or be null if 0).
 void gemm_f64(hipStream_t st, bool transA, int64_t M, int64_t L, int64_t K, double alpha, const double* A,
-              int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* ws) {
-  gemm_launch(st, transA, nullptr, M, L, K, alpha, A, lda, B, ldb, beta, C, ldc, ws);
+              int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* ws, GemmPlan* plan) {
+  gemm_launch(st, transA, nullptr, M, L, K, alpha, A, lda, B, ldb, beta, C, ldc, ws, 0, 1, 0, plan);
 }
 
 // The K split gemm_f64 (NN or TN, plain operands) uses for an M x L x K product, and rows [r0, r0 + mb) of that product
@@ -220,21 +221,21 @@ size_t gemm_rowblock_workspace_doubles(int64_t M_full, int64_t mb, int64_t L, in
   return ns > 1 ? (size_t)ns * (size_t)mb * (size_t)L : 0;
 }
 void gemm_f64_nn_rowblock(hipStream_t st, int64_t M_full, int64_t r0, int64_t mb, int64_t L, int64_t K, const double* A,
-                          int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, double* ws) {
-  gemm_launch(st, false, nullptr, mb, L, K, 1.0, A + r0, lda, B, ldb, 0.0, C + r0, ldc, ws, 0, 1, gemm_split_for(M_full, L, K));
+                          int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, double* ws, GemmPlan* plan) {
+  gemm_launch(st, false, nullptr, mb, L, K, 1.0, A + r0, lda, B, ldb, 0.0, C + r0, ldc, ws, 0, 1, gemm_split_for(M_full, L, K), plan);
 }
 
 // C (l x l, ld ldc) = A'A for A m x l: only tiles that touch the upper triangle are computed, the rest of C is
 // unspecified (cholqr.hip mirrors the upper triangle afterwards).  ws: gemm_syrk_workspace_doubles(l, m).
 void gemm_f64_syrk_upper(hipStream_t st, int64_t l, int64_t m, const double* A, int64_t lda, double* C, int64_t ldc,
-                         double* ws) {
-  gemm_launch(st, true, nullptr, l, l, m, 1.0, A, lda, A, lda, 0.0, C, ldc, ws, 1);
+                         double* ws, GemmPlan* plan) {
+  gemm_launch(st, true, nullptr, l, l, m, 1.0, A, lda, A, lda, 0.0, C, ldc, ws, 1, 1, 0, plan);
 }
 // C (M x L) = A (M x K) * B with B (K x L) upper triangular: entries below the diagonal must be ZERO (those beyond
 // a column chunk's last column are not read, the ones inside the chunk are)
 void gemm_f64_trmm_upper(hipStream_t st, int64_t M, int64_t L, int64_t K, const double* A, int64_t lda, const double* B,
-                         int64_t ldb, double* C, int64_t ldc, double* ws) {
-  gemm_launch(st, false, nullptr, M, L, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, ws, 2);
+                         int64_t ldb, double* C, int64_t ldc, double* ws, GemmPlan* plan) {
+  gemm_launch(st, false, nullptr, M, L, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, ws, 2, 1, 0, plan);
 }
 
 // C (M x L) = G * B with G(i, k) = tab[|x_i - x_k| * ny + |y_i - y_k|], i = roff + row, k = koff + reduction index;

@@ -369,6 +369,32 @@ class HipBackend : public Backend {
     hipk::gemm_f64(st_, true, m, l, k, alpha, A, lda, B, ldb, beta, C, ldc, ws);
     check_launch("gemm_tn");
   }
+  void gemm_view(int form, bool trans, int64_t m, int64_t l, int64_t k, double alpha, const double* A, int64_t lda,
+                 const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int64_t m_full, int64_t r0,
+                 int64_t* plan8) override {
+    bind();
+    hipk::GemmPlan p = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (form == 0) {
+      double* ws = gemm_ws(hipk::gemm_workspace_doubles(m, l, k));
+      hipk::gemm_f64(st_, trans, m, l, k, alpha, A, lda, B, ldb, beta, C, ldc, ws, &p);
+    } else if (form == 1) {
+      double* ws = gemm_ws(hipk::gemm_syrk_workspace_doubles(l, k));
+      hipk::gemm_f64_syrk_upper(st_, l, k, A, lda, C, ldc, ws, &p);
+    } else if (form == 2) {
+      double* ws = gemm_ws(hipk::gemm_workspace_doubles(m, l, k));
+      hipk::gemm_f64_trmm_upper(st_, m, l, k, A, lda, B, ldb, C, ldc, ws, &p);
+    } else {
+      double* ws = gemm_ws(hipk::gemm_rowblock_workspace_doubles(m_full, m, l, k));
+      hipk::gemm_f64_nn_rowblock(st_, m_full, r0, m, l, k, A, lda, B, ldb, C, ldc, ws, &p);
+    }
+    check_launch("gemm_view");
+    const int64_t out[8] = {p.nt, p.nchunks, p.xmode, p.wide, p.nsplit, p.persistent, p.grid_x, p.active};
+    for (int i = 0; i < 8; ++i) plan8[i] = out[i];
+  }
+  void fill_bytes(double* p, int byte, size_t count) override {
+    bind();
+    HIP_CHECK(hipMemsetAsync(p, byte, count * sizeof(double), st_));
+  }
   void gemm_nn_gridcov(int64_t m, int64_t l, int64_t k, const double* tab, int64_t nx, int64_t ny, int64_t roff,
                        int64_t koff, const double* B, int64_t ldb, double* C, int64_t ldc) override {
     bind();

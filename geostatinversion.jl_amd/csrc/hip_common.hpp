@@ -19,13 +19,19 @@ inline bool first_use_on_this_device(std::atomic<uint64_t>& mask) {
 }
 
 // ---- gemm_f64.hip ----
+// What the launcher decided for one product, filled where it computes each value when a host launcher is given a plan
+// (gsi_gemm_view hands it to the kernel tests, which assert on what ran): column tiles per chunk, column chunks, XMODE of the
+// instantiation, 16-byte operator loads, K splits launched, persistent mode, grid.x, output tiles.
+struct GemmPlan { int64_t nt, nchunks, xmode, wide, nsplit, persistent, grid_x, active; };
 size_t gemm_workspace_doubles(int64_t M, int64_t L, int64_t K);
 void gemm_f64(hipStream_t st, bool transA, int64_t M, int64_t L, int64_t K, double alpha, const double* A,
-              int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* ws);
+              int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* ws,
+              GemmPlan* plan = nullptr);
 // rows [r0, r0 + mb) of the NN product of an M_full-row launch, with that launch's K split (bit-identical blocks)
 size_t gemm_rowblock_workspace_doubles(int64_t M_full, int64_t mb, int64_t L, int64_t K);
 void gemm_f64_nn_rowblock(hipStream_t st, int64_t M_full, int64_t r0, int64_t mb, int64_t L, int64_t K, const double* A,
-                          int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, double* ws);
+                          int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, double* ws,
+                          GemmPlan* plan = nullptr);
 // C (l x l) = A'A, upper-triangle tiles only; C = A * B with B upper triangular (CholeskyQR: half the flops each)
 size_t gemm_syrk_workspace_doubles(int64_t l, int64_t m);
 // syrk_f64.hip: G = A'A (both triangles) for l <= 320 by the register-resident kernel; false = shape not covered
@@ -35,9 +41,9 @@ bool syrk_full_from_upper(hipStream_t st, int64_t l, int64_t m, const double* Y,
 bool trmm_upper_tall(hipStream_t st, int64_t m, int64_t l, const double* A, int64_t lda, const double* X, int64_t ldx, double* C,
                      int64_t ldc);
 void gemm_f64_syrk_upper(hipStream_t st, int64_t l, int64_t m, const double* A, int64_t lda, double* C, int64_t ldc,
-                         double* ws);
+                         double* ws, GemmPlan* plan = nullptr);
 void gemm_f64_trmm_upper(hipStream_t st, int64_t M, int64_t L, int64_t K, const double* A, int64_t lda, const double* B,
-                         int64_t ldb, double* C, int64_t ldc, double* ws);
+                         int64_t ldb, double* C, int64_t ldc, double* ws, GemmPlan* plan = nullptr);
 // C = G * B, G(i,k) = tab[|x_i-x_k| * ny + |y_i-y_k|] generated in registers (tab: nx * ny kernel table)
 void gemm_f64_gridcov(hipStream_t st, int64_t M, int64_t L, int64_t K, const double* tab, int64_t nx, int64_t ny,
                       int64_t roff, int64_t koff, const double* B, int64_t ldb, double* C, int64_t ldc, double* ws);

@@ -271,3 +271,29 @@ def gemm(A, B, *, trans=False, alpha=1.0, ctx=None):
     L.check(ctx.lib.gsi_gemm(ctx.h, int(trans), m, l, k, float(alpha), L.dptr(Af), Af.shape[0], L.dptr(Bf), k,
                              L.dptr(Cm), m), ctx.lib)
     return Cm
+
+
+GEMM_PLAN_FIELDS = ("nt", "nchunks", "xmode", "wide", "nsplit", "persistent", "grid_x", "active")
+
+
+def gemm_view(A, B, C_image, *, m, l, k, form=0, trans=False, alpha=1.0, beta=0.0, lda, a_off=0, ldb=0, b_off=0, ldc,
+              c_off=0, m_full=0, r0=0, ctx=None):
+    """One contraction launch on a device layout of the caller's choosing (`gsi_gemm_view`, the kernel tests' entry).
+
+    A, B: packed matrices; on the device they lie at element offset a_off / b_off of an allocation filled with NaN, with
+    leading dimension lda / ldb.  C_image: the whole device image of C, c_off + ldc * l doubles.  Returns (the image after the
+    launch, {field: value} for GEMM_PLAN_FIELDS as the launcher decided them)."""
+    ctx = ctx or default_context()
+    Af = L.fmat(A, "A")
+    Bf = None if B is None else L.fmat(B, "B")
+    img = np.array(C_image, dtype=np.float64).reshape(-1)
+    if img.size != c_off + ldc * l:
+        raise ValueError("C_image must hold c_off + ldc * l doubles")
+    ar, ac = (m_full, k) if form == 3 else ((k, m) if (trans or form == 1) else (m, k))
+    if Af.shape != (ar, ac) or (Bf is not None and Bf.shape != (k, l)):
+        raise ValueError("dimension mismatch")
+    plan = np.zeros(8, dtype=np.int64)
+    L.check(ctx.lib.gsi_gemm_view(ctx.h, int(form), int(bool(trans)), m, l, k, float(alpha), float(beta), L.dptr(Af), lda,
+                                  a_off, None if Bf is None else L.dptr(Bf), ldb, b_off, L.dptr(img), ldc, c_off, m_full, r0,
+                                  plan.ctypes.data_as(C.POINTER(L.c_i64))), ctx.lib)
+    return img, dict(zip(GEMM_PLAN_FIELDS, (int(v) for v in plan)))
