@@ -93,15 +93,17 @@ class Context:
         """Which path ran under the communicator (`gsi_ctx_path_info`): the form of the panel LUs (and how many ran in each
         form since the last phase_reset), the self-test mask of the in-kernel pivot exchange, collectives entered since the
         last phase_reset, the ranks the communicator joined, LU time-outs seen / hidden by a transparent re-run; randsvd calls that
-        finished in the sample space of a LowRankCovMatrix, range-finder power steps formed there and the ones declined."""
-        n = 16
+        finished in the sample space of a LowRankCovMatrix, range-finder power steps formed there and the ones declined, panels
+        of those steps factored as two column halves and the ones factored again whole."""
+        n = 18
         out = (C.c_int64 * n)()
         L.check(self.lib.gsi_ctx_path_info(self.h, out, n), self.lib)
         forms = {self.LU_FORMS[f]: int(out[6 + f]) for f in range(1, 6) if out[6 + f]}
         return {"lu_form": self.LU_FORMS[out[0]] if 0 <= out[0] < 6 else int(out[0]), "lu_forms_run": forms,
                 "lu_selftest_mask": int(out[1]), "collectives": int(out[2]), "n_ranks_seen": int(out[3]),
                 "lu_timeouts": int(out[4]), "lu_timeouts_recovered": int(out[5]), "svd_sweep_cap_hits": int(out[12]),
-                "lowrank_tails": int(out[13]), "lowrank_power_steps": int(out[14]), "lowrank_power_declines": int(out[15])}
+                "lowrank_tails": int(out[13]), "lowrank_power_steps": int(out[14]), "lowrank_power_declines": int(out[15]),
+                "lowrank_split_lus": int(out[16]), "lowrank_split_declines": int(out[17])}
 
     def release_cache(self):
         """Return cached device memory (released panels, idle workspaces) to the driver (`gsi_ctx_release_cache`)."""

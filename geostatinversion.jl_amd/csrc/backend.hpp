@@ -234,6 +234,41 @@ class Backend {
     (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)ipiv; (void)L; (void)ldl; (void)l; (void)c; (void)T_next;
     return false;
   }
+  // The same panel factored as two column halves, split at l1: what the right half's update by the
+  // left half's L would do to n x (l - l1) numbers is a change of N x (l - l1) coefficients.  The caller runs
+  //   P[:, 0:l1] = S (c T1);  lu_L_keep(P, n, l1);                       lowrank_split_schur  ->  Tt
+  //   P[:, l1:l] = S Tt;                                                  lowrank_split_rows
+  //   lu_L_keep(P + l1 + l1 ldp, n - l1, l - l1);                         lowrank_split_join   ->  ipiv of the whole panel
+  // and then lowrank_power_step on the whole panel, whose check covers both halves.
+  // lowrank_split_ok: both halves would take the factorization whose pivots and top block the steps below read (false: the
+  //   caller factors the panel whole; also the default, so that no other backend is asked for the rest).
+  // lowrank_split_schur: ipiv1, the left half's interchanges, are kept; with [U11 | U12] = c L11^-1 S[perm(0:l1)] T from the
+  //   pivot rows and C1 U11 = c T1:  Tt (N x (l - l1), ld N) <- c T2 - C1 U12, so that S Tt is the right half's Schur
+  //   complement on all rows, in S's row order.
+  // lowrank_split_rows: the right half's rows brought into the left half's pivoted order, its rows [0, l1) cleared.
+  // lowrank_split_join: the second factorization's interchanges ipiv2 applied to rows >= l1 of the left half; *ipiv <- the l
+  //   interchanges of the whole panel (valid until the next lowrank_split_schur).
+  // lowrank_split_undo: the power step declined what the halves gave and the caller factors the panel again, whole: a zero
+  //   pivot only a half's factorization flagged is forgotten.
+  virtual bool lowrank_split_ok(int64_t n, int64_t N, int64_t l, int64_t l1) {
+    (void)n; (void)N; (void)l; (void)l1;
+    return false;
+  }
+  virtual void lowrank_split_schur(const double* S, int64_t lds, int64_t n, int64_t N, const double* T, const int32_t* ipiv1,
+                                   const double* P, int64_t ldp, int64_t l, int64_t l1, double c, double* Tt) {
+    (void)S; (void)lds; (void)n; (void)N; (void)T; (void)ipiv1; (void)P; (void)ldp; (void)l; (void)l1; (void)c; (void)Tt;
+    throw Error(1 /* GSI_ERR_ARG */, "lowrank_split_schur: not available on this backend");
+  }
+  virtual void lowrank_split_rows(double* P, int64_t ldp, int64_t n, int64_t l, int64_t l1) {
+    (void)P; (void)ldp; (void)n; (void)l; (void)l1;
+    throw Error(1 /* GSI_ERR_ARG */, "lowrank_split_rows: not available on this backend");
+  }
+  virtual void lowrank_split_join(double* P, int64_t ldp, int64_t n, int64_t l, int64_t l1, const int32_t* ipiv2,
+                                  int32_t** ipiv) {
+    (void)P; (void)ldp; (void)n; (void)l; (void)l1; (void)ipiv2; (void)ipiv;
+    throw Error(1 /* GSI_ERR_ARG */, "lowrank_split_join: not available on this backend");
+  }
+  virtual void lowrank_split_undo() {}
   // G (l x l, ld l), columns orthogonalised in place by one-sided Jacobi; on return
   // U (l x l) = left singular vectors sorted by descending S, S (l) singular values.
   virtual void svd_small(double* G, int64_t l, double* U, double* S) = 0;
@@ -318,6 +353,10 @@ class Backend {
   virtual void profile(bool on) = 0;
   virtual void phase_begin(Phase p) = 0;
   virtual void phase_end(Phase p) = 0;
+  // phase_end for an interval that belongs to an entry the phase has already counted (the second product and the second
+  // factorization of a panel that is factored in two halves): its time is added, the phase's count stays.  bench.py divides a
+  // phase's time by its count, so one panel must stay one entry.
+  virtual void phase_end_more(Phase p) { phase_end(p); }
   virtual void phase_reset() = 0;
   virtual void phase_times(double* ms, int64_t* counts) = 0;
   // [0] CholeskyQR2 factorizations, [1] Householder factorizations (incl. fallbacks), [2] Jacobi sweeps of
@@ -375,6 +414,11 @@ struct ScopedPhase {
   Backend* be; Phase p;
   ScopedPhase(Backend* b, Phase ph) : be(b), p(ph) { be->phase_begin(p); }
   ~ScopedPhase() { be->phase_end(p); }
+};
+struct ScopedPhaseMore {       // more time for the entry a ScopedPhase of the same phase counted (Backend::phase_end_more)
+  Backend* be; Phase p;
+  ScopedPhaseMore(Backend* b, Phase ph) : be(b), p(ph) { be->phase_begin(p); }
+  ~ScopedPhaseMore() { be->phase_end_more(p); }
 };
 
 }  // namespace gsi

@@ -90,7 +90,7 @@ class HipBackend : public Backend {
     hipStreamSynchronize(st_);
     stager_.reset();
     if (ev_stage_) hipEventDestroy(ev_stage_);
-    for (auto& b : {&ws_gemm_, &ws_lu_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_}) free_ws(*b);
+    for (auto& b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_}) free_ws(*b);
     collect_garbage();
     for (auto& b : pool_) hipFree(b.p);
     for (auto& ev : ev_pool_) hipEventDestroy(ev);
@@ -190,7 +190,7 @@ class HipBackend : public Backend {
   }
   void release_cache() override {
     bind();
-    for (DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_})
+    for (DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_})
       if (b->bytes > ((size_t)64 << 20)) free_ws(*b);
     (void)hipStreamSynchronize(st_);
     collect_garbage();
@@ -198,7 +198,7 @@ class HipBackend : public Backend {
   }
   int64_t bytes_in_use() const override {
     int64_t ws = 0;
-    for (const DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_svdf_, &ws_qr_hh_})
+    for (const DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_svdf_, &ws_qr_hh_})
       if (!b->pooled) ws += (int64_t)b->bytes;          // pooled workspaces are counted by alloc()
     return in_use_ + pooled_ + ws + (int64_t)garbage_bytes_;
   }
@@ -1200,6 +1200,92 @@ class HipBackend : public Backend {
     if (h->v[0] != 0 || h->v[1] != 0) return false;   // a zero pivot (or a lost exchange): the entry point reports it
     return finite && mx <= CHECK_MAX;
   }
+  // ---- the panel of a power step factored in two column halves (Backend::lowrank_split_*) ----
+  // What the three steps hand to each other lies in ws_split_: the l interchanges of the whole panel, the verdicts of the two
+  // compositions, and the first half's index lists.  Nothing comes to the host: every launch shape follows from (n, N, l, l1).
+  static constexpr int64_t SPLIT_MAX_L1 = 192;
+  struct SplitWs { int32_t* piv; int32_t* verdict1; int32_t* verdict2; int64_t* idx1; int64_t o_chk, o_sm, ldr; };
+  static int64_t up8(int64_t x) { return (x + 7) & ~(int64_t)7; }
+  SplitWs split_ws(int64_t l1) {
+    // lr_compose's lists for the first half: the moved rows at 0, its l1 pivot rows at o_chk (no sampled rows), S[mv] at o_sm
+    SplitWs w;
+    w.o_chk = up8(2 * l1); w.o_sm = w.o_chk + up8(l1); w.ldr = up8(w.o_sm + 2 * l1);
+    grow(ws_split_, 2048 + sizeof(int64_t) * (size_t)(2 * up8(5 * SPLIT_MAX_L1 + 16) + SPLIT_MAX_L1));
+    char* base = (char*)ws_split_.p;
+    w.piv = (int32_t*)base;                               // [2 SPLIT_MAX_L1]
+    w.verdict1 = (int32_t*)(base + 1536 + 64);
+    w.verdict2 = w.verdict1 + 4;
+    w.idx1 = (int64_t*)(base + 2048);                      // src, sub (ldr each), chk (l1)
+    return w;
+  }
+  bool lu2_takes(int64_t m) {                             // lu_L_impl's first choice: the leaves held in registers
+    static const bool tall_first = (getenv("GSI_LU_TALL") != nullptr && getenv("GSI_LU_TALL")[0] == '1');
+    hipk::Lu2Work w;
+    return !tall_first && !lu2_lost_ && ranks_sharing_device_ <= 1 && hipk::lu2_config(m, ncus_, &w.bs, &w.rpt, &w.grid) &&
+           lu2_fits(w.bs, w.rpt, w.grid);
+  }
+  bool lowrank_split_ok(int64_t n, int64_t N, int64_t l, int64_t l1) override {
+    bind();
+    if (l1 < 1 || l1 > SPLIT_MAX_L1 || l <= l1 || l > 2 * l1 || l - l1 < 8 || l > 384 || N < 1 || N > 4096 || n < 2 * l ||
+        n >= ((int64_t)1 << 31))
+      return false;
+    return lu2_takes(n) && lu2_takes(n - l1);
+  }
+  void lowrank_split_schur(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* T, const int32_t* ipiv1,
+                           const double* P, int64_t ldp, int64_t l, int64_t l1, double c, double* Tt) override {
+    bind();
+    const int64_t l2 = l - l1;
+    const SplitWs w = split_ws(l1);
+    const size_t l1l = (size_t)up8(l1 * l), Nl1 = (size_t)up8(N * l1);
+    Scratch buf(this, (size_t)up8(l1) * (size_t)N + 2 * l1l + 8 + Nl1);
+    double* R = buf.p;                      // S[perm(0:l1)] (l1 x N, ld up8(l1))
+    double* Mp = R + (size_t)up8(l1) * N;   // R T (l1 x l)
+    double* Ut11 = Mp + l1l;                // U11' (l1 x l1), then U12 (l1 x l2)
+    double* U12 = Ut11 + (size_t)up8(l1 * l1);
+    double* C1 = Mp + 2 * l1l + 8;          // c T1 U11^-1 (N x l1)
+    size_t gmax = hipk::gemm_workspace_doubles(l1, l, N);
+    gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l2, l1));
+    double* ws = gemm_ws(gmax + 64);
+    int64_t* src = w.idx1, * sub = w.idx1 + w.ldr, * chk = w.idx1 + 2 * w.ldr;
+    hipk::lr_compose(st_, ipiv1, flags_ + 0, n, l1, l1, w.o_chk, w.o_sm, w.ldr, src, sub, chk, w.verdict1);
+    hipk::lr_pivots(st_, ipiv1, l1, 0, w.piv);                                                  // (the next LU reuses ws_lu_)
+    hipk::lr_gather_rows(st_, Sm, lds, N, src + w.o_chk, sub + w.o_chk, l1, R, up8(l1));
+    hipk::gemm_f64(st_, false, l1, l, N, 1.0, R, up8(l1), T, N, 0.0, Mp, l1, ws);             // S[perm(0:l1)] T
+    hipk::lr_solve_u12(st_, P, ldp, Mp, l1, l, c, Ut11, U12);                                   // [U11 | U12] = c L11^-1 Mp
+    hipk::lr_solve_c(st_, Ut11, l1, T, N, c, C1);                                               // C1 U11 = c T1
+    hipk::scal_copy(st_, N * l2, c, T + (size_t)N * l1, Tt);
+    hipk::gemm_f64(st_, false, N, l2, l1, -1.0, C1, N, U12, l1, 1.0, Tt, N, ws);              // c T2 - C1 U12
+    check_launch("lowrank_split_schur");
+  }
+  void lowrank_split_rows(double* P, int64_t ldp, int64_t n, int64_t l, int64_t l1) override {
+    bind();
+    (void)n;
+    const int64_t l2 = l - l1;
+    const SplitWs w = split_ws(l1);
+    Scratch tmp(this, (size_t)(2 * l1) * (size_t)l2);
+    hipk::lr_move_rows(st_, P + (size_t)l1 * ldp, ldp, l2, w.idx1, w.idx1 + w.ldr, w.verdict1, 2 * l1, tmp.p, 2 * l1, l1);
+    check_launch("lowrank_split_rows");
+  }
+  void lowrank_split_join(double* P, int64_t ldp, int64_t n, int64_t l, int64_t l1, const int32_t* ipiv2,
+                          int32_t** ipiv) override {
+    bind();
+    const int64_t l2 = l - l1;
+    const SplitWs w = split_ws(l1);
+    const int64_t ldr = up8(4 * l2);        // the moved rows at 0 and S[mv] at 2 l2; no check rows
+    Scratch buf(this, (size_t)(2 * ldr + 8) + (size_t)(2 * l2) * (size_t)l1);
+    int64_t* src = reinterpret_cast<int64_t*>(buf.p), * sub = src + ldr, * chk = sub + ldr;
+    double* tmp = buf.p + 2 * ldr + 8;
+    hipk::lr_compose(st_, ipiv2, flags_ + 0, n - l1, l2, 0, 2 * l2, 2 * l2, ldr, src, sub, chk, w.verdict2);
+    hipk::lr_pivots(st_, ipiv2, l2, l1, w.piv + l1);
+    hipk::lr_move_rows(st_, P + l1, ldp, l1, src, sub, w.verdict2, 2 * l2, tmp, 2 * l2, 0);
+    check_launch("lowrank_split_join");
+    *ipiv = w.piv;
+  }
+  void lowrank_split_undo() override {
+    bind();
+    hipk::lr_forget_zero_pivot(st_, flags_ + 0);
+    check_launch("lowrank_split_undo");
+  }
   void svd_small(double* G, int64_t l, double* U, double* S) override {
     bind();
     if (l > 5000) throw Error(GSI_ERR_ARG, "sketch width l = K+p > 5000 is not supported by the LDS-resident block Jacobi SVD");
@@ -1438,10 +1524,13 @@ class HipBackend : public Backend {
     cur_.b = get_event();
     hipEventRecord(cur_.a, st_);
   }
-  void phase_end(Phase) override {
+  void phase_end(Phase) override { phase_end_counted(true); }
+  void phase_end_more(Phase) override { phase_end_counted(false); }
+  void phase_end_counted(bool counted) {
     if (!prof_) return;
     if (roctx().pop) roctx().pop();
     hipEventRecord(cur_.b, st_);
+    cur_.counted = counted;
     records_.push_back(cur_);
   }
   void phase_reset() override {
@@ -1456,7 +1545,7 @@ class HipBackend : public Backend {
     hipStreamSynchronize(st_);
     for (auto& r : records_) {
       float t = 0.f;
-      if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) { acc_ms_[r.phase] += t; acc_n_[r.phase] += 1; }
+      if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) { acc_ms_[r.phase] += t; acc_n_[r.phase] += r.counted ? 1 : 0; }
       ev_pool_.push_back(r.a);
       ev_pool_.push_back(r.b);
     }
@@ -1480,7 +1569,7 @@ class HipBackend : public Backend {
     Scratch(const Scratch&) = delete;
     Scratch& operator=(const Scratch&) = delete;
   };
-  struct Rec { Phase phase; hipEvent_t a, b; };
+  struct Rec { Phase phase; hipEvent_t a, b; bool counted; };
   hipEvent_t get_event() {
     if (!ev_pool_.empty()) { hipEvent_t e = ev_pool_.back(); ev_pool_.pop_back(); return e; }
     hipEvent_t e;
@@ -1557,7 +1646,7 @@ class HipBackend : public Backend {
   int32_t* flags_ = nullptr;  // [0] lu info, [1] chol info, [8] jacobi rotation counter
   double* scal_ = nullptr;
   void* pin_power_ = nullptr; // pinned: the verdict of a power step (lowrank_power_step)
-  DevBuf ws_gemm_, ws_lu_, ws_qr_, ws_svd_, ws_blas2_, ws_lus_, ws_svdf_, ws_qr_hh_;
+  DevBuf ws_gemm_, ws_lu_, ws_split_, ws_qr_, ws_svd_, ws_blas2_, ws_lus_, ws_svdf_, ws_qr_hh_;
   std::mutex mu_;
   std::vector<DevBuf> sizes_;
   std::vector<DevBuf> pool_;

@@ -235,6 +235,16 @@ void lr_compose(hipStream_t st, const int32_t* piv, const int32_t* info, int64_t
 // Ut (l x l) <- (c L11^-1 Mp)' on and below the diagonal, L11 the unit lower triangle on top of L;  C (N x l) <- c T U^-1
 void lr_solve_u(hipStream_t st, const double* L, int64_t ldl, const double* Mp, int64_t l, double c, double* Ut);
 void lr_solve_c(hipStream_t st, const double* Ut, int64_t l, const double* T, int64_t N, double c, double* C);
+// A panel factored in two column halves.  [U11 | U12] = c L11^-1 Mp from the left half's pivot rows,
+// Mp (l1 x l, ld l1): Ut11 (l1 x l1) <- U11' on and below its diagonal, U12 (l1 x (l - l1), ld l1) as it stands
+void lr_solve_u12(hipStream_t st, const double* L, int64_t ldl, const double* Mp, int64_t l1, int64_t l, double c, double* Ut11,
+                  double* U12);
+// X[sub[k]] <- X[src[k]] on nc columns of X (ld ldx) for the k < verdict[2] (<= maxmv) moved rows of lr_compose's first block,
+// all read into tmp (maxmv x nc, ld ldt) before any is written; then rows [0, nzero) <- 0
+void lr_move_rows(hipStream_t st, double* X, int64_t ldx, int64_t nc, const int64_t* src, const int64_t* sub,
+                  const int32_t* verdict, int64_t maxmv, double* tmp, int64_t ldt, int64_t nzero);
+void lr_pivots(hipStream_t st, const int32_t* piv, int64_t cnt, int64_t add, int32_t* dst);   // dst[j] <- piv[j] + add
+void lr_forget_zero_pivot(hipStream_t st, int32_t* info);                                      // *info > 0: <- 0
 // ---- jacobi_svd.hip ----
 struct SvdWork {
   int32_t* rotcount;  // [1]

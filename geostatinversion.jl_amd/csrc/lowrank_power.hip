@@ -314,4 +314,107 @@ void lr_solve_c(hipStream_t st, const double* Ut, int64_t l, const double* T, in
                      N, c, C);
 }
 
+// ---- a panel factored in two column halves (hip_backend.hip: lowrank_split_*) ----
+// The first l1 rows of U, [U11 | U12] = c L11^-1 Mp, from the l1 pivot rows of the left half: Mp (l1 x l, ld l1) = S[perm(0:l1)] T,
+// L11 the unit lower triangle on top of the left half.  Workgroup b solves the columns [b NC, b NC + NC).  A column j < l1
+// belongs to the upper triangular U11 and stops at row j; it is written as row j of Ut11 (l1 x l1, ld l1: U11', what
+// lr_solve_c_kernel reads).  A column j >= l1 is a column of U12 (l1 x (l - l1), ld l1), written as it stands.
+template <int NC>
+__global__ __launch_bounds__(64) void lr_solve_u12_kernel(const double* __restrict__ L, int64_t ldl, const double* __restrict__ Mp,
+                                                          int l1, int l, double c, double* __restrict__ Ut11,
+                                                          double* __restrict__ U12) {
+  __shared__ double xs[NC][LRP_MAXL];
+  const int lane = threadIdx.x, col0 = blockIdx.x * NC;
+  const int m = (col0 + NC < l1) ? col0 + NC : l1;
+  double v[NC][LRP_MAXL / 64];
+#pragma unroll
+  for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+    for (int ib = 0; ib < LRP_MAXL / 64; ++ib) {
+      const int i = ib * 64 + lane;
+      v[cc][ib] = (i < m && col0 + cc < l) ? Mp[i + (int64_t)(col0 + cc) * l1] : 0.0;
+    }
+  __builtin_amdgcn_sched_barrier(0);                    // (the loads together, then the stores to LDS)
+#pragma unroll
+  for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+    for (int ib = 0; ib < LRP_MAXL / 64; ++ib) xs[cc][ib * 64 + lane] = v[cc][ib];
+  __syncthreads();
+  lrp_lower_solve<NC, true>(L, ldl, m, xs, lane);
+  for (int cc = 0; cc < NC; ++cc) {
+    const int col = col0 + cc;
+    if (col >= l) break;
+    if (col < l1) {
+      for (int i = lane; i <= col; i += 64) Ut11[col + (int64_t)i * l1] = c * xs[cc][i];
+    } else {
+      for (int i = lane; i < l1; i += 64) U12[i + (int64_t)(col - l1) * l1] = c * xs[cc][i];
+    }
+  }
+}
+
+void lr_solve_u12(hipStream_t st, const double* L, int64_t ldl, const double* Mp, int64_t l1, int64_t l, double c, double* Ut11,
+                  double* U12) {
+  hipLaunchKernelGGL(lr_solve_u12_kernel<LRP_NC_U>, dim3((unsigned)((l + LRP_NC_U - 1) / LRP_NC_U)), dim3(64), 0, st, L, ldl, Mp,
+                     (int)l1, (int)l, c, Ut11, U12);
+}
+
+// The interchanges of one half applied to nc columns of the other, X (ld ldx): X[sub[k]] <- X[src[k]] for the moved rows
+// k < nmv = verdict[2] of lr_compose (src[k] = perm(sub[k]); at most maxmv).  Every moved row is read into tmp (ld ldt) before
+// any is written -- two launches --, so the order among them does not matter and no column waits for a chain of exchanges.
+// The second launch also writes zeros to the rows [0, nzero): the block above the right half's Schur complement.
+__global__ __launch_bounds__(256) void lr_rows_out_kernel(const double* __restrict__ X, int64_t ldx, int nc,
+                                                          const int64_t* __restrict__ src, const int32_t* __restrict__ verdict,
+                                                          int maxmv, double* __restrict__ tmp, int64_t ldt) {
+  const int nmv = verdict[2] < maxmv ? verdict[2] : maxmv;
+  const int64_t total = (int64_t)nmv * nc;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = e % nmv, c = e / nmv;
+    tmp[k + c * ldt] = X[src[k] + c * ldx];
+  }
+}
+__global__ __launch_bounds__(256) void lr_rows_in_kernel(double* __restrict__ X, int64_t ldx, int nc,
+                                                         const int64_t* __restrict__ sub, const int32_t* __restrict__ verdict,
+                                                         int maxmv, const double* __restrict__ tmp, int64_t ldt, int nzero) {
+  const int nmv = verdict[2] < maxmv ? verdict[2] : maxmv;
+  const int64_t rows = (int64_t)nmv + nzero, total = rows * nc;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = e % rows, c = e / rows;
+    if (k < nmv) {
+      const int64_t r = sub[k];
+      X[r + c * ldx] = r < nzero ? 0.0 : tmp[k + c * ldt];      // (a row both branches reach gets the same zero from both)
+    } else {
+      X[(k - nmv) + c * ldx] = 0.0;
+    }
+  }
+}
+
+void lr_move_rows(hipStream_t st, double* X, int64_t ldx, int64_t nc, const int64_t* src, const int64_t* sub,
+                  const int32_t* verdict, int64_t maxmv, double* tmp, int64_t ldt, int64_t nzero) {
+  if (nc < 1 || maxmv < 1) return;
+  const unsigned g_out = (unsigned)((maxmv * nc + 255) / 256), g_in = (unsigned)(((maxmv + nzero) * nc + 255) / 256);
+  hipLaunchKernelGGL(lr_rows_out_kernel, dim3(g_out), dim3(256), 0, st, X, ldx, (int)nc, src, verdict, (int)maxmv, tmp, ldt);
+  hipLaunchKernelGGL(lr_rows_in_kernel, dim3(g_in), dim3(256), 0, st, X, ldx, (int)nc, sub, verdict, (int)maxmv, tmp, ldt,
+                     (int)nzero);
+}
+
+// dst[j] <- piv[j] + add, j < cnt: the first half's interchanges kept while the second factorization reuses the workspace they
+// lie in, then the second half's appended in the whole panel's row numbers
+__global__ __launch_bounds__(256) void lr_pivots_kernel(const int32_t* __restrict__ piv, int cnt, int32_t add,
+                                                        int32_t* __restrict__ dst) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < cnt) dst[j] = piv[j] + add;
+}
+void lr_pivots(hipStream_t st, const int32_t* piv, int64_t cnt, int64_t add, int32_t* dst) {
+  hipLaunchKernelGGL(lr_pivots_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, piv, (int)cnt, (int32_t)add, dst);
+}
+
+// A zero pivot that a half's factorization flagged (info = its column + 1) is forgotten: the panel is factored again whole,
+// and that factorization reports its own.  A lost exchange (info < 0) stays.
+__global__ void lr_forget_zero_pivot_kernel(int32_t* __restrict__ info) {
+  if (info[0] > 0) info[0] = 0;
+}
+void lr_forget_zero_pivot(hipStream_t st, int32_t* info) {
+  hipLaunchKernelGGL(lr_forget_zero_pivot_kernel, dim3(1), dim3(1), 0, st, info);
+}
+
 }}  // namespace gsi::hipk

@@ -863,6 +863,42 @@ static bool lowrank_tail_applies(const Operator& A, int64_t l) {
   return !off && A.kind == OP_LOWRANK && !A.ctx->comm && A.m == A.n && A.mloc == A.m && A.N <= 4096 && l <= A.N - 1;
 }
 
+// One panel of randsvd_lowrank_single factored as two column halves, split at l1: P (n x l, ld n)
+// <- L of lu(S (c T)) and *ipiv its interchanges, as lu_L_keep of the whole panel leaves them up to rounding.  The right
+// half's update by the left half's L is a change of its N x (l - l1) coefficients (Backend::lowrank_split_schur), so no block
+// of the factorization reads the left half again.  One panel stays one entry of PH_GEMM_N and PH_LU: the second product and the
+// second factorization add their time to them, and the sample-space work goes to PH_OTHER, whose entry the power step counts.
+static void lowrank_lu_halves(const Operator& A, const double* T, int64_t l, int64_t l1, double* P, double* Tt, int32_t** ipiv) {
+  Backend* be = A.ctx->be.get();
+  const int64_t n = A.n, l2 = l - l1;
+  int32_t* half = nullptr;
+  lowrank_ScT(A, T, l1, P, n);
+  {
+    ScopedPhase ph(be, PH_LU);
+    if (!be->lu_L_keep(P, n, l1, n, &half)) throw Error(GSI_ERR_ARG, "randsvd: lowrank_split_ok without lu_L_keep");
+  }
+  {
+    ScopedPhaseMore ph(be, PH_OTHER);
+    be->lowrank_split_schur(A.data.p, A.ld, n, A.N, T, half, P, n, l, l1, 1.0 / (double)(A.N - 1), Tt);
+  }
+  {
+    ScopedPhaseMore ph(be, PH_GEMM_N);
+    be->gemm_nn(n, l2, A.N, 1.0, A.data.p, A.ld, Tt, A.N, 0.0, P + l1 * n, n);
+  }
+  {
+    ScopedPhaseMore ph(be, PH_OTHER);
+    be->lowrank_split_rows(P, n, n, l, l1);
+  }
+  {
+    ScopedPhaseMore ph(be, PH_LU);
+    if (!be->lu_L_keep(P + l1 + l1 * n, n - l1, l2, n, &half)) throw Error(GSI_ERR_ARG, "randsvd: lowrank_split_ok without lu_L_keep");
+  }
+  {
+    ScopedPhaseMore ph(be, PH_OTHER);
+    be->lowrank_split_join(P, n, n, l, l1, half, ipiv);
+  }
+}
+
 // randsvd of a LowRankCovMatrix on one rank (lowrank_tail_applies).  Every panel the range finder factors is P = S (c T) with
 // T (N x l) = S'X of the panel X before it, so T is what goes from step to step:
 //   T = S'Omega;   2q times:  P = S (c T), L = lu(P).L, T = S'L;   finish from T.
@@ -870,35 +906,69 @@ static bool lowrank_tail_applies(const Operator& A, int64_t l) {
 // the finish runs in the coordinates of range(S) (Backend::lowrank_tail, section 4.10).  Where a power step declines, S'L is
 // the product from the L in memory, for this panel and the rest of the call (GSI_NO_LOWRANK_POWER=1: for all of them; a
 // decline at the first LU gives the bits of that leg); where the tail declines, Y = S (c T) and the ordinary deferred-Q
-// ending follow.  Both are the products and factorizations the general range finder runs, bit for bit.
+// ending follow.  Both are the products and factorizations the general range finder runs, bit for bit.  While the power steps
+// run, a panel of 160 < l <= 320 columns is factored as two halves (lowrank_lu_halves; GSI_NO_LOWRANK_SPLIT=1: whole);
+// one that the power step then declines is formed and factored again whole before anything else reads it.
 static void randsvd_lowrank_single(const Operator& A, const double* Omega, int64_t K, int64_t l, int64_t q, double* Z, double* S) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
   check_rangefinder_args(A, l, q);
   static const bool power_off = (getenv("GSI_NO_LOWRANK_POWER") != nullptr);
+  static const bool split_off = (getenv("GSI_NO_LOWRANK_SPLIT") != nullptr);
   bool power = !power_off && q > 0;                         // power steps still on
   const int64_t n = A.n;
   const double cN = 1.0 / (double)(A.N - 1);
-  Buf T(be, (size_t)A.N * l), Tn, P;                        // P: the one n x l panel, each S (c T) overwrites the L before
+  // the panels in two halves (section 4.12), split at the column-chunk boundary of the contraction kernel: both half products
+  // are whole chunks.  Off where the backend declines, and for the rest of the call once a power step declined such a panel.
+  constexpr int64_t SPLIT_L1 = 160;
+  bool split = power && !split_off && be->lowrank_split_ok(n, A.N, l, SPLIT_L1);
+  Buf T(be, (size_t)A.N * l), Tn, Tt, P;                    // P: the one n x l panel, each S (c T) overwrites the L before
   if (power) Tn = Buf(be, (size_t)A.N * l);
+  if (split) Tt = Buf(be, (size_t)A.N * (l - SPLIT_L1));
   int32_t* ipiv = nullptr;                                  // the pivots lu_L_keep left in backend workspace
   lowrank_StX(A, Omega, n, l, T.p);                         // Y = A*Omega            :55
   for (int64_t step = 0; step < 2 * q; ++step) {            // :60-61, then :67-69 and :70-73 per iteration
     if (P.p == nullptr) P = Buf(be, (size_t)n * l);
-    lowrank_ScT(A, T.p, l, P.p, n);
-    if (power) {
-      ScopedPhase ph(be, PH_LU);
-      power = be->lu_L_keep(P.p, n, l, n, &ipiv);           // (false: not available, nothing ran)
+    const bool halves = power && split;
+    if (halves) {
+      lowrank_lu_halves(A, T.p, l, SPLIT_L1, P.p, Tt.p, &ipiv);
+    } else {
+      lowrank_ScT(A, T.p, l, P.p, n);
+      if (power) {
+        ScopedPhase ph(be, PH_LU);
+        power = be->lu_L_keep(P.p, n, l, n, &ipiv);         // (false: not available, nothing ran)
+      }
+      if (!power) lu_panel(c, P.p, n, l);
     }
-    if (!power) lu_panel(c, P.p, n, l);
     if (power) {                                            // T <- S'L in sample space
       const double* G = sample_gram(A);                     // (made at the operator's first power step)
       power = false;
       if (G != nullptr) {
         ScopedPhase ph(be, PH_OTHER);                       // (not PH_GEMM_T / _N: bench.py's roofline counts those as tall products)
         power = be->lowrank_power_step(A.data.p, A.ld, A.mloc, A.N, G, T.p, ipiv, P.p, n, l, cN, Tn.p);
-        if (!power) c.lowrank_power_declines += 1;
       }
+      if (halves && power) c.lowrank_split_lus += 1;
+      if (halves && !power) {                               // declined: the same panel again, whole (T is still held)
+        c.lowrank_split_declines += 1;
+        split = false;
+        Tt.reset();
+        be->lowrank_split_undo();
+        {
+          ScopedPhaseMore ph(be, PH_GEMM_N);
+          be->gemm_nn(n, l, A.N, cN, A.data.p, A.ld, T.p, A.N, 0.0, P.p, n);
+        }
+        bool whole;
+        {
+          ScopedPhaseMore ph(be, PH_LU);
+          whole = be->lu_L_keep(P.p, n, l, n, &ipiv);
+        }
+        if (!whole) throw Error(GSI_ERR_ARG, "randsvd: lowrank_split_ok without lu_L_keep");
+        if (G != nullptr) {
+          ScopedPhaseMore ph(be, PH_OTHER);
+          power = be->lowrank_power_step(A.data.p, A.ld, A.mloc, A.N, G, T.p, ipiv, P.p, n, l, cN, Tn.p);
+        }
+      }
+      if (!power && G != nullptr) c.lowrank_power_declines += 1;
     }
     if (power) {
       std::swap(T, Tn);

@@ -48,6 +48,8 @@ struct Context {
   int64_t lowrank_tails = 0;           // randsvd steps of a LowRankCovMatrix that ran their tail in sample space (randsvd_lowrank_single)
   int64_t lowrank_power_steps = 0;     // power steps S'L formed in sample space (randsvd_lowrank_single)
   int64_t lowrank_power_declines = 0;  // ... and the ones the backend declined (that call took the direct path from there on)
+  int64_t lowrank_split_lus = 0;       // panels of those power steps factored as two column halves
+  int64_t lowrank_split_declines = 0;  // ... and the ones whose power step declined them (factored again whole; off for the rest of that call)
   int rank() const { return comm ? comm->rank : 0; }
   int nranks() const { return comm ? comm->nranks : 1; }
 };
