@@ -94,8 +94,9 @@ class Context:
         form since the last phase_reset), the self-test mask of the in-kernel pivot exchange, collectives entered since the
         last phase_reset, the ranks the communicator joined, LU time-outs seen / hidden by a transparent re-run; randsvd calls that
         finished in the sample space of a LowRankCovMatrix, range-finder power steps formed there and the ones declined, panels
-        of those steps factored as two column halves and the ones factored again whole."""
-        n = 18
+        of those steps factored as two column halves and the ones factored again whole; sample-space tails that formed part of
+        Z beside the small SVD."""
+        n = 19
         out = (C.c_int64 * n)()
         L.check(self.lib.gsi_ctx_path_info(self.h, out, n), self.lib)
         forms = {self.LU_FORMS[f]: int(out[6 + f]) for f in range(1, 6) if out[6 + f]}
@@ -103,7 +104,8 @@ class Context:
                 "lu_selftest_mask": int(out[1]), "collectives": int(out[2]), "n_ranks_seen": int(out[3]),
                 "lu_timeouts": int(out[4]), "lu_timeouts_recovered": int(out[5]), "svd_sweep_cap_hits": int(out[12]),
                 "lowrank_tails": int(out[13]), "lowrank_power_steps": int(out[14]), "lowrank_power_declines": int(out[15]),
-                "lowrank_split_lus": int(out[16]), "lowrank_split_declines": int(out[17])}
+                "lowrank_split_lus": int(out[16]), "lowrank_split_declines": int(out[17]),
+                "lowrank_tail_overlaps": int(out[18])}
 
     def release_cache(self):
         """Return cached device memory (released panels, idle workspaces) to the driver (`gsi_ctx_release_cache`)."""

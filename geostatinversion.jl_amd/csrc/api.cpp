@@ -201,6 +201,7 @@ int gsi_ctx_path_info(gsi_ctx* ctx, int64_t* out, int64_t n_out) {
     v[GSI_PATH_LOWRANK_POWER_DECLINES] = c.lowrank_power_declines;
     v[GSI_PATH_LOWRANK_SPLIT_LUS] = c.lowrank_split_lus;
     v[GSI_PATH_LOWRANK_SPLIT_DECLINES] = c.lowrank_split_declines;
+    v[GSI_PATH_LOWRANK_TAIL_OVERLAPS] = c.be->lowrank_tail_overlaps();
     for (int64_t i = 0; i < n_out; ++i) out[i] = i < GSI_PATH_INFO_COUNT ? v[i] : 0;
   });
 }

@@ -217,11 +217,17 @@ class Backend {
   // columns zero, and Sv (l) the singular values.  false (declines, Z and Sv untouched): a Cholesky broke down, a second
   // round's Gram matrix was not near the identity, l > N - 1 (centred samples span N - 1 dimensions), or a shape it does not
   // cover; pipeline.cpp:randsvd_lowrank_single then forms Y = S (c T) and runs the ordinary deferred-Q ending.
+  // scratch (optional, scratch_doubles doubles): a dead panel of the caller's that the backend may overwrite instead of taking
+  // a temporary of its own (the rows of S B1 formed beside the small SVD; contents undefined on return, whatever the verdict).
   virtual bool lowrank_tail(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
-                            int64_t K, double c, double* Z, int64_t ldz, double* Sv) {
+                            int64_t K, double c, double* Z, int64_t ldz, double* Sv, double* scratch = nullptr,
+                            size_t scratch_doubles = 0) {
     (void)S; (void)lds; (void)n; (void)N; (void)G; (void)T; (void)l; (void)K; (void)c; (void)Z; (void)ldz; (void)Sv;
+    (void)scratch; (void)scratch_doubles;
     return false;
   }
+  // calls of lowrank_tail that formed part of Z beside the small SVD
+  virtual int64_t lowrank_tail_overlaps() { return 0; }
   // One power step of the range finder in sample space.  The panel Y = c S T (T: N x l, ld N) was
   // factored by lu_L_keep into ipiv and L (n x l, ld ldl): P Y = L U, so L = (P S) C with C = c T U^-1, where
   // U = L11^-1 (P Y)[0:l] comes from the pivot rows, and

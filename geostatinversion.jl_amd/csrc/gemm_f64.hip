@@ -127,10 +127,15 @@ size_t gemm_syrk_workspace_doubles(int64_t l, int64_t m) {
 // through the irregular-X instantiation: 6.3 vs 5.3 ms.)
 static int gemm_chunk_tiles(int) { return NTMAX; }
 
-static void gemm_launch(hipStream_t st, bool transA, const GenA* gen, int64_t M, int64_t L, int64_t K, double alpha,
+// max_grid > 0 (a multiple of 8): a launch that shares the chip with another stream's work.  Persistent mode then runs on
+// min(CUs, max_grid) workgroups (one fills a CU's LDS, so the other CUs stay free for the neighbour); where persistent mode does
+// not apply, the launch goes ahead only if its plain grid already fits under the cap.  false: not applicable, nothing launched.
+// query_only: the verdict (and the plan) without the launch.
+static bool gemm_launch(hipStream_t st, bool transA, const GenA* gen, int64_t M, int64_t L, int64_t K, double alpha,
                         const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
-                        int64_t ldc, double* ws, int tri = 0, int gen_mode = 1, int force_nsplit = 0, GemmPlan* plan = nullptr) {
-  if (M <= 0 || L <= 0) return;
+                        int64_t ldc, double* ws, int tri = 0, int gen_mode = 1, int force_nsplit = 0, GemmPlan* plan = nullptr,
+                        int max_grid = 0, bool query_only = false) {
+  if (M <= 0 || L <= 0) return max_grid <= 0;
   // The kernel addresses a tile with one uniform 64-bit base per operand plus per-thread byte offsets spanning up to
   // 160 columns of B, 128 rows of a transposed A or 32 columns of a plain A: 32 bits reach panels of ~3.3 million
   // rows; beyond that the 64-bit-offset instantiation (XMODE 2) takes over.
@@ -173,9 +178,11 @@ static void gemm_launch(hipStream_t st, bool transA, const GenA* gen, int64_t M,
   if (persist_on && gen == nullptr && xmode == 0 && tri == 0 && ns_eff == 1 && (ncus & 7) == 0 && active >= 2 * (int64_t)ncus &&
       K <= 128 * BK) {
     nitems = active;
-    grid.x = (unsigned)ncus;
+    grid.x = (unsigned)((max_grid > 0 && max_grid < ncus) ? max_grid : ncus);
   }
+  if (max_grid > 0 && nitems == 0 && ((int64_t)grid.x * (int64_t)grid.y > (int64_t)max_grid || ns_eff != 1)) return false;
   if (plan != nullptr) *plan = {nt, nchunks, xmode, wide, ns_eff, nitems > 0 ? 1 : 0, (int64_t)grid.x, active};
+  if (query_only) return true;
   const GenA none = {nullptr, 1, 0, 0, 0, 0.0, 0.0, 0.0};
   if (gen != nullptr && gen_mode == 2)
     launch_dispatch<false, 2>(nt, grid, st, M, L, K, A, lda, B, ldb, C, ldc, alpha, beta, slabs, kchunk, (int)nchunks, wide, xmode, tri, *gen, nitems);
@@ -192,6 +199,7 @@ static void gemm_launch(hipStream_t st, bool transA, const GenA* gen, int64_t M,
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, M, L, ns_eff, slabs, C, ldc,
                        alpha, beta);
   }
+  return true;
 }
 
 void gemm_splitk_reduce(hipStream_t st, int64_t M, int64_t L, int nsplit, const double* slabs, double* C, int64_t ldc) {
@@ -205,6 +213,14 @@ void gemm_splitk_reduce(hipStream_t st, int64_t M, int64_t L, int nsplit, const 
 void gemm_f64(hipStream_t st, bool transA, int64_t M, int64_t L, int64_t K, double alpha, const double* A,
               int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* ws, GemmPlan* plan) {
   gemm_launch(st, transA, nullptr, M, L, K, alpha, A, lda, B, ldb, beta, C, ldc, ws, 0, 1, 0, plan);
+}
+
+// The NN product under a grid cap (gemm_launch: max_grid), always with ONE K split: it never touches the split-K workspace,
+// which the uncapped products of another stream may be using at the same time.  false: not applicable, nothing launched.
+bool gemm_f64_nn_capped(hipStream_t st, int64_t M, int64_t L, int64_t K, const double* A, int64_t lda, const double* B,
+                        int64_t ldb, double* C, int64_t ldc, int max_grid, bool query_only, GemmPlan* plan) {
+  if (max_grid < 8 || (max_grid & 7) != 0) return false;
+  return gemm_launch(st, false, nullptr, M, L, K, 1.0, A, lda, B, ldb, 0.0, C, ldc, nullptr, 0, 1, 1, plan, max_grid, query_only);
 }
 
 // The K split gemm_f64 (NN or TN, plain operands) uses for an M x L x K product, and rows [r0, r0 + mb) of that product

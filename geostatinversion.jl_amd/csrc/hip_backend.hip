@@ -88,6 +88,7 @@ class HipBackend : public Backend {
   ~HipBackend() override {
     hipSetDevice(device_);
     hipStreamSynchronize(st_);
+    drain_side();
     stager_.reset();
     if (ev_stage_) hipEventDestroy(ev_stage_);
     for (auto& b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_}) free_ws(*b);
@@ -99,6 +100,9 @@ class HipBackend : public Backend {
     hipFree(scal_);
     if (pin_power_) hipHostFree(pin_power_);
     if (mr_recs_) hipFree(mr_recs_);
+    if (ev_fork_) hipEventDestroy(ev_fork_);
+    if (ev_join_) hipEventDestroy(ev_join_);
+    if (st2_) hipStreamDestroy(st2_);
     hipStreamDestroy(st_);
   }
   const char* name() const override { return "hip-gfx950"; }
@@ -169,6 +173,7 @@ class HipBackend : public Backend {
     }
     if (p) {
       hipStreamSynchronize(st_);
+      drain_side();
       hipFree(p);
     }
     // Panels of the tall problems are GBs each and come back every pass: keep up to 160 GB of them (of 288 GB; a
@@ -181,6 +186,7 @@ class HipBackend : public Backend {
   }
   void trim_pool(int64_t keep_bytes) {
     hipStreamSynchronize(st_);
+    drain_side();
     std::lock_guard<std::mutex> g(mu_);
     while (!pool_.empty() && pooled_ > keep_bytes) {
       hipFree(pool_.back().p);
@@ -193,6 +199,7 @@ class HipBackend : public Backend {
     for (DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_})
       if (b->bytes > ((size_t)64 << 20)) free_ws(*b);
     (void)hipStreamSynchronize(st_);
+    drain_side();
     collect_garbage();
     trim_pool(0);
   }
@@ -345,6 +352,7 @@ class HipBackend : public Backend {
   void sync() override {
     bind();
     HIP_CHECK(hipStreamSynchronize(st_));
+    if (st2_) HIP_CHECK(hipStreamSynchronize(st2_));
   }
 
   // ---- products ----
@@ -1065,13 +1073,45 @@ class HipBackend : public Backend {
   // -- the operations of qr_thinQ_deferred + op_mul_t + svd_tall_fused with the tall products replaced by N x l ones; one tall
   // product (Z, K = N) is left.  Each Gram matrix is the exact one of its panel up to eps |M|^2 |G| (against eps |S M|^2 when
   // the panel is formed): the second rounds' check catches a panel whose coefficients grew too large for that to hold.
+  //
+  // The overlap.  Between the last Gram round and M = (XW2 U sqrt(S))[:, 0:K] lies a chain of small dependent launches (the
+  // Cholesky, the Jacobi sweeps) on a few workgroups, and behind it the one tall product.  C = B1 M, and B1 is known before the
+  // chain: Y_f = S[0:n_f] B1 (n_f x l) is formed on the side stream while the chain runs, on all but TAIL_RESERVE_CUS CUs
+  // (hipk::gemm_f64_nn_capped), and those rows of Z then cost a reduction of length l instead of N: Z[0:n_f] = Y_f M.  The rows
+  // from n_f on are the row block of today's product (the same tiles in the same order: the same bits).  n_f is a multiple of
+  // the contraction's row tile fixed by (n, the fraction), so repeated calls give the same bits.  Y_f goes into `scratch` (the
+  // caller's dead panel) or a pooled temporary.  On by default where the capped product runs persistent;
+  // GSI_LOWRANK_TAIL_OVERLAP=0 switches it off, =<fraction in (0, 1)> forces that row fraction on any shape the capped
+  // launch takes.
+  // Both constants were measured at the headline: with 8 or 16 CUs left free the first kernel behind the
+  // fork waited for the whole side product; 0.40 n rows at 224 CUs end just before M is ready (0.34 and 0.46 were slower).
+  static constexpr double TAIL_OVERLAP_FRACTION = 0.40;
+  static constexpr int TAIL_RESERVE_CUS = 32;
   bool lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
-                    int64_t K, double c, double* Z, int64_t ldz, double* Sv) override {
+                    int64_t K, double c, double* Z, int64_t ldz, double* Sv, double* scratch, size_t scratch_doubles) override {
     bind();
     static const bool off = (getenv("GSI_NO_CHOLQR") != nullptr);
     if (off || l < 1 || l > 384 || l > N - 1 || K < 1 || K > l || N > 4096 || n < 2 * l) return false;
+    // < 0: the default gate; 0: off; in (0, 1): forced
+    static const double ov_env = [] {
+      const char* e = getenv("GSI_LOWRANK_TAIL_OVERLAP");
+      if (e == nullptr || e[0] == 0) return -1.0;
+      const double v = atof(e);
+      return (v > 0.0 && v < 1.0) ? v : 0.0;
+    }();
+    static const int reserve = [] {                          // experiments: the CUs left to the main stream
+      const char* e = getenv("GSI_LOWRANK_TAIL_RESERVE_CUS");
+      const int v = e ? atoi(e) : TAIL_RESERVE_CUS;
+      return (v >= 8 && (v & 7) == 0) ? v : TAIL_RESERVE_CUS;
+    }();
     const size_t Nl = ((size_t)N * l + 7) & ~(size_t)7, ll = ((size_t)l * l + 7) & ~(size_t)7;
     Scratch buf(this, 3 * Nl + 12 * ll);
+    const int cap = std::max(8, ((ncus_ - reserve) / 8) * 8);
+    int64_t nf = 0;
+    if (ov_env != 0.0) {
+      nf = (int64_t)((ov_env > 0.0 ? ov_env : TAIL_OVERLAP_FRACTION) * (double)n) / 128 * 128;
+      if (nf >= n) nf = (n - 1) / 128 * 128;
+    }
     double* A0 = buf.p;                 // c T; then B0; then C
     double* A1 = A0 + Nl;               // A0 X1; then B1
     double* P = A1 + Nl;                // G times the current coefficients
@@ -1089,7 +1129,19 @@ class HipBackend : public Backend {
     gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, l));
     gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, K, l));
     gmax = std::max(gmax, hipk::gemm_workspace_doubles(n, K, N));
+    if (nf >= 128) {
+      // (the capped launch reads its operands' alignment: A1 is where B1 will be)
+      hipk::GemmPlan plan = {0, 0, 0, 0, 0, 0, 0, 0};
+      const bool takes = hipk::gemm_f64_nn_capped(st_, nf, l, N, Sm, lds, A1, N, A1, nf, cap, true, &plan);
+      if (!takes || (ov_env < 0.0 && plan.persistent == 0)) nf = 0;
+    } else {
+      nf = 0;
+    }
+    Scratch own(this, (nf > 0 && (scratch == nullptr || scratch_doubles < (size_t)nf * (size_t)l)) ? (size_t)nf * (size_t)l : 0);
+    double* Yf = (nf > 0) ? (own.p != nullptr ? own.p : scratch) : nullptr;      // nf x l, ld nf
+    if (nf > 0) gmax = std::max(gmax, hipk::gemm_workspace_doubles(nf, K, l));
     double* ws = gemm_ws(gmax + 64);
+    SideJoin side(this);                                    // (after every buffer the side stream touches: joined before they go)
     // one round on the panel S M: P = G M, Gram = M'P, R = chol(Gram) in place, X = R^-1
     auto round = [&](const double* M, int i, bool check) {
       hipk::gemm_f64(st_, false, N, l, N, 1.0, G, N, M, N, 0.0, P, N, ws);
@@ -1108,9 +1160,15 @@ class HipBackend : public Backend {
     hipk::gemm_f64(st_, false, N, l, l, 1.0, A0, N, X[2], l, 0.0, A1, N, ws);               // W RW1^-1 = S B1
     round(A1, 3, true);
     check_launch("lowrank_tail");
+    if (nf > 0) {
+      side.fork();
+      (void)hipk::gemm_f64_nn_capped(st2_, nf, l, N, Sm, lds, A1, N, Yf, nf, cap);        // Y_f = S[0:n_f] B1
+      check_launch("lowrank_tail (side product)");
+    }
     HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     if (f != 0) {
+      side.join();
       phase_end(PH_QR);
       return false;                                         // nothing of Z or Sv written: the caller's path takes over
     }
@@ -1125,7 +1183,14 @@ class HipBackend : public Backend {
     phase_begin(PH_SMALL_GEMM);
     hipk::gemm_f64(st_, false, l, K, l, 1.0, X[3], l, U, l, 0.0, Mm, l, ws);                // XW2 U sqrt(S), first K columns
     hipk::gemm_f64(st_, false, N, K, l, 1.0, A1, N, Mm, l, 0.0, A0, N, ws);                 // C = B1 (XW2 U sqrt(S))
-    hipk::gemm_f64(st_, false, n, K, N, 1.0, Sm, lds, A0, N, 0.0, Z, ldz, ws);              // Z = S C
+    if (nf > 0) {
+      side.join();
+      hipk::gemm_f64(st_, false, nf, K, l, 1.0, Yf, nf, Mm, l, 0.0, Z, ldz, ws);            // Z[0:n_f] = Y_f M
+      hipk::gemm_f64_nn_rowblock(st_, n, nf, n - nf, K, N, Sm, lds, A0, N, Z, ldz, ws);     // Z[n_f:n] = S[n_f:n] C
+      ++n_tail_overlaps_;
+    } else {
+      hipk::gemm_f64(st_, false, n, K, N, 1.0, Sm, lds, A0, N, 0.0, Z, ldz, ws);            // Z = S C
+    }
     // the last l - K columns of Z are zero by definition (RandMatFact.jl:87)
     if (K < l) HIP_CHECK(hipMemsetAsync(Z + (size_t)K * ldz, 0, sizeof(double) * ((size_t)(l - K - 1) * ldz + n), st_));
     check_launch("lowrank_tail");
@@ -1477,6 +1542,7 @@ class HipBackend : public Backend {
     int32_t h[16];
     HIP_CHECK(hipMemcpyAsync(h, flags_, sizeof(h), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
+    if (st2_) HIP_CHECK(hipStreamSynchronize(st2_));   // (idle unless a call ended in an exception between fork and join)
     HIP_CHECK(hipGetLastError());
     if (!garbage_.empty()) collect_garbage();
     if (h[0] >= 0) mr_in_flight_ = false;
@@ -1558,6 +1624,7 @@ class HipBackend : public Backend {
   }
   int64_t lu_timeouts() override { return n_lu_timeouts_; }
   int64_t svd_cap_hits() override { return n_svd_cap_hits_; }
+  int64_t lowrank_tail_overlaps() override { return n_tail_overlaps_; }
   void set_ranks_sharing_device(int n) override { ranks_sharing_device_ = n; }
   int device() const { return device_; }
 
@@ -1619,6 +1686,7 @@ class HipBackend : public Backend {
     if (e != hipSuccess) {   // give the cache of released panels back and retry once (the other phases' workspaces may be
       (void)hipGetLastError();   // in use by the caller: they stay)
       (void)hipStreamSynchronize(st_);
+      drain_side();
       collect_garbage();
       trim_pool(0);
       e = hipMalloc(&b.p, bytes);
@@ -1630,6 +1698,47 @@ class HipBackend : public Backend {
     }
     b.bytes = bytes;
   }
+  void drain_side() { if (st2_) (void)hipStreamSynchronize(st2_); }
+  hipStream_t side_stream() {
+    if (st2_ != nullptr) return st2_;
+    int least = 0, greatest = 0;                  // (numerically larger = lower priority; st_ has the default, 0)
+    HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    hipStream_t s = nullptr;
+    HIP_CHECK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least));
+    hipEvent_t a = nullptr, b = nullptr;
+    if (hipEventCreateWithFlags(&a, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess) {
+      if (a) hipEventDestroy(a);
+      hipStreamDestroy(s);
+      throw Error(GSI_ERR_HIP, "lowrank_tail: the side stream's events could not be created");
+    }
+    st2_ = s; ev_fork_ = a; ev_join_ = b;
+    return st2_;
+  }
+  // Joins the side stream into st_ on every way out of the scope that forked it.  join(): the ordinary way (st_ waits for what
+  // the side stream was given; the host does not).  Left to the destructor -- an exception is in flight -- the host waits too.
+  struct SideJoin {
+    HipBackend* be; bool open = false;
+    explicit SideJoin(HipBackend* b) : be(b) {}
+    void fork() {
+      hipStream_t s2 = be->side_stream();
+      HIP_CHECK(hipEventRecord(be->ev_fork_, be->st_));
+      HIP_CHECK(hipStreamWaitEvent(s2, be->ev_fork_, 0));
+      open = true;
+    }
+    void join() {
+      if (!open) return;
+      open = false;
+      HIP_CHECK(hipEventRecord(be->ev_join_, be->st2_));
+      HIP_CHECK(hipStreamWaitEvent(be->st_, be->ev_join_, 0));
+    }
+    ~SideJoin() {
+      if (!open) return;
+      if (hipEventRecord(be->ev_join_, be->st2_) == hipSuccess) (void)hipStreamWaitEvent(be->st_, be->ev_join_, 0);
+      (void)hipStreamSynchronize(be->st2_);
+    }
+    SideJoin(const SideJoin&) = delete;
+    SideJoin& operator=(const SideJoin&) = delete;
+  };
   double* gemm_ws(size_t doubles) {
     if (doubles == 0) return (double*)ws_gemm_.p;
     grow(ws_gemm_, doubles * sizeof(double));
@@ -1640,6 +1749,12 @@ class HipBackend : public Backend {
   int ncus_ = 0;
   std::string arch_;
   hipStream_t st_ = nullptr;
+  // the side stream of lowrank_tail's overlap (created at its first use, lower priority than st_) and the two events that
+  // order it against st_: work is put on it only between a fork and a join inside one call, so whatever drains st_ after
+  // that call has drained it too; the places that drain or tear down st_ drain it all the same (drain_side)
+  hipStream_t st2_ = nullptr;
+  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
+  int64_t n_tail_overlaps_ = 0;
   std::unique_ptr<HostStager> stager_;        // the pinned staging ring of the host boundary (created at the first large transfer)
   bool stager_failed_ = false;
   hipEvent_t ev_stage_ = nullptr;

@@ -27,6 +27,11 @@ size_t gemm_workspace_doubles(int64_t M, int64_t L, int64_t K);
 void gemm_f64(hipStream_t st, bool transA, int64_t M, int64_t L, int64_t K, double alpha, const double* A,
               int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* ws,
               GemmPlan* plan = nullptr);
+// C = A * B on at most max_grid (a multiple of 8) workgroups and with one K split (no workspace): the persistent mode on
+// min(CUs, max_grid) workgroups, or a plain grid that already fits.  false: not applicable, nothing launched; query_only: the
+// verdict and the plan without the launch.
+bool gemm_f64_nn_capped(hipStream_t st, int64_t M, int64_t L, int64_t K, const double* A, int64_t lda, const double* B,
+                        int64_t ldb, double* C, int64_t ldc, int max_grid, bool query_only = false, GemmPlan* plan = nullptr);
 // rows [r0, r0 + mb) of the NN product of an M_full-row launch, with that launch's K split (bit-identical blocks)
 size_t gemm_rowblock_workspace_doubles(int64_t M_full, int64_t mb, int64_t L, int64_t K);
 void gemm_f64_nn_rowblock(hipStream_t st, int64_t M_full, int64_t r0, int64_t mb, int64_t L, int64_t K, const double* A,

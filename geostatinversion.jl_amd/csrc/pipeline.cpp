@@ -980,7 +980,8 @@ static void randsvd_lowrank_single(const Operator& A, const double* Omega, int64
   }
   Tn.reset();
   const double* G = sample_gram(A);
-  if (G != nullptr && be->lowrank_tail(A.data.p, A.ld, n, A.N, G, T.p, l, K, cN, Z, n, S)) {
+  // (P: L is dead after the last power step, the tail may write over it)
+  if (G != nullptr && be->lowrank_tail(A.data.p, A.ld, n, A.N, G, T.p, l, K, cN, Z, n, S, P.p, P.p != nullptr ? (size_t)n * l : 0)) {
     c.lowrank_tails += 1;
     return;
   }
