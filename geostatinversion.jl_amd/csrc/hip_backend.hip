@@ -1,41 +1,20 @@
-// hip_backend.hip -- the gfx950 implementation of gsi::Backend / gsi::Comm: one HIP stream
-// per context, every operation enqueued on it (no host round trips except where the
-// algorithm needs a scalar), workspaces grown on demand, RCCL for the collectives.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
+// hip_backend.hip -- the gfx950 implementation of gsi::Backend: one HIP stream per context, every operation enqueued on it (no host
+// round trips except where the algorithm needs a scalar), workspaces grown on demand.  The communicators are in hip_comm.hip.
 #include <dlfcn.h>
-#include <fcntl.h>
-#include <sched.h>
-#include <sys/mman.h>
-#include <time.h>
-#include <unistd.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <atomic>
 #include <mutex>
-#include <string>
-#include <chrono>
 #include <map>
 #include <memory>
 #include <set>
 #include <vector>
-#include "../../include/gsi_hip.h"
-#include "backend.hpp"
+#include "hip_backend.hpp"
 #include "hip_common.hpp"
 #include "host_staging.hpp"
 
 namespace gsi {
-
-#define HIP_CHECK(expr)                                                                            \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess)                                                                          \
-      throw Error(_e == hipErrorOutOfMemory ? GSI_ERR_OOM : GSI_ERR_HIP,                            \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));                               \
-  } while (0)
 
 namespace {
 
@@ -63,9 +42,21 @@ static RoctxApi& roctx() { static RoctxApi api; return api; }
 static const char* const kPhaseNames[PH_COUNT] = {"gsi:A*X", "gsi:A'*X", "gsi:lu(Y).L", "gsi:thin QR", "gsi:svd(l x l)",
                                                  "gsi:panel x (l x l)", "gsi:collective", "gsi:other", "gsi:waiting for peers"};
 
-class HipBackend : public Backend {
+class HipBackend : public HipDevice {
+  // A pooled temporary that goes back to the block cache on every exit path (a throwing HIP_CHECK between alloc
+  // and release leaked pooled blocks).  release() is ordered on the stream: WHERE a Scratch ends is part of what a function does.
+  // try_alloc: null instead of an exception, where memory is no reason to fail.
+  struct Scratch {
+    HipBackend* be; double* p;
+    explicit Scratch(HipBackend* b, size_t doubles = 0) : be(b), p(doubles ? b->alloc(doubles) : nullptr) {}
+    ~Scratch() { if (p) be->release(p); }
+    double* try_alloc(size_t doubles) { try { return p = be->alloc(doubles); } catch (const Error&) { return p = nullptr; } }
+    void adopt(double* q) { p = q; }
+    double* give_up() { double* q = p; p = nullptr; return q; }
+    Scratch(const Scratch&) = delete; Scratch& operator=(const Scratch&) = delete;
+  };
  public:
-  explicit HipBackend(int device) : device_(device) {
+  explicit HipBackend(int device) : HipDevice(device) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0)
@@ -81,8 +72,8 @@ class HipBackend : public Backend {
     // non-blocking: nothing of this library uses the NULL stream, and a runtime-internal or foreign NULL-stream operation
     // must never wait for (or be waited for by) a persistent kernel of ours that spins for its peers
     HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    HIP_CHECK(hipMalloc(&flags_, 16 * sizeof(int32_t)));
-    HIP_CHECK(hipMemsetAsync(flags_, 0, 16 * sizeof(int32_t), st_));
+    HIP_CHECK(hipMalloc(&flags_, FLAG_COUNT * sizeof(int32_t)));
+    HIP_CHECK(hipMemsetAsync(flags_, 0, FLAG_COUNT * sizeof(int32_t), st_));
     HIP_CHECK(hipMalloc(&scal_, (64 + 8 + 256) * sizeof(double)));   // scalars + partial sums of long dot products
   }
   ~HipBackend() override {
@@ -91,7 +82,7 @@ class HipBackend : public Backend {
     drain_side();
     stager_.reset();
     if (ev_stage_) hipEventDestroy(ev_stage_);
-    for (auto& b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_}) free_ws(*b);
+    for (DevBuf* b : ws_all_) free_ws(*b);
     collect_garbage();
     for (auto& b : pool_) hipFree(b.p);
     for (auto& ev : ev_pool_) hipEventDestroy(ev);
@@ -106,8 +97,6 @@ class HipBackend : public Backend {
     hipStreamDestroy(st_);
   }
   const char* name() const override { return "hip-gfx950"; }
-  hipStream_t stream() const { return st_; }
-  void bind() { hipSetDevice(device_); }
 
   // ---- memory ----
   // Panel-sized temporaries come and go inside every entry point; everything is ordered on the one
@@ -196,7 +185,7 @@ class HipBackend : public Backend {
   }
   void release_cache() override {
     bind();
-    for (DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_})
+    for (DevBuf* b : ws_all_)
       if (b->bytes > ((size_t)64 << 20)) free_ws(*b);
     (void)hipStreamSynchronize(st_);
     drain_side();
@@ -205,8 +194,8 @@ class HipBackend : public Backend {
   }
   int64_t bytes_in_use() const override {
     int64_t ws = 0;
-    for (const DevBuf* b : {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_svdf_, &ws_qr_hh_})
-      if (!b->pooled) ws += (int64_t)b->bytes;          // pooled workspaces are counted by alloc()
+    for (const DevBuf* b : ws_all_)                     // (ws_lus_ has never been part of this figure: it stays out of it)
+      if (b != &ws_lus_ && !b->pooled) ws += (int64_t)b->bytes;          // pooled workspaces are counted by alloc()
     return in_use_ + pooled_ + ws + (int64_t)garbage_bytes_;
   }
   // ---- the host boundary (host_staging.hpp): caller memory is pageable; transfers of GSI_STAGE_MIN_MB (default 16) MiB and
@@ -426,23 +415,22 @@ class HipBackend : public Backend {
     double* ws = gemm_ws(hipk::gemm_pointcov_workspace_doubles(m, l, k));
     // the wide kernel streams a tile-ordered copy of the sketch panel (k x l doubles); memory is never a reason to fail: without
     // the copy the product runs on the 128 x 160 kernel, which reads X where it lies
-    double* xpack = nullptr;
+    Scratch xpack(this);
     const size_t xdoubles = hipk::gemm_pointcov_pack_doubles(m, l, k);          // 0: not the wide kernel's product
-    if (xdoubles > 0) { try { xpack = alloc(xdoubles); } catch (const Error&) { xpack = nullptr; } }
-    struct Free { HipBackend* be; double* p; ~Free() { if (p) be->release(p); } } xfree{this, xpack};
-    hipk::gemm_f64_pointcov(st_, m, l, k, p4.p, npts, d, kind, sigma2, nugget, roff, koff, B, ldb, C, ldc, ws, xpack);
+    if (xdoubles > 0) xpack.try_alloc(xdoubles);
+    hipk::gemm_f64_pointcov(st_, m, l, k, p4.p, npts, d, kind, sigma2, nugget, roff, koff, B, ldb, C, ldc, ws, xpack.p);
     check_launch("gemm_nn_pointcov (in-loader generator)");
   }
 
   // ---- matrix-free FFT covariance ----
-  struct FftCov { int64_t N[3], M[3]; double* lam; double* W; int nb_max; };
-  // every temporary of a plan's construction goes back to the block cache on every exit path (a throwing HIP_CHECK
-  // or allocation between alloc and release leaked pooled blocks)
-  struct Hold { HipBackend* be; double* p; ~Hold() { if (p) be->release(p); } };
+  struct FftCov {                         // (W goes back before lam, on every way out)
+    int64_t N[3], M[3]; Scratch lam, W; int nb_max;
+    explicit FftCov(HipBackend* be) : lam(be), W(be) {}
+  };
   // the grid squeezed of its singleton axes, its embedding, the limits, and the plan's two arrays (spectrum, work array);
   // *reembed: FFTRF's exact 2 N embedding is not a power of two on some axis
   std::unique_ptr<FftCov> fftcov_new_plan(const int64_t N[3], int fftrf, bool* reembed, int* dims) {
-    std::unique_ptr<FftCov> p(new FftCov());
+    std::unique_ptr<FftCov> p(new FftCov(this));
     int64_t Mtot = 1;
     int d = 0;
     for (int a = 0; a < 3; ++a) { p->N[a] = 1; p->M[a] = 1; }
@@ -469,8 +457,8 @@ class HipBackend : public Backend {
     const int64_t w_mb = w_env > 0 ? w_env : ((d == 2 && 16 * Mtot <= ((int64_t)128 << 20)) ? 256 : 2048);
     int64_t nb = (w_mb << 20) / (16 * Mtot);
     p->nb_max = (int)std::max<int64_t>(1, std::min<int64_t>(nb, 64));
-    p->lam = alloc(hipk::fft_plan_doubles(p->M));
-    try { p->W = alloc((size_t)2 * Mtot * p->nb_max); } catch (...) { release(p->lam); throw; }
+    p->lam.adopt(alloc(hipk::fft_plan_doubles(p->M)));
+    p->W.adopt(alloc((size_t)2 * Mtot * p->nb_max));
     *dims = d;
     return p;
   }
@@ -478,24 +466,20 @@ class HipBackend : public Backend {
   // d real axes) as cur' = cur^T B (the contraction kernel's A'B form: the array as a k x rest matrix), which also rotates
   // that axis to the back: d applications restore the natural order.
   enum FftFactor { FFT_F_COS = 0, FFT_F_COS_WEIGHTED = 1, FFT_F_SIN_WEIGHTED = 2 };
-  void fft_rotate_apply(Hold& bufh, int64_t cur[3], int64_t& tot, int d, int64_t rows_out, int64_t period, FftFactor f) {
-    double*& buf = bufh.p;
+  void fft_rotate_apply(Scratch& buf, int64_t cur[3], int64_t& tot, int d, int64_t rows_out, int64_t period, FftFactor f) {
     // cur = (k, rest) column-major; B = k x rows_out; result (rest x rows_out) = the array with axis 0 replaced and last
     const int64_t k = cur[0], rest = (tot / k);
-    Hold Bh{this, alloc((size_t)k * rows_out)};
-    double* B = Bh.p;
+    Scratch B(this, (size_t)k * rows_out);
     // B[kk + t k] : weighted (the D and S factors) is indexed [t = row of the INPUT, k' = output]; unweighted [k, t]
-    if (f == FFT_F_COS) hipk::fft_cos_matrix(st_, B, k, rows_out, period, false);              // C_a^T: B[k, t]
-    else if (f == FFT_F_COS_WEIGHTED) hipk::fft_cos_matrix(st_, B, k, rows_out, period, true);  // D_a^T: B[t, k'] = w_t cos(.)
-    else hipk::fft_sin_matrix(st_, B, k, rows_out, period);                                   // S_a^T: B[t, k'] = w_t sin(.)
-    Hold outh{this, alloc((size_t)rest * rows_out)};
-    double* out = outh.p;
+    if (f == FFT_F_COS) hipk::fft_cos_matrix(st_, B.p, k, rows_out, period, false);              // C_a^T: B[k, t]
+    else if (f == FFT_F_COS_WEIGHTED) hipk::fft_cos_matrix(st_, B.p, k, rows_out, period, true);  // D_a^T: B[t, k'] = w_t cos(.)
+    else hipk::fft_sin_matrix(st_, B.p, k, rows_out, period);                                   // S_a^T: B[t, k'] = w_t sin(.)
+    Scratch out(this, (size_t)rest * rows_out);
     double* ws = gemm_ws(hipk::gemm_workspace_doubles(rest, rows_out, k));
-    hipk::gemm_f64(st_, true, rest, rows_out, k, 1.0, buf, k, B, k, 0.0, out, rest, ws);
+    hipk::gemm_f64(st_, true, rest, rows_out, k, 1.0, buf.p, k, B.p, k, 0.0, out.p, rest, ws);
     check_launch("fft re-embedding product");
-    release(buf);
-    buf = out;
-    outh.p = nullptr;
+    release(buf.give_up());
+    buf.adopt(out.give_up());
     tot = rest * rows_out;
     // rotate the dimension list: (k, c1, c2) -> (c1, c2, rows_out) over the d real axes
     int64_t nd[3] = {1, 1, 1};
@@ -506,7 +490,7 @@ class HipBackend : public Backend {
   // The second half of the re-embedding, shared by the power-law and the covariance-function plans: the lags of a kernel over
   // the box (bufh: N[0] x N[1] x N[2], natural order) -> (x_a D_a) c on the power-of-two embedding M, natural order; with
   // sine = true (x_a S_a) c, the odd-odd part of a centrally symmetric 2-D kernel.
-  void fftcov_lags_to_spectrum(Hold& bufh, int64_t cur[3], int64_t& tot, const FftCov* p, int d, bool sine) {
+  void fftcov_lags_to_spectrum(Scratch& bufh, int64_t cur[3], int64_t& tot, const FftCov* p, int d, bool sine) {
     for (int a = 0; a < d; ++a) fft_rotate_apply(bufh, cur, tot, d, p->M[a], p->M[a], sine ? FFT_F_SIN_WEIGHTED : FFT_F_COS_WEIGHTED);
   }
   void* fftcov_create(const int64_t N[3], double beta, int fftrf) override {
@@ -516,7 +500,7 @@ class HipBackend : public Backend {
     std::unique_ptr<FftCov> p = fftcov_new_plan(N, fftrf, &reembed, &d);
     const int64_t Mtot = p->M[0] * p->M[1] * p->M[2];
     if (!reembed) {
-      hipk::fft_spectrum(st_, p->lam, p->lam + Mtot, p->M, beta, fftrf);
+      hipk::fft_spectrum(st_, p->lam.p, p->lam.p + Mtot, p->M, beta, fftrf);
       check_launch("fft_spectrum");
       return p.release();
     }
@@ -524,22 +508,16 @@ class HipBackend : public Backend {
     // through the power-of-two passes with a re-embedded spectrum (fft_cov.hip, "FFTRF's convention on a grid ...").
     //   c  = (x_a C_a) lambda_{2N}    C_a[t, k]  = cos(2 pi t k / 2 N_a),            t < N_a, k < 2 N_a     (lags 0 .. N_a - 1)
     //   l' = (x_a D_a) c              D_a[k', t] = w_t cos(2 pi t k' / M'_a), w_0 = 1, w_t = 2              (c' even, 0 beyond)
-    try {
-      int64_t cur[3] = {1, 1, 1};
-      for (int a = 0; a < d; ++a) cur[a] = 2 * p->N[a];
-      int64_t tot = cur[0] * cur[1] * cur[2];
-      Hold bufh{this, nullptr};
-      bufh.p = alloc((size_t)tot);
-      hipk::fft_spectrum_natural(st_, bufh.p, cur, beta, 1);
-      for (int a = 0; a < d; ++a) fft_rotate_apply(bufh, cur, tot, d, p->N[a], 2 * p->N[a], FFT_F_COS);   // lags 0 .. N_a - 1 of c
-      fftcov_lags_to_spectrum(bufh, cur, tot, p.get(), d, false);              // the spectrum of the re-embedded kernel
-      hipk::fft_lines_layout(st_, bufh.p, p->lam, p->M);
-      hipk::fft_finish_plan(st_, p->lam, p->lam + Mtot, p->M);
-      check_launch("fft re-embedded spectrum");
-    } catch (...) {
-      release(p->W); release(p->lam);
-      throw;
-    }
+    int64_t cur[3] = {1, 1, 1};
+    for (int a = 0; a < d; ++a) cur[a] = 2 * p->N[a];
+    int64_t tot = cur[0] * cur[1] * cur[2];
+    Scratch bufh(this, (size_t)tot);
+    hipk::fft_spectrum_natural(st_, bufh.p, cur, beta, 1);
+    for (int a = 0; a < d; ++a) fft_rotate_apply(bufh, cur, tot, d, p->N[a], 2 * p->N[a], FFT_F_COS);   // lags 0 .. N_a - 1 of c
+    fftcov_lags_to_spectrum(bufh, cur, tot, p.get(), d, false);              // the spectrum of the re-embedded kernel
+    hipk::fft_lines_layout(st_, bufh.p, p->lam.p, p->M);
+    hipk::fft_finish_plan(st_, p->lam.p, p->lam.p + Mtot, p->M);
+    check_launch("fft re-embedded spectrum");
     return p.release();
   }
   // The same operator type for a covariance FUNCTION of the grid lags (gsi_op_fft_gridcov[_table]):
@@ -553,49 +531,39 @@ class HipBackend : public Backend {
     bool reembed = false;
     int d = 0;
     std::unique_ptr<FftCov> p = fftcov_new_plan(N, 0, &reembed, &d);
-    try {
-      int64_t cur[3] = {p->N[0], p->N[1], p->N[2]};      // singleton axes do not move an element of the lag table
-      int64_t tot = cur[0] * cur[1] * cur[2];
-      // a second quadrant only where it differs from the first: both axes of a 2-D grid longer than one point
-      const bool mirrored = (table ? table_mirror != nullptr : theta != 0.0) && d == 2 && N[2] == 1;
-      Hold cp{this, nullptr}, cm{this, nullptr};
-      cp.p = alloc((size_t)tot);
-      if (mirrored) cm.p = alloc((size_t)tot);
-      if (table) {
-        upload2d(cp.p, tot, table, tot, tot, 1);
-        if (mirrored) upload2d(cm.p, tot, table_mirror, tot, tot, 1);
-      } else {
-        const double inv_ell[3] = {1.0 / ell[0], 1.0 / ell[1], 1.0 / ell[2]};
-        hipk::fft_lag_table(st_, cp.p, cm.p, N, kind, inv_ell, std::cos(theta), std::sin(theta), sigma2);
-        check_launch("fft_lag_table");
-      }
-      if (mirrored) {
-        hipk::fft_even_odd_split(st_, cp.p, cm.p, tot);
-        int64_t cur_s[3] = {cur[0], cur[1], cur[2]};
-        int64_t tot_s = tot;
-        fftcov_lags_to_spectrum(cm, cur_s, tot_s, p.get(), d, true);
-      }
-      fftcov_lags_to_spectrum(cp, cur, tot, p.get(), d, false);
-      if (mirrored) hipk::fft_subtract(st_, cp.p, cm.p, tot);
-      hipk::fft_lines_layout(st_, cp.p, p->lam, p->M);
-      hipk::fft_finish_plan_lags(st_, p->lam, p->M, nugget);
-      check_launch("fft covariance-function spectrum");
-    } catch (...) {
-      release(p->W); release(p->lam);
-      throw;
+    int64_t cur[3] = {p->N[0], p->N[1], p->N[2]};      // singleton axes do not move an element of the lag table
+    int64_t tot = cur[0] * cur[1] * cur[2];
+    // a second quadrant only where it differs from the first: both axes of a 2-D grid longer than one point
+    const bool mirrored = (table ? table_mirror != nullptr : theta != 0.0) && d == 2 && N[2] == 1;
+    Scratch cp(this, (size_t)tot), cm(this, mirrored ? (size_t)tot : 0);
+    if (table) {
+      upload2d(cp.p, tot, table, tot, tot, 1);
+      if (mirrored) upload2d(cm.p, tot, table_mirror, tot, tot, 1);
+    } else {
+      const double inv_ell[3] = {1.0 / ell[0], 1.0 / ell[1], 1.0 / ell[2]};
+      hipk::fft_lag_table(st_, cp.p, cm.p, N, kind, inv_ell, std::cos(theta), std::sin(theta), sigma2);
+      check_launch("fft_lag_table");
     }
+    if (mirrored) {
+      hipk::fft_even_odd_split(st_, cp.p, cm.p, tot);
+      int64_t cur_s[3] = {cur[0], cur[1], cur[2]};
+      int64_t tot_s = tot;
+      fftcov_lags_to_spectrum(cm, cur_s, tot_s, p.get(), d, true);
+    }
+    fftcov_lags_to_spectrum(cp, cur, tot, p.get(), d, false);
+    if (mirrored) hipk::fft_subtract(st_, cp.p, cm.p, tot);
+    hipk::fft_lines_layout(st_, cp.p, p->lam.p, p->M);
+    hipk::fft_finish_plan_lags(st_, p->lam.p, p->M, nugget);
+    check_launch("fft covariance-function spectrum");
     return p.release();
   }
   void fftcov_destroy(void* plan) override {
-    FftCov* p = static_cast<FftCov*>(plan);
-    if (!p) return;
-    release(p->W); release(p->lam);
-    delete p;
+    delete static_cast<FftCov*>(plan);
   }
   void fftcov_apply(void* plan, int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy) override {
     bind();
     FftCov* p = static_cast<FftCov*>(plan);
-    hipk::fft_cov_apply(st_, p->N, p->M, p->lam, reinterpret_cast<double2*>(p->W), p->nb_max, l, X, ldx, Y, ldy);
+    hipk::fft_cov_apply(st_, p->N, p->M, p->lam.p, reinterpret_cast<double2*>(p->W.p), p->nb_max, l, X, ldx, Y, ldy);
     check_launch("fft_cov_apply");
   }
 
@@ -614,18 +582,13 @@ class HipBackend : public Backend {
     // Panels of up to 4096 rows per CU: leaves held in registers (panel_lu_leaf.hip), left-looking updates between the
     // blocks (panel_lu_blocks.hip).  Everything else takes the streamed leaves below (panel_lu_streamed.hip).
     hipk::Lu2Work w2;
-    static const bool tall_first = (getenv("GSI_LU_TALL") != nullptr && getenv("GSI_LU_TALL")[0] == '1');
     // Panels taller than the register file holds (up to GSI_LU_OV_MAX rows, default 5 x 2^20): the resident kernel on all
     // CUs with the rows beyond its window evaluated lazily out of L2 / Infinity Cache / HBM; beyond that the streamed leaves
     // win (measured cross-over: 6e6 rows at l = 320).  GSI_LU_OV=0 switches it off (A/B).
     static const int64_t ov_max = getenv("GSI_LU_OV_MAX") ? atoll(getenv("GSI_LU_OV_MAX")) : ((int64_t)5 << 20);
     static const bool ov_off = (getenv("GSI_LU_OV") != nullptr && getenv("GSI_LU_OV")[0] == '0');
-    // Ranks that SHARE this device (the RCCL-free communicators, one-GPU rehearsals of a multi-GPU job) each factor their
-    // replicated panel with a whole-chip grid of their own: the grids cannot all be resident, so the persistent kernel is
-    // not a candidate at all (seen: 2 rank processes on one GPU, gathered 10^6 x 320 panel: a poll time-out on some runs).
-    const bool resident_ok = !tall_first && !lu2_lost_ && ranks_sharing_device_ <= 1;
-    bool fits = resident_ok && hipk::lu2_config(m, ncus_, &w2.bs, &w2.rpt, &w2.grid) && lu2_fits(w2.bs, w2.rpt, w2.grid);
-    if (!fits && resident_ok && !ov_off && m <= ov_max && ncus_ >= 1) {
+    bool fits = lu2_takes(m, &w2);
+    if (!fits && lu2_resident_ok() && !ov_off && m <= ov_max && ncus_ >= 1) {
       const int g = std::min(ncus_, 256);
       if (m > (int64_t)g * 4096) {
         if (lu2_ov_resident_ < 0) lu2_ov_resident_ = hipk::lu2_resident_per_cu_ov();
@@ -643,7 +606,7 @@ class HipBackend : public Backend {
       w2.nb = (nb_env == 32 || nb_env == 64) ? nb_env : hipk::LU2_NB;
       grow(ws_lu_, hipk::lu2_work_bytes(l, w2.grid));
       hipk::lu2_carve(w2, l, ws_lu_.p);
-      w2.info = flags_ + 0;
+      w2.info = flags_ + FLAG_LU_INFO;
       hipk::lu2_L(st_, Y, m, l, ld, w2);
       check_launch("lu2_L");
       ipiv_dev = w2.ipiv;
@@ -655,7 +618,7 @@ class HipBackend : public Backend {
       // round 4, are kept as tools/rejected_kernels/panel_lu_round1_sweeps.hip.txt.)
       if (m >= ((int64_t)1 << 31)) throw Error(GSI_ERR_ARG, "lu: panels of 2^31 rows and more are not supported");
       grow(ws_lu_, hipk::lu3_work_bytes(l));
-      hipk::lu3_L(st_, Y, m, l, ld, ws_lu_.p, flags_ + 0, &ipiv_dev);
+      hipk::lu3_L(st_, Y, m, l, ld, ws_lu_.p, flags_ + FLAG_LU_INFO, &ipiv_dev);
       check_launch("lu3_L");
     }
     if (ipiv_dev_out) *ipiv_dev_out = ipiv_dev;
@@ -704,7 +667,7 @@ class HipBackend : public Backend {
     LusWs ws = lus_ws(mloc, l);
     static const bool fuse = (getenv("GSI_LUS_NO_FUSE") == nullptr);      // A/B knob
     const bool next = fuse && (s + 1 < w) && mloc > 0;
-    hipk::lus_apply(st_, Yloc, ld, mloc, row0, m, l, j0, s, w, recs, nranks, ws.ipiv, flags_ + 0, next ? ws.pval : nullptr,
+    hipk::lus_apply(st_, Yloc, ld, mloc, row0, m, l, j0, s, w, recs, nranks, ws.ipiv, flags_ + FLAG_LU_INFO, next ? ws.pval : nullptr,
                     next ? ws.pidx : nullptr);
     check_launch("lus_apply");
     lus_part_col_ = next ? j0 + s + 1 : -1;
@@ -790,7 +753,7 @@ class HipBackend : public Backend {
                 " ranks on this device) would not all be resident");
     w.rank = comm->rank; w.nranks = G;
     for (int g = 0; g < G; ++g) w.peer[g] = mr_peer_[g];
-    w.info = flags_ + 0;
+    w.info = flags_ + FLAG_LU_INFO;
     if (const char* e = getenv("GSI_LU_POLL_LIMIT")) w.poll_limit = atoi(e);
     mr_work_ = w;
     mr_reason_.clear();
@@ -835,11 +798,11 @@ class HipBackend : public Backend {
   }
   void lu_flag_export(double* flag) override {
     bind();
-    hipk::lu_flag_export(st_, flags_ + 0, flag);
+    hipk::lu_flag_export(st_, flags_ + FLAG_LU_INFO, flag);
   }
   void lu_flag_import(const double* flag) override {
     bind();
-    hipk::lu_flag_import(st_, flags_ + 0, flag);
+    hipk::lu_flag_import(st_, flags_ + FLAG_LU_INFO, flag);
     check_launch("lu_flag_import");
   }
   void lus_leaf_mr(double* Yloc, int64_t mloc, int64_t ld, int64_t row0, int64_t m, int64_t l, int64_t jb, int64_t j0, int w,
@@ -876,6 +839,32 @@ class HipBackend : public Backend {
     HIP_CHECK(hipMemcpyAsync(host, w.ipiv, sizeof(int32_t) * l, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
   }
+  // ---- the first CholeskyQR tier, as qr_thinQ, qr_thinQ_deferred and svd_tall_fused all try it ----
+  bool cholqr_gate(int64_t m, int64_t l) {
+    static const bool no_cholqr = (getenv("GSI_NO_CHOLQR") != nullptr);
+    return !no_cholqr && l <= 1024 && m >= 2 * l;
+  }
+  // contraction workspace: the Gram matrix (upper tiles, or the dedicated kernel's slab partials), Y R^-1, the l x l inverse
+  static size_t cholqr_ws_doubles(int64_t m, int64_t l) {
+    return std::max({hipk::gemm_workspace_doubles(l, l, m), hipk::gemm_syrk_workspace_doubles(l, m), hipk::syrk_upper_workspace_doubles(l, m),
+                     hipk::gemm_workspace_doubles(m, l, l), hipk::gemm_workspace_doubles(l, 32, l)});
+  }
+  int32_t read_flag(int slot) {                             // one 4-byte read-back: the stream is idle afterwards
+    int32_t f = 0;
+    HIP_CHECK(hipMemcpyAsync(&f, flags_ + slot, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    return f;
+  }
+  // Both rounds out of place: Y is read only, T = Y R1^-1 (ld ldt) and the small factors are what a true leaves behind.  A
+  // false sets the caller's hint: the next eight factorizations of this kind do not try this tier.
+  bool cholqr2_try(const double* Y, int64_t m, int64_t l, int64_t ld, double* T, int64_t ldt, double* small, double* ws, int& skip) {
+    HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOLQR, 0, sizeof(int32_t), st_));
+    hipk::cholqr2_factor(st_, Y, m, l, ld, T, ldt, small, flags_ + FLAG_CHOLQR, ws);
+    check_launch("cholqr2_factor");
+    if (read_flag(FLAG_CHOLQR) == 0) return true;
+    skip = 8;
+    return false;
+  }
   void qr_thinQ(double* Y, int64_t m, int64_t l, int64_t ld, double* R, bool replicated) override {
     bind();
     const int64_t nb = hipk::qr_max_blocks(m);
@@ -894,13 +883,7 @@ class HipBackend : public Backend {
     w.coef = base + o_coef; w.part = base + o_part; w.tau = base + o_tau; w.T = base + o_T; w.G = base + o_G;
     w.Vbuf = nullptr; w.Wt = base + o_Wt; w.W2 = base + o_W2; w.Qo = base + o_Q; w.maxblocks = nb;
     // gemm shapes inside: (t x NB, K = m), (NB x NB, K = m), (m x t, K = NB), (l x l, K = m), (m x 32, K <= l)
-    size_t gmax = hipk::gemm_workspace_doubles(l, NB, m);
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(NB, NB, m));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, m));
-    gmax = std::max(gmax, hipk::gemm_syrk_workspace_doubles(l, m));     // CholeskyQR: Gram matrix, upper tiles only
-    gmax = std::max(gmax, hipk::syrk_upper_workspace_doubles(l, m));    //             : the dedicated kernel's slab partials
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(m, l, l));       // CholeskyQR2: Y R^-1 as one product
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, 32, l));      //             : the l x l inverse
+    size_t gmax = std::max({hipk::gemm_workspace_doubles(l, NB, m), hipk::gemm_workspace_doubles(NB, NB, m), cholqr_ws_doubles(m, l)});
     for (int64_t t = NB; t <= l; t += NB) gmax = std::max(gmax, hipk::gemm_workspace_doubles(t, NB, m));
     double* ws = gemm_ws(gmax + 64);
     // Three tiers, each leaving Y untouched until it is known to have worked (one 4-byte flag read):
@@ -911,46 +894,30 @@ class HipBackend : public Backend {
     // (height, replicated) so that, with several ranks, the replicated factorizations (stacked R factors, gathered
     // panels: identical input everywhere) never see a hint left by a rank's own row block -- not even when a row
     // block happens to have G*l rows -- and stay bit-identical across ranks.
-    static const bool no_cholqr = (getenv("GSI_NO_CHOLQR") != nullptr);
-    if (!no_cholqr && l <= 1024 && m >= 2 * l) {
+    if (cholqr_gate(m, l)) {
       const int64_t ldt = (m + 1) & ~(int64_t)1;   // even: 16-byte loads in the contraction kernel
-      int32_t f = 0;
       int& skip_tier1_ = skip_tier1_by_height_[std::make_pair(m, replicated)];
       if (skip_tier1_ > 0) {
         --skip_tier1_;
-      } else {
-        // both rounds run out of place (Y -> Qo -> Y); Y is only overwritten once the flag is known to be clear
-        HIP_CHECK(hipMemsetAsync(flags_ + 9, 0, sizeof(int32_t), st_));
-        hipk::cholqr2_factor(st_, Y, m, l, ld, w.Qo, ldt, base + o_small, flags_ + 9, ws);
-        check_launch("cholqr2_factor");
-        HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        if (f == 0) {
-          hipk::cholqr2_apply(st_, Y, m, l, ld, w.Qo, ldt, R, base + o_small, ws);
-          check_launch("cholqr2_apply");
-          ++n_cholqr_;
-          return;
-        }
-        skip_tier1_ = 8;
+      } else if (cholqr2_try(Y, m, l, ld, w.Qo, ldt, base + o_small, ws, skip_tier1_)) {   // Y -> Qo, and only now Qo -> Y
+        hipk::cholqr2_apply(st_, Y, m, l, ld, w.Qo, ldt, R, base + o_small, ws);
+        check_launch("cholqr2_apply");
+        ++n_cholqr_;
+        return;
       }
       // second tier: shifted CholeskyQR3 with one more transient panel; Y still untouched
       static const bool no_scholqr3 = (getenv("GSI_NO_SCHOLQR3") != nullptr);
-      double* S2 = nullptr;
-      if (!no_scholqr3) {
-        try { S2 = alloc((size_t)ldt * l); } catch (const Error&) { S2 = nullptr; }
-      }
-      if (S2 != nullptr) {
-        struct Guard { HipBackend* be; double* p; ~Guard() { be->release(p); } } guard{this, S2};   // stream-ordered pool
-        HIP_CHECK(hipMemsetAsync(flags_ + 9, 0, sizeof(int32_t), st_));
-        hipk::scholqr3_factor(st_, Y, m, l, ld, w.Qo, ldt, S2, ldt, base + o_small, flags_ + 9, ws);
+      Scratch S2(this);                            // (stream-ordered pool; memory is no reason to fail: the third tier)
+      if (!no_scholqr3 && S2.try_alloc((size_t)ldt * l) != nullptr) {
+        HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOLQR, 0, sizeof(int32_t), st_));
+        hipk::scholqr3_factor(st_, Y, m, l, ld, w.Qo, ldt, S2.p, ldt, base + o_small, flags_ + FLAG_CHOLQR, ws);
         check_launch("scholqr3_factor");
-        HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        if (f == 0) {
-          hipk::scholqr3_apply(st_, Y, m, l, ld, S2, ldt, R, base + o_small, ws);
+        if (read_flag(FLAG_CHOLQR) == 0) {
+          hipk::scholqr3_apply(st_, Y, m, l, ld, S2.p, ldt, R, base + o_small, ws);
           check_launch("scholqr3_apply");
+          ++n_scholqr3_;
+          return;
         }
-        if (f == 0) { ++n_scholqr3_; return; }
       }
       skip_tier1_ = 0;   // neither Cholesky tier applies to this kind of panel: probe from the top next time
     }
@@ -965,8 +932,8 @@ class HipBackend : public Backend {
   // Householder gets its Q the ordinary way), and only while the workspace is one this backend keeps between calls.
   bool qr_thinQ_deferred(const double* Y, int64_t m, int64_t l, int64_t ld, const double** Q1, int64_t* ldq1, double* X2) override {
     bind();
-    static const bool off = (getenv("GSI_NO_CHOLQR") != nullptr) || (getenv("GSI_NO_QR_DEFER") != nullptr);
-    if (off || l > 1024 || m < 2 * l) return false;
+    static const bool off = (getenv("GSI_NO_QR_DEFER") != nullptr);
+    if (off || !cholqr_gate(m, l)) return false;
     const int64_t ldt = (m + 1) & ~(int64_t)1;
     if ((size_t)ldt * l * sizeof(double) > ((size_t)8 << 30)) return false;       // trimmed on return: nothing would be left to hand out
     int& skip_tier1 = skip_tier1_by_height_[std::make_pair(m, false)];
@@ -976,22 +943,10 @@ class HipBackend : public Backend {
     const size_t o_small = take(hipk::cholqr_small_doubles(l)), o_T = take((size_t)ldt * l);
     grow(ws_qr_, cnt * sizeof(double));
     double* base = (double*)ws_qr_.p;
-    size_t gmax = hipk::gemm_workspace_doubles(l, l, m);
-    gmax = std::max(gmax, hipk::gemm_syrk_workspace_doubles(l, m));
-    gmax = std::max(gmax, hipk::syrk_upper_workspace_doubles(l, m));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(m, l, l));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, 32, l));
-    double* ws = gemm_ws(gmax + 64);
-    int32_t f = 0;
-    HIP_CHECK(hipMemsetAsync(flags_ + 9, 0, sizeof(int32_t), st_));
-    hipk::cholqr2_factor(st_, Y, m, l, ld, base + o_T, ldt, base + o_small, flags_ + 9, ws);
-    check_launch("cholqr2_factor");
-    HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (f != 0) { skip_tier1 = 8; return false; }
+    double* ws = gemm_ws(cholqr_ws_doubles(m, l) + 64);
+    if (!cholqr2_try(Y, m, l, ld, base + o_T, ldt, base + o_small, ws, skip_tier1)) return false;
     HIP_CHECK(hipMemcpyAsync(X2, hipk::cholqr2_X2(base + o_small, l), sizeof(double) * (size_t)l * l, hipMemcpyDeviceToDevice, st_));
-    *Q1 = base + o_T;
-    *ldq1 = ldt;
+    *Q1 = base + o_T; *ldq1 = ldt;
     ++n_cholqr_;
     return true;
   }
@@ -1001,8 +956,8 @@ class HipBackend : public Backend {
   bool svd_tall_fused(const double* W, int64_t m, int64_t l, int64_t ld, int64_t K_scale, double* V, int64_t ldv,
                       double* S, const double* Xr) override {
     bind();
-    static const bool off = (getenv("GSI_NO_CHOLQR") != nullptr) || (getenv("GSI_NO_SVD_FUSION") != nullptr);
-    if (off || l > 1024 || m < 2 * l) return false;
+    static const bool off = (getenv("GSI_NO_SVD_FUSION") != nullptr);
+    if (off || !cholqr_gate(m, l)) return false;
     int& skip_tier1 = skip_tier1_by_height_[std::make_pair(m, false)];
     if (skip_tier1 > 0) return false;                       // this kind of panel needs the shifted tier: generic path
     const int64_t ldt = (m + 1) & ~(int64_t)1;
@@ -1013,23 +968,10 @@ class HipBackend : public Backend {
     grow(ws_svdf_, cnt * sizeof(double));
     TrimGuard trim_svdf{this, &ws_svdf_};
     double* base = (double*)ws_svdf_.p;
-    size_t gmax = hipk::gemm_workspace_doubles(l, l, m);
-    gmax = std::max(gmax, hipk::gemm_syrk_workspace_doubles(l, m));
-    gmax = std::max(gmax, hipk::syrk_upper_workspace_doubles(l, m));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(m, l, l));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, 32, l));
-    gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, l));
-    double* ws = gemm_ws(gmax + 64);
-    int32_t f = 0;
+    double* ws = gemm_ws(std::max(cholqr_ws_doubles(m, l), hipk::gemm_workspace_doubles(l, l, l)) + 64);
     phase_begin(PH_QR);
-    HIP_CHECK(hipMemsetAsync(flags_ + 9, 0, sizeof(int32_t), st_));
-    hipk::cholqr2_factor(st_, W, m, l, ld, base + o_T, ldt, base + o_small, flags_ + 9, ws);
-    check_launch("cholqr2_factor");
-    HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (f != 0) {
+    if (!cholqr2_try(W, m, l, ld, base + o_T, ldt, base + o_small, ws, skip_tier1)) {
       phase_end(PH_QR);
-      skip_tier1 = 8;
       return false;                                         // W is untouched: the caller's generic path takes over
     }
     hipk::cholqr2_R(st_, l, base + o_small, base + o_R);    // R = R2 R1
@@ -1090,8 +1032,7 @@ class HipBackend : public Backend {
   bool lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
                     int64_t K, double c, double* Z, int64_t ldz, double* Sv, double* scratch, size_t scratch_doubles) override {
     bind();
-    static const bool off = (getenv("GSI_NO_CHOLQR") != nullptr);
-    if (off || l < 1 || l > 384 || l > N - 1 || K < 1 || K > l || N > 4096 || n < 2 * l) return false;
+    if (!cholqr_gate(n, l) || l < 1 || l > 384 || l > N - 1 || K < 1 || K > l || N > 4096) return false;
     // < 0: the default gate; 0: off; in (0, 1): forced
     static const double ov_env = [] {
       const char* e = getenv("GSI_LOWRANK_TAIL_OVERLAP");
@@ -1146,11 +1087,10 @@ class HipBackend : public Backend {
     auto round = [&](const double* M, int i, bool check) {
       hipk::gemm_f64(st_, false, N, l, N, 1.0, G, N, M, N, 0.0, P, N, ws);
       hipk::gemm_f64(st_, true, l, l, N, 1.0, M, N, P, N, 0.0, Gr[i], l, ws);
-      (void)hipk::cq_gram_round(st_, Gr[i], l, X[i], check, flags_ + 9);
+      (void)hipk::cq_gram_round(st_, Gr[i], l, X[i], check, flags_ + FLAG_CHOLQR);
     };
-    int32_t f = 0;
     phase_begin(PH_QR);
-    HIP_CHECK(hipMemsetAsync(flags_ + 9, 0, sizeof(int32_t), st_));
+    HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOLQR, 0, sizeof(int32_t), st_));
     hipk::scal_copy(st_, (int64_t)N * l, c, T, A0);                                          // Y = S A0
     round(A0, 0, false);
     hipk::gemm_f64(st_, false, N, l, l, 1.0, A0, N, X[0], l, 0.0, A1, N, ws);               // Q1 = Y R1^-1 = S A1
@@ -1165,9 +1105,7 @@ class HipBackend : public Backend {
       (void)hipk::gemm_f64_nn_capped(st2_, nf, l, N, Sm, lds, A1, N, Yf, nf, cap);        // Y_f = S[0:n_f] B1
       check_launch("lowrank_tail (side product)");
     }
-    HIP_CHECK(hipMemcpyAsync(&f, flags_ + 9, sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (f != 0) {
+    if (read_flag(FLAG_CHOLQR) != 0) {
       side.join();
       phase_end(PH_QR);
       return false;                                         // nothing of Z or Sv written: the caller's path takes over
@@ -1240,7 +1178,7 @@ class HipBackend : public Backend {
     double* ws = gemm_ws(gmax + 64);
     struct Verdict { double parts[NPARTS]; int32_t v[4]; };
     if (pin_power_ == nullptr) HIP_CHECK(hipHostMalloc(&pin_power_, sizeof(Verdict), hipHostMallocDefault));
-    hipk::lr_compose(st_, ipiv, flags_ + 0, n, l, nchk, o_chk, o_sm, ldr, idx_dev, idx_dev + ldr, idx_dev + 2 * ldr, verdict);
+    hipk::lr_compose(st_, ipiv, flags_ + FLAG_LU_INFO, n, l, nchk, o_chk, o_sm, ldr, idx_dev, idx_dev + ldr, idx_dev + 2 * ldr, verdict);
     hipk::lr_gather_rows(st_, Sm, lds, N, idx_dev, idx_dev + ldr, nr, R, ldr);
     hipk::gemm_f64(st_, false, l, l, N, 1.0, R + o_chk, ldr, T, N, 0.0, Mp, l, ws);          // S[perm(0:l)] T
     hipk::lr_solve_u(st_, L, ldl, Mp, l, c, Ut);                                               // U = c L11^-1 Mp
@@ -1283,18 +1221,23 @@ class HipBackend : public Backend {
     w.idx1 = (int64_t*)(base + 2048);                      // src, sub (ldr each), chk (l1)
     return w;
   }
-  bool lu2_takes(int64_t m) {                             // lu_L_impl's first choice: the leaves held in registers
+  // Ranks that SHARE this device (the RCCL-free communicators, one-GPU rehearsals of a multi-GPU job) each factor their
+  // replicated panel with a whole-chip grid of their own: the grids cannot all be resident, so the persistent kernels are
+  // not candidates at all (seen: 2 rank processes on one GPU, gathered 10^6 x 320 panel: a poll time-out on some runs).
+  bool lu2_resident_ok() const {
     static const bool tall_first = (getenv("GSI_LU_TALL") != nullptr && getenv("GSI_LU_TALL")[0] == '1');
-    hipk::Lu2Work w;
-    return !tall_first && !lu2_lost_ && ranks_sharing_device_ <= 1 && hipk::lu2_config(m, ncus_, &w.bs, &w.rpt, &w.grid) &&
-           lu2_fits(w.bs, w.rpt, w.grid);
+    return !tall_first && !lu2_lost_ && ranks_sharing_device_ <= 1;
+  }
+  bool lu2_takes(int64_t m, hipk::Lu2Work* w) {           // lu_L_impl's first choice: the leaves held in registers (geometry in *w)
+    return lu2_resident_ok() && hipk::lu2_config(m, ncus_, &w->bs, &w->rpt, &w->grid) && lu2_fits(w->bs, w->rpt, w->grid);
   }
   bool lowrank_split_ok(int64_t n, int64_t N, int64_t l, int64_t l1) override {
     bind();
     if (l1 < 1 || l1 > SPLIT_MAX_L1 || l <= l1 || l > 2 * l1 || l - l1 < 8 || l > 384 || N < 1 || N > 4096 || n < 2 * l ||
         n >= ((int64_t)1 << 31))
       return false;
-    return lu2_takes(n) && lu2_takes(n - l1);
+    hipk::Lu2Work w;
+    return lu2_takes(n, &w) && lu2_takes(n - l1, &w);
   }
   void lowrank_split_schur(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* T, const int32_t* ipiv1,
                            const double* P, int64_t ldp, int64_t l, int64_t l1, double c, double* Tt) override {
@@ -1312,7 +1255,7 @@ class HipBackend : public Backend {
     gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l2, l1));
     double* ws = gemm_ws(gmax + 64);
     int64_t* src = w.idx1, * sub = w.idx1 + w.ldr, * chk = w.idx1 + 2 * w.ldr;
-    hipk::lr_compose(st_, ipiv1, flags_ + 0, n, l1, l1, w.o_chk, w.o_sm, w.ldr, src, sub, chk, w.verdict1);
+    hipk::lr_compose(st_, ipiv1, flags_ + FLAG_LU_INFO, n, l1, l1, w.o_chk, w.o_sm, w.ldr, src, sub, chk, w.verdict1);
     hipk::lr_pivots(st_, ipiv1, l1, 0, w.piv);                                                  // (the next LU reuses ws_lu_)
     hipk::lr_gather_rows(st_, Sm, lds, N, src + w.o_chk, sub + w.o_chk, l1, R, up8(l1));
     hipk::gemm_f64(st_, false, l1, l, N, 1.0, R, up8(l1), T, N, 0.0, Mp, l1, ws);             // S[perm(0:l1)] T
@@ -1340,7 +1283,7 @@ class HipBackend : public Backend {
     Scratch buf(this, (size_t)(2 * ldr + 8) + (size_t)(2 * l2) * (size_t)l1);
     int64_t* src = reinterpret_cast<int64_t*>(buf.p), * sub = src + ldr, * chk = sub + ldr;
     double* tmp = buf.p + 2 * ldr + 8;
-    hipk::lr_compose(st_, ipiv2, flags_ + 0, n - l1, l2, 0, 2 * l2, 2 * l2, ldr, src, sub, chk, w.verdict2);
+    hipk::lr_compose(st_, ipiv2, flags_ + FLAG_LU_INFO, n - l1, l2, 0, 2 * l2, 2 * l2, ldr, src, sub, chk, w.verdict2);
     hipk::lr_pivots(st_, ipiv2, l2, l1, w.piv + l1);
     hipk::lr_move_rows(st_, P + l1, ldp, l1, src, sub, w.verdict2, 2 * l2, tmp, 2 * l2, 0);
     check_launch("lowrank_split_join");
@@ -1348,7 +1291,7 @@ class HipBackend : public Backend {
   }
   void lowrank_split_undo() override {
     bind();
-    hipk::lr_forget_zero_pivot(st_, flags_ + 0);
+    hipk::lr_forget_zero_pivot(st_, flags_ + FLAG_LU_INFO);
     check_launch("lowrank_split_undo");
   }
   void svd_small(double* G, int64_t l, double* U, double* S) override {
@@ -1358,7 +1301,7 @@ class HipBackend : public Backend {
     hipk::SvdWork w;
     w.norms = (double*)ws_svd_.p;
     w.pairs = (int32_t*)((char*)ws_svd_.p + sizeof(double) * (l + 8) + 64);
-    w.rotcount = flags_ + 8;
+    w.rotcount = flags_ + FLAG_SVD_ROTATIONS;
     const int sw = hipk::svd_small(st_, G, l, U, S, w);
     last_svd_sweeps_ = sw < 0 ? -sw : sw;
     if (sw < 0) ++n_svd_cap_hits_;          // 40 sweeps and rotatable pairs left (factors graded over > 1e10): gsi_ctx_path_info reports it
@@ -1367,7 +1310,7 @@ class HipBackend : public Backend {
   void chol_upper(double* B, int64_t j) override {
     bind();
     if (j > 2048) throw Error(GSI_ERR_ARG, "chol_upper: j too large");
-    hipk::chol_upper(st_, B, j, flags_ + 1);
+    hipk::chol_upper(st_, B, j, flags_ + FLAG_CHOL_INFO);
     check_launch("chol_upper");
   }
   void trsm_right_upper(double* F, int64_t m, int64_t j, int64_t ldf, const double* C) override {
@@ -1414,9 +1357,7 @@ class HipBackend : public Backend {
     if (nb > 4096) nb = 4096;
     if (nb > nf) nb = nf;
     if (nb < 1) nb = 1;
-    Hold plan{this, nullptr}, ws{this, nullptr};
-    plan.p = alloc(hipk::fftrf_plan_doubles(g));
-    ws.p = alloc((size_t)(fs * nb));
+    Scratch plan(this, hipk::fftrf_plan_doubles(g)), ws(this, (size_t)(fs * nb));
     hipk::fftrf_plan(st_, g, plan.p);
     for (int64_t f0 = 0; f0 < nf; f0 += nb) {
       const int b = (int)((nf - f0 < nb) ? (nf - f0) : nb);
@@ -1527,7 +1468,7 @@ class HipBackend : public Backend {
   }
   void forgive_lost_coresidency() override {
     bind();
-    (void)hipMemsetAsync(flags_, 0, 8 * sizeof(int32_t), st_);
+    (void)hipMemsetAsync(flags_, 0, FLAG_ERROR_WORDS * sizeof(int32_t), st_);
     lu2_lost_ = false;
     lu2_retry_ = false;          // (mr_disabled_ stays as the self-test left it)
   }
@@ -1539,16 +1480,17 @@ class HipBackend : public Backend {
 
   int take_error(std::string* msg) override {
     bind();
-    int32_t h[16];
+    int32_t h[FLAG_COUNT];
     HIP_CHECK(hipMemcpyAsync(h, flags_, sizeof(h), hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     if (st2_) HIP_CHECK(hipStreamSynchronize(st2_));   // (idle unless a call ended in an exception between fork and join)
     HIP_CHECK(hipGetLastError());
     if (!garbage_.empty()) collect_garbage();
-    if (h[0] >= 0) mr_in_flight_ = false;
-    if (h[0] != 0 || h[1] != 0) {
-      HIP_CHECK(hipMemsetAsync(flags_, 0, 8 * sizeof(int32_t), st_));
-      if (h[0] < 0) {
+    const int32_t lu = h[FLAG_LU_INFO], chol = h[FLAG_CHOL_INFO];
+    if (lu >= 0) mr_in_flight_ = false;
+    if (lu != 0 || chol != 0) {
+      HIP_CHECK(hipMemsetAsync(flags_, 0, FLAG_ERROR_WORDS * sizeof(int32_t), st_));
+      if (lu < 0) {
         // co-residency of the persistent leaf kernel was lost (a workgroup never got a CU: the GPU is shared with
         // another queue).  The panel of that factorization is destroyed; this context factors with
         // streamed leaves (no spin-waits between workgroups) from now on, and the entry point may be re-run on its inputs.
@@ -1564,16 +1506,16 @@ class HipBackend : public Backend {
         }
         mr_in_flight_ = false;
         if (msg) *msg = "lu(): the pivot exchange between workgroups timed out (GPU shared with another job?); "
-                        "this context now streams its leaves (no spin-waits) [waited for: phase " + std::to_string(h[2]) +
-                        ", slot " + std::to_string(h[3]) + ", epoch " + std::to_string(h[4]) + ", by rank*1024+workgroup " +
-                        std::to_string(h[5]) + "]";
+                        "this context now streams its leaves (no spin-waits) [waited for: phase " + std::to_string(h[FLAG_WAIT_PHASE]) +
+                        ", slot " + std::to_string(h[FLAG_WAIT_SLOT]) + ", epoch " + std::to_string(h[FLAG_WAIT_EPOCH]) +
+                        ", by rank*1024+workgroup " + std::to_string(h[FLAG_WAIT_WHO]) + "]";
         return GSI_ERR_INTERNAL;
       }
-      if (h[0] != 0) {
-        if (msg) *msg = "SingularException(" + std::to_string(h[0]) + "): exactly zero pivot in lu()";
+      if (lu != 0) {
+        if (msg) *msg = "SingularException(" + std::to_string(lu) + "): exactly zero pivot in lu()";
         return GSI_ERR_SINGULAR;
       }
-      if (msg) *msg = "PosDefException: matrix is not positive definite; Cholesky failed at " + std::to_string(h[1]);
+      if (msg) *msg = "PosDefException: matrix is not positive definite; Cholesky failed at " + std::to_string(chol);
       return GSI_ERR_NOT_POSDEF;
     }
     return 0;
@@ -1626,16 +1568,8 @@ class HipBackend : public Backend {
   int64_t svd_cap_hits() override { return n_svd_cap_hits_; }
   int64_t lowrank_tail_overlaps() override { return n_tail_overlaps_; }
   void set_ranks_sharing_device(int n) override { ranks_sharing_device_ = n; }
-  int device() const { return device_; }
 
  private:
-  struct Scratch {                 // a pooled temporary that goes back to the block cache on every exit path
-    HipBackend* be; double* p;
-    Scratch(HipBackend* b, size_t doubles) : be(b), p(doubles ? b->alloc(doubles) : nullptr) {}
-    ~Scratch() { if (p) be->release(p); }
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-  };
   struct Rec { Phase phase; hipEvent_t a, b; bool counted; };
   hipEvent_t get_event() {
     if (!ev_pool_.empty()) { hipEvent_t e = ev_pool_.back(); ev_pool_.pop_back(); return e; }
@@ -1745,10 +1679,8 @@ class HipBackend : public Backend {
     return (double*)ws_gemm_.p;
   }
 
-  int device_;
   int ncus_ = 0;
   std::string arch_;
-  hipStream_t st_ = nullptr;
   // the side stream of lowrank_tail's overlap (created at its first use, lower priority than st_) and the two events that
   // order it against st_: work is put on it only between a fork and a join inside one call, so whatever drains st_ after
   // that call has drained it too; the places that drain or tear down st_ drain it all the same (drain_side)
@@ -1758,10 +1690,19 @@ class HipBackend : public Backend {
   std::unique_ptr<HostStager> stager_;        // the pinned staging ring of the host boundary (created at the first large transfer)
   bool stager_failed_ = false;
   hipEvent_t ev_stage_ = nullptr;
-  int32_t* flags_ = nullptr;  // [0] lu info, [1] chol info, [8] jacobi rotation counter
+  enum FlagSlot {                // the slots of flags_; the first FLAG_ERROR_WORDS are what take_error reads and clears
+    FLAG_LU_INFO = 0,            // lu: 0, the column of an exactly zero pivot, or < 0 when the pivot exchange timed out
+    FLAG_CHOL_INFO = 1,          // chol_upper: 0 or the column at which the matrix stopped being positive definite
+    FLAG_WAIT_PHASE = 2, FLAG_WAIT_SLOT = 3, FLAG_WAIT_EPOCH = 4, FLAG_WAIT_WHO = 5,   // what a timed-out LU workgroup waited for
+    FLAG_ERROR_WORDS = 8, FLAG_SVD_ROTATIONS = 8,     // (behind the error words:) the Jacobi SVD's rotation counter
+    FLAG_CHOLQR = 9,             // the verdict of a CholeskyQR attempt: non-zero = this tier does not apply (read_flag)
+    FLAG_COUNT = 16
+  };
+  int32_t* flags_ = nullptr;
   double* scal_ = nullptr;
   void* pin_power_ = nullptr; // pinned: the verdict of a power step (lowrank_power_step)
   DevBuf ws_gemm_, ws_lu_, ws_split_, ws_qr_, ws_svd_, ws_blas2_, ws_lus_, ws_svdf_, ws_qr_hh_;
+  DevBuf* const ws_all_[9] = {&ws_gemm_, &ws_lu_, &ws_split_, &ws_qr_, &ws_svd_, &ws_blas2_, &ws_lus_, &ws_svdf_, &ws_qr_hh_};
   std::mutex mu_;
   std::vector<DevBuf> sizes_;
   std::vector<DevBuf> pool_;
@@ -1798,474 +1739,9 @@ class HipBackend : public Backend {
   const double* lus_part_Y_ = nullptr;
 };
 
-// ---- RCCL, bound lazily so a single-GPU user never needs librccl to resolve -----------------
-struct RcclApi {
-  void* h = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*ReduceScatter)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-  ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*GroupStart)() = nullptr;
-  ncclResult_t (*GroupEnd)() = nullptr;
-};
-RcclApi& rccl() {
-  static RcclApi api;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    api.h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!api.h) api.h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!api.h) return;
-    api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.h, "ncclGetUniqueId");
-    api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.h, "ncclCommInitRank");
-    api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.h, "ncclCommDestroy");
-    api.AllReduce = (decltype(api.AllReduce))dlsym(api.h, "ncclAllReduce");
-    api.AllGather = (decltype(api.AllGather))dlsym(api.h, "ncclAllGather");
-    api.ReduceScatter = (decltype(api.ReduceScatter))dlsym(api.h, "ncclReduceScatter");
-    api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.h, "ncclGetErrorString");
-    api.Send = (decltype(api.Send))dlsym(api.h, "ncclSend");
-    api.Recv = (decltype(api.Recv))dlsym(api.h, "ncclRecv");
-    api.GroupStart = (decltype(api.GroupStart))dlsym(api.h, "ncclGroupStart");
-    api.GroupEnd = (decltype(api.GroupEnd))dlsym(api.h, "ncclGroupEnd");
-  });
-  if (!api.h || !api.GetUniqueId || !api.CommInitRank || !api.AllReduce || !api.AllGather || !api.ReduceScatter)
-    throw Error(GSI_ERR_RCCL, "librccl.so could not be loaded: multi-GPU needs RCCL");
-  return api;
-}
-#define RCCL_CHECK(expr)                                                                       \
-  do {                                                                                         \
-    ncclResult_t _r = (expr);                                                                  \
-    if (_r != ncclSuccess)                                                                     \
-      throw Error(GSI_ERR_RCCL, std::string(#expr) + ": " +                                     \
-                                    (rccl().GetErrorString ? rccl().GetErrorString(_r) : "rccl error")); \
-  } while (0)
-
-// all[g] = rank g's buffer as this process addresses it: its own pointer, an IPC mapping of everybody else's
-static bool ipc_open_all(int nranks, int rank, void* mine, const hipIpcMemHandle_t* hs, void** all, std::vector<void*>* opened) {
-  bool ok = true;
-  for (int g = 0; g < nranks && ok; ++g) {
-    if (g == rank) { all[g] = mine; continue; }
-    void* p = nullptr;
-    if (hipIpcOpenMemHandle(&p, hs[g], hipIpcMemLazyEnablePeerAccess) != hipSuccess) { (void)hipGetLastError(); ok = false; p = nullptr; }
-    all[g] = p;
-    if (p && opened) opened->push_back(p);
-  }
-  return ok;
-}
-
-class RcclComm : public Comm {
- public:
-  RcclComm(HipBackend* be, int n, int r, const void* id) : be_(be) {
-    nranks = n;
-    rank = r;
-    static_assert(sizeof(ncclUniqueId) <= GSI_UNIQUE_ID_BYTES, "unique id does not fit the ABI slot");
-    ncclUniqueId uid;
-    std::memcpy(&uid, id, sizeof(uid));
-    be_->bind();
-    RCCL_CHECK(rccl().CommInitRank(&comm_, n, uid, r));
-  }
-  ~RcclComm() override {
-    if (comm_) {
-      be_->bind();
-      hipStreamSynchronize(be_->stream());
-      rccl().CommDestroy(comm_);
-    }
-  }
-  void do_allreduce_sum(double* buf, size_t count) override {
-    be_->bind();
-    RCCL_CHECK(rccl().AllReduce(buf, buf, count, ncclDouble, ncclSum, comm_, be_->stream()));
-  }
-  void do_allgather(const double* send, double* recv, size_t count) override {
-    be_->bind();
-    RCCL_CHECK(rccl().AllGather(send, recv, count, ncclDouble, comm_, be_->stream()));
-  }
-  void do_reduce_scatter_sum(const double* send, double* recv, size_t count) override {
-    be_->bind();
-    RCCL_CHECK(rccl().ReduceScatter(send, recv, count, ncclDouble, ncclSum, comm_, be_->stream()));
-  }
-  // point-to-point xGMI: every pair of GPUs has a direct link, so the grouped sends / receives use all 7 links at once
-  void do_alltoall(const double* send, double* recv, size_t count) override {
-    be_->bind();
-    RcclApi& r = rccl();
-    if (!r.Send || !r.Recv || !r.GroupStart || !r.GroupEnd) throw Error(GSI_ERR_RCCL, "librccl has no ncclSend / ncclRecv");
-    RCCL_CHECK(r.GroupStart());
-    for (int g = 0; g < nranks; ++g) {
-      RCCL_CHECK(r.Send(send + (size_t)g * count, count, ncclDouble, g, comm_, be_->stream()));
-      RCCL_CHECK(r.Recv(recv + (size_t)g * count, count, ncclDouble, g, comm_, be_->stream()));
-    }
-    RCCL_CHECK(r.GroupEnd());
-  }
-  // one process per GPU: IPC handles travel through an all-gather, every rank maps its peers' buffers.  The mapping of
-  // OTHER processes' buffers cannot be exercised on the one-GPU build box (RCCL refuses two ranks on one device), which is
-  // why pipeline.cpp:lus_mr_selftest makes the path prove itself on the machine it runs on before it is used.
-  bool share_pointers(void* mine, size_t bytes, void** all) override {
-    (void)bytes;
-    static const bool on = !(getenv("GSI_LU_PEER") != nullptr && getenv("GSI_LU_PEER")[0] == '0');   // GSI_LU_PEER=0: never
-    if (!on) return false;
-    be_->bind();
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-    hipIpcMemHandle_t h;
-    std::memset(&h, 0, sizeof(h));
-    bool ok = (hipIpcGetMemHandle(&h, mine) == hipSuccess);     // a failure here must not skip the collective below
-    if (!ok) (void)hipGetLastError();
-    double* send = be_->alloc(8);
-    double* recv = be_->alloc((size_t)8 * nranks);
-    HIP_CHECK(hipMemcpyAsync(send, &h, 64, hipMemcpyHostToDevice, be_->stream()));
-    allgather(send, recv, 8);
-    std::vector<hipIpcMemHandle_t> hs((size_t)nranks);
-    HIP_CHECK(hipMemcpyAsync(hs.data(), recv, (size_t)64 * nranks, hipMemcpyDeviceToHost, be_->stream()));
-    HIP_CHECK(hipStreamSynchronize(be_->stream()));
-    be_->release(send);
-    be_->release(recv);
-    if (ok) ok = ipc_open_all(nranks, rank, mine, hs.data(), all, nullptr);
-    return ok;      // false on this rank alone is fine: the ranks all-reduce their answers before anyone relies on the buffers
-  }
-
- private:
-  HipBackend* be_;
-  ncclComm_t comm_ = nullptr;
-};
-
-// ---- ranks as THREADS of one process (GSI_LOCAL_COMM=1): one context per thread, on different GPUs with peer access or --
-//      what makes the whole multi-rank pipeline runnable on a one-GPU box -- on the SAME GPU.  RCCL refuses two ranks on one
-//      device; this communicator needs nothing but HIP: every rank's device pointers are valid in every thread of the
-//      process, so a collective is "synchronise my stream, meet at a host barrier, read the peers' buffers with kernels /
-//      copies on my own stream, synchronise, meet again".  Rank-ordered sums (deterministic).  Not a performance path.
-struct LocalGroup {
-  int nranks = 0;
-  std::mutex mu;
-  std::condition_variable cv;
-  int arrived = 0;
-  uint64_t generation = 0;
-  std::vector<const double*> src;
-  std::vector<int> device;               // device of every rank's context
-  void barrier() {
-    std::unique_lock<std::mutex> lk(mu);
-    const uint64_t gen = generation;
-    if (++arrived == nranks) { arrived = 0; ++generation; cv.notify_all(); return; }
-    // a rank thread that died (an exception on its way out, a caller that returned) must not hang the others for ever
-    static const int timeout_s = getenv("GSI_SHM_TIMEOUT_S") ? std::max(1, atoi(getenv("GSI_SHM_TIMEOUT_S"))) : 300;
-    if (!cv.wait_for(lk, std::chrono::seconds(timeout_s), [&] { return generation != gen; })) {
-      --arrived;
-      throw Error(GSI_ERR_RCCL, "local communicator: a rank did not reach the barrier (GSI_SHM_TIMEOUT_S)");
-    }
-  }
-};
-static std::mutex g_local_mu;
-static std::map<std::string, std::shared_ptr<LocalGroup>> g_local_groups;
-
-class LocalComm : public Comm {
- public:
-  LocalComm(HipBackend* be, int n, int r, const void* id) : be_(be) {
-    nranks = n;
-    rank = r;
-    const std::string key((const char*)id, 32);
-    std::unique_lock<std::mutex> lk(g_local_mu);
-    auto& grp = g_local_groups[key];
-    if (!grp) { grp = std::make_shared<LocalGroup>(); grp->nranks = n; grp->src.assign((size_t)n, nullptr); grp->device.assign((size_t)n, -1); }
-    if (grp->nranks != n) throw Error(GSI_ERR_ARG, "local communicator: ranks disagree on nranks");
-    grp->device[(size_t)r] = be_->device();
-    grp_ = grp;
-    lk.unlock();
-    grp_->barrier();                      // like ncclCommInitRank: returns when every rank has joined (and registered its device)
-    for (int d = 0, cnt = 0; hipGetDeviceCount(&cnt) == hipSuccess && d < cnt; ++d)      // best effort: peers on other GPUs
-      if (d != be_->device()) { (void)hipDeviceEnablePeerAccess(d, 0); (void)hipGetLastError(); }
-  }
-  // publish my buffer, wait until every rank has published and its producing work is complete
-  void publish(const double* p) {
-    be_->bind();
-    HIP_CHECK(hipStreamSynchronize(be_->stream()));
-    { std::lock_guard<std::mutex> g(grp_->mu); grp_->src[(size_t)rank] = p; }
-    grp_->barrier();
-  }
-  void finish() {                       // my reads of the peers' buffers are done; nobody may reuse a buffer before all are
-    HIP_CHECK(hipStreamSynchronize(be_->stream()));
-    grp_->barrier();
-  }
-  void do_allreduce_sum(double* buf, size_t count) override {
-    publish(buf);
-    double* tmp = be_->alloc(count);
-    hipStream_t st = be_->stream();
-    HIP_CHECK(hipMemcpyAsync(tmp, grp_->src[0], count * sizeof(double), hipMemcpyDeviceToDevice, st));
-    for (int g = 1; g < nranks; ++g) hipk::axpy(st, (int64_t)count, 1.0, grp_->src[(size_t)g], tmp);
-    finish();                           // every rank has summed the ORIGINAL buffers
-    HIP_CHECK(hipMemcpyAsync(buf, tmp, count * sizeof(double), hipMemcpyDeviceToDevice, st));
-    be_->release(tmp);
-  }
-  void do_allgather(const double* send, double* recv, size_t count) override {
-    publish(send);
-    for (int g = 0; g < nranks; ++g)
-      HIP_CHECK(hipMemcpyAsync(recv + (size_t)g * count, grp_->src[(size_t)g], count * sizeof(double), hipMemcpyDeviceToDevice,
-                               be_->stream()));
-    finish();
-  }
-  void do_reduce_scatter_sum(const double* send, double* recv, size_t count) override {
-    publish(send);
-    hipStream_t st = be_->stream();
-    HIP_CHECK(hipMemcpyAsync(recv, grp_->src[0] + (size_t)rank * count, count * sizeof(double), hipMemcpyDeviceToDevice, st));
-    for (int g = 1; g < nranks; ++g) hipk::axpy(st, (int64_t)count, 1.0, grp_->src[(size_t)g] + (size_t)rank * count, recv);
-    finish();
-  }
-  void do_alltoall(const double* send, double* recv, size_t count) override {
-    publish(send);
-    for (int g = 0; g < nranks; ++g)
-      HIP_CHECK(hipMemcpyAsync(recv + (size_t)g * count, grp_->src[(size_t)g] + (size_t)rank * count, count * sizeof(double),
-                               hipMemcpyDeviceToDevice, be_->stream()));
-    finish();
-  }
-  bool share_pointers(void* mine, size_t, void** all) override {       // one process: the pointers themselves
-    publish((const double*)mine);
-    for (int g = 0; g < nranks; ++g) all[g] = const_cast<double*>(grp_->src[(size_t)g]);
-    finish();
-    return true;
-  }
-  void host_barrier() override { grp_->barrier(); }
-  int ranks_on_my_device() override {
-    std::lock_guard<std::mutex> g(grp_->mu);
-    int c = 0;
-    for (int q = 0; q < nranks; ++q) c += (grp_->device[(size_t)q] == be_->device()) ? 1 : 0;
-    return std::max(c, 1);
-  }
-
- private:
-  HipBackend* be_;
-  std::shared_ptr<LocalGroup> grp_;
-};
-static bool local_comm_requested() { return getenv("GSI_LOCAL_COMM") != nullptr; }
-
-// ---- ranks as PROCESSES of one node without RCCL (GSI_SHM_COMM=1): host barriers and IPC handles in a POSIX shared-memory
-//      block, payloads through one staging buffer per rank that every peer maps with hipIpcOpenMemHandle.  Two uses: the
-//      cross-PROCESS half of the multi-rank code (IPC mapping of the pivot-exchange buffer, persistent kernels of different
-//      processes polling each other's memory) runs on a one-GPU box, where RCCL refuses two ranks on one device; and a node
-//      without librccl still has a communicator.  Rank-ordered sums (deterministic, identical on every rank).  A collective
-//      is: copy into my staging buffer, synchronise, barrier, read the peers' staging buffers, synchronise, barrier -- not
-//      a performance path.
-struct ShmBlock {
-  std::atomic<uint32_t> arrived;
-  std::atomic<uint32_t> generation;
-  uint32_t ok[16];
-  char busid[16][32];                    // PCI bus id of every rank's device
-  hipIpcMemHandle_t stage[16];
-  hipIpcMemHandle_t shared[16];
-};
-static_assert(std::atomic<uint32_t>::is_always_lock_free, "process-shared atomics");
-
-class ShmComm : public Comm {
- public:
-  ShmComm(HipBackend* be, int n, int r, const void* id) : be_(be) {
-    nranks = n;
-    rank = r;
-    if (n < 1 || n > 16) throw Error(GSI_ERR_ARG, "shared-memory communicator: 1..16 ranks");
-    char name[96];
-    std::memcpy(name, (const char*)id + 16, 95);
-    name[95] = 0;
-    if (std::memcmp(id, "gsi-shm-comm", 12) != 0 || name[0] != '/')
-      throw Error(GSI_ERR_ARG, "shared-memory communicator: the id does not come from gsi_comm_unique_id() under GSI_SHM_COMM");
-    if (const char* e = getenv("GSI_SHM_TIMEOUT_S")) timeout_s_ = std::max(1, atoi(e));
-    const int fd = shm_open(name, O_CREAT | O_RDWR, 0600);      // whoever comes first creates it: zero-filled = initial state
-    if (fd < 0) throw Error(GSI_ERR_RCCL, std::string("shm_open(") + name + ") failed");
-    if (ftruncate(fd, sizeof(ShmBlock)) != 0) { close(fd); throw Error(GSI_ERR_RCCL, "shared-memory communicator: ftruncate failed"); }
-    void* m = mmap(nullptr, sizeof(ShmBlock), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (m == MAP_FAILED) throw Error(GSI_ERR_RCCL, "shared-memory communicator: mmap failed");
-    blk_ = (ShmBlock*)m;
-    be_->bind();
-    size_t mb = 64;
-    if (const char* e = getenv("GSI_SHM_STAGE_MB")) mb = (size_t)std::max(1, atoi(e));
-    cap_ = mb * 1024 * 1024 / sizeof(double);
-    bool ok = (hipMalloc((void**)&stage_, cap_ * sizeof(double)) == hipSuccess);
-    hipIpcMemHandle_t h;
-    std::memset(&h, 0, sizeof(h));
-    if (ok) ok = (hipIpcGetMemHandle(&h, stage_) == hipSuccess);
-    if (!ok) (void)hipGetLastError();
-    blk_->stage[rank] = h;
-    blk_->ok[rank] = ok ? 1u : 0u;
-    std::memset(blk_->busid[rank], 0, sizeof(blk_->busid[rank]));
-    if (hipDeviceGetPCIBusId(blk_->busid[rank], (int)sizeof(blk_->busid[rank]) - 1, be_->device()) != hipSuccess) {
-      (void)hipGetLastError();
-      snprintf(blk_->busid[rank], sizeof(blk_->busid[rank]), "device-%d", be_->device());
-    }
-    barrier();
-    if (rank == 0) shm_unlink(name);                            // every rank has it mapped: nothing is left behind in /dev/shm
-    for (int g = 0; g < nranks; ++g) ok = ok && blk_->ok[g] != 0;
-    std::vector<hipIpcMemHandle_t> hs(blk_->stage, blk_->stage + nranks);
-    void* all[16] = {nullptr};
-    if (ok) ok = ipc_open_all(nranks, rank, stage_, hs.data(), all, &opened_);
-    blk_->ok[rank] = ok ? 1u : 0u;
-    barrier();
-    for (int g = 0; g < nranks; ++g) ok = ok && blk_->ok[g] != 0;
-    barrier();                                                  // ok[] is reused by share_pointers
-    if (!ok) { cleanup(); throw Error(GSI_ERR_RCCL, "shared-memory communicator: the ranks' staging buffers could not be mapped (hipIpc)"); }
-    for (int g = 0; g < nranks; ++g) peer_[g] = (const double*)all[g];
-    for (int g = 0; g < nranks; ++g) same_device_ += (std::strncmp(blk_->busid[g], blk_->busid[rank], sizeof(blk_->busid[g])) == 0) ? 1 : 0;
-  }
-  int ranks_on_my_device() override { return std::max(same_device_, 1); }
-  ~ShmComm() override {
-    be_->bind();
-    (void)hipStreamSynchronize(be_->stream());
-    cleanup();
-  }
-  void do_allreduce_sum(double* buf, size_t count) override {
-    hipStream_t st = be_->stream();
-    for (size_t off = 0; off < count || off == 0; off += cap_) {
-      const size_t c = std::min(cap_, count - off);
-      stage_in(buf + off, c);
-      if (c) HIP_CHECK(hipMemcpyAsync(buf + off, peer_[0], c * sizeof(double), hipMemcpyDeviceToDevice, st));
-      for (int g = 1; g < nranks && c; ++g) hipk::axpy(st, (int64_t)c, 1.0, peer_[g], buf + off);
-      done_reading();
-      if (count == 0) break;
-    }
-  }
-  void do_allgather(const double* send, double* recv, size_t count) override {
-    for (size_t off = 0; off < count || off == 0; off += cap_) {
-      const size_t c = std::min(cap_, count - off);
-      stage_in(send + off, c);
-      for (int g = 0; g < nranks && c; ++g)
-        HIP_CHECK(hipMemcpyAsync(recv + (size_t)g * count + off, peer_[g], c * sizeof(double), hipMemcpyDeviceToDevice, be_->stream()));
-      done_reading();
-      if (count == 0) break;
-    }
-  }
-  // blocks of `count` doubles per destination: the staging buffer holds nranks segments of one chunk
-  void do_reduce_scatter_sum(const double* send, double* recv, size_t count) override {
-    hipStream_t st = be_->stream();
-    const size_t cc = std::max<size_t>(cap_ / (size_t)nranks, 1);
-    for (size_t off = 0; off < count || off == 0; off += cc) {
-      const size_t c = std::min(cc, count - off);
-      stage_blocks(send, count, off, c, cc);
-      if (c) HIP_CHECK(hipMemcpyAsync(recv + off, peer_[0] + (size_t)rank * cc, c * sizeof(double), hipMemcpyDeviceToDevice, st));
-      for (int g = 1; g < nranks && c; ++g) hipk::axpy(st, (int64_t)c, 1.0, peer_[g] + (size_t)rank * cc, recv + off);
-      done_reading();
-      if (count == 0) break;
-    }
-  }
-  void do_alltoall(const double* send, double* recv, size_t count) override {
-    const size_t cc = std::max<size_t>(cap_ / (size_t)nranks, 1);
-    for (size_t off = 0; off < count || off == 0; off += cc) {
-      const size_t c = std::min(cc, count - off);
-      stage_blocks(send, count, off, c, cc);
-      for (int g = 0; g < nranks && c; ++g)
-        HIP_CHECK(hipMemcpyAsync(recv + (size_t)g * count + off, peer_[g] + (size_t)rank * cc, c * sizeof(double), hipMemcpyDeviceToDevice,
-                                 be_->stream()));
-      done_reading();
-      if (count == 0) break;
-    }
-  }
-  // the buffers are mapped exactly as RcclComm maps them (the handles travel through the shared block instead of an all-gather)
-  bool share_pointers(void* mine, size_t, void** all) override {
-    static const bool on = !(getenv("GSI_LU_PEER") != nullptr && getenv("GSI_LU_PEER")[0] == '0');
-    if (!on) return false;
-    be_->bind();
-    hipIpcMemHandle_t h;
-    std::memset(&h, 0, sizeof(h));
-    bool ok = (hipIpcGetMemHandle(&h, mine) == hipSuccess);
-    if (!ok) (void)hipGetLastError();
-    blk_->shared[rank] = h;
-    blk_->ok[rank] = ok ? 1u : 0u;
-    barrier();
-    for (int g = 0; g < nranks; ++g) ok = ok && blk_->ok[g] != 0;
-    std::vector<hipIpcMemHandle_t> hs(blk_->shared, blk_->shared + nranks);
-    barrier();                                                  // everybody has read the slots
-    if (ok) ok = ipc_open_all(nranks, rank, mine, hs.data(), all, &opened_);
-    return ok;      // as with RCCL: the caller all-reduces the ranks' answers before anyone relies on the buffers
-  }
-
- private:
-  void barrier() {
-    const uint32_t gen = blk_->generation.load(std::memory_order_acquire);
-    if (blk_->arrived.fetch_add(1, std::memory_order_acq_rel) + 1 == (uint32_t)nranks) {
-      blk_->arrived.store(0, std::memory_order_relaxed);
-      blk_->generation.fetch_add(1, std::memory_order_release);
-      return;
-    }
-    timespec t0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (uint64_t it = 0; blk_->generation.load(std::memory_order_acquire) == gen; ++it) {
-      if (it < 4096) continue;
-      sched_yield();
-      if ((it & 1023) == 0) {
-        timespec t1;
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        if (t1.tv_sec - t0.tv_sec > timeout_s_)
-          throw Error(GSI_ERR_RCCL, "shared-memory communicator: a rank did not reach the barrier (GSI_SHM_TIMEOUT_S)");
-      }
-    }
-  }
-  void stage_in(const double* src, size_t c) {                 // my chunk -> my staging buffer, visible to every rank
-    be_->bind();
-    if (c) HIP_CHECK(hipMemcpyAsync(stage_, src, c * sizeof(double), hipMemcpyDeviceToDevice, be_->stream()));
-    HIP_CHECK(hipStreamSynchronize(be_->stream()));
-    barrier();
-  }
-  void stage_blocks(const double* send, size_t count, size_t off, size_t c, size_t cc) {
-    be_->bind();
-    for (int g = 0; g < nranks && c; ++g)
-      HIP_CHECK(hipMemcpyAsync(stage_ + (size_t)g * cc, send + (size_t)g * count + off, c * sizeof(double), hipMemcpyDeviceToDevice,
-                               be_->stream()));
-    HIP_CHECK(hipStreamSynchronize(be_->stream()));
-    barrier();
-  }
-  void done_reading() {                                        // nobody overwrites a staging buffer a peer still reads
-    HIP_CHECK(hipStreamSynchronize(be_->stream()));
-    barrier();
-  }
-  void cleanup() {
-    for (void* p : opened_) (void)hipIpcCloseMemHandle(p);
-    opened_.clear();
-    (void)hipGetLastError();
-    if (blk_) {
-      try { if (!std::uncaught_exceptions()) { const int t = timeout_s_; timeout_s_ = std::min(t, 10); barrier(); timeout_s_ = t; } } catch (...) {}
-      munmap(blk_, sizeof(ShmBlock));
-      blk_ = nullptr;
-    }
-    if (stage_) { (void)hipFree(stage_); stage_ = nullptr; }
-  }
-
-  HipBackend* be_;
-  ShmBlock* blk_ = nullptr;
-  double* stage_ = nullptr;
-  size_t cap_ = 0;
-  const double* peer_[16] = {nullptr};
-  std::vector<void*> opened_;
-  int same_device_ = 0;
-  int timeout_s_ = 300;
-};
-static bool shm_comm_requested() { return getenv("GSI_SHM_COMM") != nullptr; }
-
 }  // namespace
 
 Backend* make_backend(int device_id) { return new HipBackend(device_id); }
-Comm* make_comm(Backend* be, int nranks, int rank, const void* unique_id) {
-  if (local_comm_requested()) return new LocalComm(static_cast<HipBackend*>(be), nranks, rank, unique_id);
-  if (shm_comm_requested()) return new ShmComm(static_cast<HipBackend*>(be), nranks, rank, unique_id);
-  return new RcclComm(static_cast<HipBackend*>(be), nranks, rank, unique_id);
-}
-void comm_unique_id(void* id_out) {
-  std::memset(id_out, 0, GSI_UNIQUE_ID_BYTES);
-  if (local_comm_requested()) {         // ranks are threads of this process: any id that is unique within it
-    static std::atomic<uint64_t> counter{1};
-    const uint64_t c = counter.fetch_add(1);
-    std::memcpy(id_out, "gsi-local-comm", 14);
-    std::memcpy((char*)id_out + 16, &c, sizeof(c));
-    return;
-  }
-  if (shm_comm_requested()) {           // ranks are processes of this node: the name of a shared-memory block nobody has used
-    static std::atomic<uint64_t> counter{1};
-    timespec t;
-    clock_gettime(CLOCK_REALTIME, &t);
-    std::memcpy(id_out, "gsi-shm-comm", 12);
-    snprintf((char*)id_out + 16, 96, "/gsi-shm-%ld-%llu-%lld%09ld", (long)getpid(), (unsigned long long)counter.fetch_add(1),
-             (long long)t.tv_sec, (long)t.tv_nsec);
-    return;
-  }
-  ncclUniqueId uid;
-  RCCL_CHECK(rccl().GetUniqueId(&uid));
-  std::memcpy(id_out, &uid, sizeof(uid));
-}
 const char* backend_name() { return "hip-gfx950"; }
 
 }  // namespace gsi

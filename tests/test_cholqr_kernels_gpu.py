@@ -216,6 +216,49 @@ def test_svd_tall_fused_first_tier(gsi, m, l):
     assert np.abs(V.T @ V - np.eye(l)).max() < 1e-12
 
 
+# ---- the hint the three first-tier callers share (hip_backend.hip, cholqr2_try / skip_tier1_by_height_) -----------------
+def test_first_tier_hint_shared_by_callers(gsi):
+    """A failed first tier in svd_tall_fused leaves the hint qr_thinQ reads: eight factorizations of that height start at
+    the second tier (the svd_tall's own generic QR is the first of them), the ninth probes from the top again; a panel of
+    another height never sees the hint."""
+    m, l = 4096, 128
+    rng = np.random.default_rng(m + 7 * l)
+    U, _ = np.linalg.qr(rng.standard_normal((m, l)))
+    V, _ = np.linalg.qr(rng.standard_normal((l, l)))
+    W = np.asfortranarray((U * np.logspace(0, -10, l)) @ V.T)         # cond 1e10, as test_scholqr3_second_tier
+    Y, Y1 = int_panel(m, l), int_panel(m + 1, l)
+    (R_ref, bound), (R1_ref, bound1) = reference(Y), reference(Y1)
+    c = gsi.Context(0)
+    try:
+        def counted(f):
+            before = c.counters()
+            out = f()
+            return out, tier_deltas(before, c.counters())
+
+        def other_height():
+            (Q, R), d = counted(lambda: gsi.qr_thinQ(Y1, return_R=True, ctx=c))
+            assert d == {"cholqr2": 1, "scholqr3": 0, "householder": 0}, d
+            check_qr(Y1, Q, R, R1_ref, bound1)
+
+        other_height()                                                        # before the hint exists
+        (S, Vs), d = counted(lambda: gsi.svd_tall(W, ctx=c))
+        assert d == {"cholqr2": 0, "scholqr3": 1, "householder": 0}, d        # fused path declined, generic QR one tier down
+        Sref = np.linalg.svd(W, compute_uv=False)
+        assert np.all(np.diff(S) <= 0)
+        assert np.abs(S - Sref).max() <= 1e-12 * Sref[0]
+        assert np.abs(Vs.T @ Vs - np.eye(l)).max() < 1e-12
+        for i in range(8):
+            (Q, R), d = counted(lambda: gsi.qr_thinQ(Y, return_R=True, ctx=c))
+            tier = "scholqr3" if i < 7 else "cholqr2"
+            assert d == {k: int(k == tier) for k in TIERS}, (i, d)
+            check_qr(Y, Q, R, R_ref, bound)
+            if i == 3:
+                other_height()                                                # while the hint is live
+        other_height()                                                        # after it has run out
+    finally:
+        c.close()
+
+
 # ---- the same answer with a dedicated kernel switched off (the switches are read once per process: one child each) ---
 def child_main(shapes):
     """Runs in a child process: every shape through qr_thinQ on a fresh context, the first-tier checks, one line out."""
