@@ -96,6 +96,12 @@ SIGNATURES = {
     "gsi_pcga_params_basis": (C.c_int, [c_vp, c_vp, c_dp, c_dp, C.c_double, c_dp]),
     "gsi_pcga_update_basis": (C.c_int, [c_vp, c_vp, c_dp, C.c_double, c_dp, c_i64, c_dp, c_dp]),
     "gsi_basis_download_col": (C.c_int, [c_vp, c_vp, c_i64, c_dp]),
+    "gsi_fwd_linear_create": (C.c_int, [c_vp, C.POINTER(c_vp), c_i64, c_i64, C.POINTER(c_i64), C.POINTER(c_i64), c_dp, c_dp,
+                                        C.c_int]),
+    "gsi_fwd_destroy": (C.c_int, [c_vp]),
+    "gsi_fwd_info": (C.c_int, [c_vp, C.POINTER(c_i64), c_i64]),
+    "gsi_fwd_apply": (C.c_int, [c_vp, c_vp, c_dp, c_i64, c_i64, c_dp, c_i64]),
+    "gsi_pcga_forward_basis": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp, C.c_double, c_dp]),
     "gsi_ctx_profile": (C.c_int, [c_vp, C.c_int]),
     "gsi_ctx_phase_reset": (C.c_int, [c_vp]),
     "gsi_ctx_phase_times": (C.c_int, [c_vp, c_dp, C.POINTER(c_i64)]),

@@ -41,6 +41,11 @@ struct gsi_basis {
   gsi_mat* owner = nullptr;   // precision 64: the matrix whose buffer Z64 points into, kept alive by this basis
 };
 
+struct gsi_fwd {
+  gsi_ctx* ctx;
+  FwdModel m;
+};
+
 namespace {
 thread_local std::string g_last_error;
 
@@ -1250,6 +1255,53 @@ int gsi_basis_download_col(gsi_ctx* ctx, const gsi_basis* basis, int64_t col, do
     be->fill_zero(Xd.p, (size_t)n);
     be->basis_gemv_f32(basis->buf32.p, n, basis->K, wd.p, 0.0, Xd.p, sd.p);
     be->download2d(host, n, sd.p, n, n, 1);
+  });
+}
+
+// ---- sparse forward models ------------------------------------------------------
+int gsi_fwd_linear_create(gsi_ctx* ctx, gsi_fwd** fwd, int64_t nobs, int64_t n, const int64_t* rowptr, const int64_t* colidx,
+                          const double* vals, const double* weights, int link) {
+  return guarded([&] {
+    REQUIRE(ctx && fwd, "gsi_fwd_linear_create: ctx / fwd is NULL");
+    *fwd = nullptr;
+    std::unique_ptr<gsi_fwd> f(new gsi_fwd());
+    f->ctx = ctx;
+    fwd_create(ctx->c, f->m, nobs, n, rowptr, colidx, vals, weights, link);
+    *fwd = f.release();
+  });
+}
+int gsi_fwd_destroy(gsi_fwd* fwd) {
+  return guarded([&] { delete fwd; });
+}
+int gsi_fwd_info(const gsi_fwd* fwd, int64_t* out, int64_t n_out) {
+  return guarded([&] {
+    REQUIRE(fwd && out && n_out >= 0, "bad argument");
+    const FwdModel& m = fwd->m;
+    const int64_t v[8] = {m.nobs, m.n, m.nnz, m.plan.nseg(), m.plan.nsplit, m.last_form, m.host_products, m.products};
+    for (int64_t i = 0; i < n_out; ++i) out[i] = i < 8 ? v[i] : 0;
+  });
+}
+int gsi_fwd_apply(gsi_ctx* ctx, const gsi_fwd* fwd, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo) {
+  return guarded([&] {
+    REQUIRE(ctx && fwd && P && out, "NULL argument");
+    REQUIRE(fwd->ctx == ctx, "gsi_fwd_apply: the forward model belongs to another context");
+    REQUIRE(ncols >= 1 && ldp >= fwd->m.n && ldo >= fwd->m.nobs, "gsi_fwd_apply: bad ncols / leading dimension");
+    fwd_apply(ctx->c, fwd->m, P, ldp, ncols, out, ldo);
+    check_async_errors(ctx->c);
+  });
+}
+int gsi_pcga_forward_basis(gsi_ctx* ctx, const gsi_basis* basis, const gsi_fwd* fwd, const double* s, const double* X,
+                           double delta, double* results_out) {
+  return guarded([&] {
+    REQUIRE(ctx && basis && fwd && s && X && results_out, "NULL argument");
+    REQUIRE(basis->ctx == ctx, "gsi_pcga_forward_basis: the basis belongs to another context");
+    REQUIRE(fwd->ctx == ctx, "gsi_pcga_forward_basis: the forward model belongs to another context");
+    if (fwd->m.n != basis->n)
+      throw Error(GSI_ERR_ARG, "gsi_pcga_forward_basis: the forward model has n = " + std::to_string(fwd->m.n) +
+                                   ", the basis n = " + std::to_string(basis->n));
+    const void* Z = basis->precision == 64 ? (const void*)basis->Z64 : (const void*)basis->buf32.p;
+    fwd_forward_basis(ctx->c, fwd->m, Z, basis->precision, basis->K, s, X, delta, results_out);
+    check_async_errors(ctx->c);
   });
 }
 

@@ -23,6 +23,36 @@ enum Phase : int {
   PH_COMM = 6, PH_OTHER = 7, PH_COMM_WAIT = 8, PH_COUNT = 9
 };
 
+// One batch of products of a sparse forward model (gsi_fwd), every pointer in backend memory:
+//   dst[r + c ldo] = sum over the nonzeros t of row r of vals[t] g(w[j_t] p(j_t, c)),   g = identity (link 0) or exp (link 1)
+// for the columns p(:, c) of
+//   plain:   the ncols = K columns of Z (fp64, ld ldz) as they are;
+//   else:    the K + 3 columns of paramstorun (direct.jl:39-45), never formed: s + delta Z[:, c] (c < K; Z in fp64 or fp32,
+//            widened per element), s + delta X, s + delta s, s.
+// The rows are cut into segments (fwd_plan.hpp): segment k = nonzeros [segptr[k], segptr[k + 1]), row r = segments
+// [rowseg[r], rowseg[r + 1]).  rowseg == null: no row is split, segment r is row r.  Otherwise `partial` (nseg x ncols)
+// takes one sum per segment and the rows' sums are added from it in segment order.
+struct FwdProduct {
+  int64_t nobs = 0, n = 0, nnz = 0, nseg = 0, maxlen = 0;
+  const int64_t* segptr = nullptr;
+  const int64_t* rowseg = nullptr;
+  const int32_t* colidx = nullptr;
+  const double* vals = nullptr;
+  const double* w = nullptr;          // n weights, or null for ones
+  int link = 0;
+  const void* Z = nullptr;
+  int zbits = 64;                     // 64: Z is double; 32: float
+  int64_t ldz = 0, K = 0;
+  bool plain = false;
+  const double* s = nullptr;
+  const double* X = nullptr;
+  double delta = 0.0;
+  double* out = nullptr;              // nobs x ncols, ld ldo
+  int64_t ldo = 0;
+  double* partial = nullptr;          // nseg x ncols when rowseg != null
+  int64_t ncols() const { return plain ? K : K + 3; }
+};
+
 // All pointers below are "backend memory" (HBM for the HIP backend), column-major fp64.
 class Backend {
  public:
@@ -346,6 +376,11 @@ class Backend {
   // y (n) = beta * X + Z32 (n x K, fp32) * w (K): fp64 accumulation   (direct.jl:59-65 with the basis in fp32)
   virtual void basis_gemv_f32(const void* Z32, int64_t n, int64_t K, const double* w, double beta, const double* X,
                               double* y) = 0;
+
+  // ---- sparse forward model on the device (FwdProduct above) ----
+  // Returns the form that computed a.out -- 1: one lane per output, 2: one wave per segment -- or 0: "not mine", nothing
+  // ran, and pipeline.cpp forms the batch with pcga_params and multiplies on the host.
+  virtual int fwd_products(const FwdProduct& a) { (void)a; return 0; }
 
   // error flags raised asynchronously by kernels (zero pivot, non-posdef); checked and
   // cleared by the pipeline at the end of each entry point. Returns GSI_* code or 0.

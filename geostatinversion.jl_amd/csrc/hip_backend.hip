@@ -1457,6 +1457,29 @@ class HipBackend : public HipDevice {
     hipk::basis_gemv_f32(st_, (const float*)Z32, n, K, w, beta, X, y);
     check_launch("basis_gemv_f32");
   }
+  // The sparse forward model (pcga_forward.hip).  The form follows the mean segment length: FWD_WAVE_MIN nonzeros and more
+  // go one wave per segment, shorter ones one lane per output (the crossover of the sweep in profiles/pcga_forward.json:
+  // 4096 rays of 16 cells run 0.65 ms in the wave form against 0.83 ms, rays of 4 cells 0.66 against 0.62;
+  // DESIGN.md section 4.7b).  GSI_FWD_FORM=lane|wave, read at every call, overrides.
+  static constexpr int64_t FWD_WAVE_MIN = 16;
+  int fwd_products(const FwdProduct& a) override {
+    bind();
+    int form = (a.nseg > 0 && a.nnz / a.nseg >= FWD_WAVE_MIN) ? 2 : 1;
+    if (const char* e = getenv("GSI_FWD_FORM")) {
+      const std::string f(e);
+      if (f == "lane") form = 1;
+      else if (f == "wave") form = 2;
+      else if (!f.empty()) throw Error(GSI_ERR_ARG, "GSI_FWD_FORM must be lane or wave, not '" + f + "'");
+    }
+    if (form == 1) hipk::fwd_lane(st_, a);
+    else hipk::fwd_wave(st_, a);
+    check_launch(form == 1 ? "fwd_lane" : "fwd_wave");
+    if (a.rowseg) {
+      hipk::fwd_reduce(st_, a);
+      check_launch("fwd_reduce");
+    }
+    return form;
+  }
 
   // The persistent leaf kernel spins on records of ALL its workgroups: the grid must fit the chip at this kernel's
   // occupancy (registers, LDS, waves).  Queried once per instantiation; a panel that does not fit takes the streamed leaves.

@@ -6,6 +6,8 @@
 #include <cstddef>
 #include "pointcov.hpp"
 
+namespace gsi { struct FwdProduct; }   // backend.hpp
+
 namespace gsi { namespace hipk {
 
 // The > 64 KB dynamic-LDS opt-in (hipFuncSetAttribute) is a property of a kernel ON ONE DEVICE.  A process may
@@ -290,5 +292,12 @@ void basis_gemv_f32(hipStream_t st, const float* Z, int64_t n, int64_t K, const 
 void extract_upper(hipStream_t st, const double* Y, int64_t ld, int64_t l, double* R);
 void pcga_params(hipStream_t st, const double* Z, int64_t n, int64_t K, const double* s, const double* X,
                  double delta, double* out);
+
+// ---- pcga_forward.hip: the sparse forward model (backend.hpp: FwdProduct) ----
+// one lane per (segment, column) output, for short rows; one wave per segment and group of 16 columns, for long ones
+void fwd_lane(hipStream_t st, const FwdProduct& a);
+void fwd_wave(hipStream_t st, const FwdProduct& a);
+// out[r, c] = the partial sums of row r's segments, added in segment order (only when rows were split)
+void fwd_reduce(hipStream_t st, const FwdProduct& a);
 
 }}  // namespace gsi::hipk

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include "../../include/gsi_hip.h"
 
@@ -1188,6 +1189,155 @@ int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double 
   }
   if (j > 0) be->download2d(Q_host, m, Qfull.p, m, m, j);   // return Qfull[:, 1:j]           :47
   return j;
+}
+
+// ---- the sparse forward model (gsi_fwd) ------------------------------------------------------
+namespace {
+template <class T>
+void upload_as_doubles(Backend* be, Buf& dst, const T* src, size_t count) {
+  // integers travel as the bytes of a double-typed allocation: every transfer is a byte copy
+  const size_t nd = (count * sizeof(T) + sizeof(double) - 1) / sizeof(double);
+  std::vector<double> stage(std::max<size_t>(nd, 1), 0.0);
+  if (count) std::memcpy(stage.data(), src, count * sizeof(T));
+  dst = Buf(be, stage.size());
+  be->upload2d(dst.p, (int64_t)stage.size(), stage.data(), (int64_t)stage.size(), (int64_t)stage.size(), 1);
+}
+
+bool fwd_host_forced() {
+  const char* e = getenv("GSI_FWD_HOST");
+  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
+}
+
+// out[:, c] = h(P[:, c]) on the host, nonzeros of a row in storage order
+void fwd_host_csr(const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo) {
+  const bool has_w = !F.w.empty();
+  for (int64_t c = 0; c < ncols; ++c) {
+    const double* p = P + c * ldp;
+    for (int64_t r = 0; r < F.nobs; ++r) {
+      double acc = 0.0;
+      for (int64_t t = F.rowptr[(size_t)r]; t < F.rowptr[(size_t)r + 1]; ++t) {
+        const int64_t j = F.colidx[(size_t)t];
+        double a = (has_w ? F.w[(size_t)j] : 1.0) * p[j];
+        if (F.link) a = std::exp(a);
+        acc += F.vals[(size_t)t] * a;
+      }
+      out[r + c * ldo] = acc;
+    }
+  }
+}
+
+void fwd_fill(const FwdModel& F, FwdProduct& a) {
+  a.nobs = F.nobs; a.n = F.n; a.nnz = F.nnz; a.nseg = F.plan.nseg(); a.maxlen = F.plan.maxlen;
+  a.segptr = reinterpret_cast<const int64_t*>(F.d_segptr.p);
+  a.rowseg = F.plan.nsplit ? reinterpret_cast<const int64_t*>(F.d_rowseg.p) : nullptr;
+  a.colidx = reinterpret_cast<const int32_t*>(F.d_colidx.p);
+  a.vals = F.d_vals.p;
+  a.w = F.w.empty() ? nullptr : F.d_w.p;
+  a.link = F.link;
+}
+}  // namespace
+
+void fwd_create(Context& c, FwdModel& F, int64_t nobs, int64_t n, const int64_t* rowptr, const int64_t* colidx,
+                const double* vals, const double* weights, int link) {
+  auto bad = [](const std::string& m) { throw Error(GSI_ERR_ARG, "gsi_fwd_linear_create: " + m); };
+  if (nobs < 1 || n < 1) bad("nobs = " + std::to_string(nobs) + ", n = " + std::to_string(n) + ": both must be at least 1");
+  if (n >= ((int64_t)1 << 31)) bad("n = " + std::to_string(n) + " does not fit the 32-bit column indices (n < 2^31)");
+  if (link != 0 && link != 1) bad("link = " + std::to_string(link) + " (0: identity, 1: exp)");
+  if (!rowptr) bad("rowptr is NULL");
+  if (rowptr[0] != 0) bad("rowptr[0] = " + std::to_string(rowptr[0]) + ", not 0 (offsets are 0-based)");
+  for (int64_t r = 0; r < nobs; ++r)
+    if (rowptr[r + 1] < rowptr[r])
+      bad("rowptr decreases at row " + std::to_string(r) + ": " + std::to_string(rowptr[r]) + " -> " +
+          std::to_string(rowptr[r + 1]));
+  const int64_t nnz = rowptr[nobs];
+  if (nnz > 0 && (!colidx || !vals)) bad("colidx / vals is NULL");
+  for (int64_t r = 0; r < nobs; ++r)
+    for (int64_t t = rowptr[r]; t < rowptr[r + 1]; ++t)
+      if (colidx[t] < 0 || colidx[t] >= n)
+        bad("entry " + std::to_string(t) + " (row " + std::to_string(r) + ") has column index " + std::to_string(colidx[t]) +
+            " outside [0, " + std::to_string(n) + ")");
+  int64_t limit = FWD_DEFAULT_SEG_LIMIT;
+  if (const char* e = getenv("GSI_FWD_SEG")) {
+    if (e[0] != '\0') {
+      limit = atoll(e);
+      if (limit < 1) bad(std::string("GSI_FWD_SEG = '") + e + "': a segment holds at least one nonzero");
+    }
+  }
+  F.ctx = &c; F.nobs = nobs; F.n = n; F.nnz = nnz; F.link = link; F.seg_limit = limit;
+  F.rowptr.assign(rowptr, rowptr + nobs + 1);
+  F.colidx.resize((size_t)nnz);
+  for (int64_t t = 0; t < nnz; ++t) F.colidx[(size_t)t] = (int32_t)colidx[t];
+  F.vals.assign(vals, vals + nnz);
+  if (weights) F.w.assign(weights, weights + n);
+  F.plan = fwd_plan(rowptr, nobs, limit);
+  Backend* be = c.be.get();
+  upload_as_doubles(be, F.d_segptr, F.plan.segptr.data(), F.plan.segptr.size());
+  if (F.plan.nsplit) upload_as_doubles(be, F.d_rowseg, F.plan.rowseg.data(), F.plan.rowseg.size());
+  upload_as_doubles(be, F.d_colidx, F.colidx.data(), F.colidx.size());
+  F.d_vals = Buf(be, std::max<size_t>((size_t)nnz, 1));
+  if (nnz) be->upload2d(F.d_vals.p, nnz, F.vals.data(), nnz, nnz, 1);
+  if (weights) {
+    F.d_w = Buf(be, (size_t)n);
+    be->upload2d(F.d_w.p, n, F.w.data(), n, n, 1);
+  }
+}
+
+void fwd_forward_basis(Context& c, const FwdModel& F, const void* Z, int zbits, int64_t K, const double* s, const double* X,
+                       double delta, double* out) {
+  Backend* be = c.be.get();
+  const int64_t n = F.n, nobs = F.nobs, nc = K + 3;
+  F.products += 1;
+  Buf sv(be, (size_t)n), Xv(be, (size_t)n);
+  be->upload2d(sv.p, n, s, n, n, 1);
+  be->upload2d(Xv.p, n, X, n, n, 1);
+  if (!fwd_host_forced()) {
+    Buf O(be, (size_t)nobs * nc), part;
+    if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * nc);
+    FwdProduct a;
+    fwd_fill(F, a);
+    a.Z = Z; a.zbits = zbits; a.ldz = n; a.K = K; a.plain = false;
+    a.s = sv.p; a.X = Xv.p; a.delta = delta;
+    a.out = O.p; a.ldo = nobs; a.partial = part.p;
+    const int form = be->fwd_products(a);
+    if (form != 0) {
+      be->download2d(out, nobs, O.p, nobs, nobs, nc);
+      F.last_form = form;
+      return;
+    }
+  }
+  // the host path: the batch as direct.jl:39-45 forms it, downloaded, and the model applied column by column
+  Buf Pd(be, (size_t)n * nc);
+  if (zbits == 32) be->pcga_params_f32(Z, n, K, sv.p, Xv.p, delta, Pd.p);
+  else be->pcga_params((const double*)Z, n, K, sv.p, Xv.p, delta, Pd.p);
+  std::vector<double> P((size_t)n * nc);
+  be->download2d(P.data(), n, Pd.p, n, n, nc);
+  fwd_host_csr(F, P.data(), n, nc, out, nobs);
+  F.host_products += 1;
+  F.last_form = 3;
+}
+
+void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo) {
+  Backend* be = c.be.get();
+  const int64_t n = F.n, nobs = F.nobs;
+  F.products += 1;
+  if (!fwd_host_forced()) {
+    Buf Pd(be, (size_t)n * ncols), O(be, (size_t)nobs * ncols), part;
+    if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * ncols);
+    be->upload2d(Pd.p, n, P, ldp, n, ncols);
+    FwdProduct a;
+    fwd_fill(F, a);
+    a.Z = Pd.p; a.zbits = 64; a.ldz = n; a.K = ncols; a.plain = true;
+    a.out = O.p; a.ldo = nobs; a.partial = part.p;
+    const int form = be->fwd_products(a);
+    if (form != 0) {
+      be->download2d(out, ldo, O.p, nobs, nobs, ncols);
+      F.last_form = form;
+      return;
+    }
+  }
+  fwd_host_csr(F, P, ldp, ncols, out, ldo);
+  F.host_products += 1;
+  F.last_form = 3;
 }
 
 }  // namespace gsi

@@ -7,6 +7,7 @@
 #include <memory>
 #include <vector>
 #include "backend.hpp"
+#include "fwd_plan.hpp"
 
 namespace gsi {
 
@@ -141,6 +142,33 @@ struct PcgaLowRank {
   bool r_diag = false;
   void mul(const double* x, double* y) const;   // x, y: nobs + 1
 };
+// A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
+// vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
+// double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.
+struct FwdModel {
+  Context* ctx = nullptr;
+  int64_t nobs = 0, n = 0, nnz = 0, seg_limit = 0;
+  int link = 0;
+  std::vector<int64_t> rowptr;
+  std::vector<int32_t> colidx;
+  std::vector<double> vals, w;     // w empty: ones
+  FwdPlan plan;
+  Buf d_segptr, d_rowseg, d_colidx, d_vals, d_w;
+  // what ran (gsi_fwd_info): form of the last product (0 none yet, 1 lane-per-output, 2 wave-per-segment, 3 host path),
+  // products that took the host path, products in total
+  mutable int64_t last_form = 0, host_products = 0, products = 0;
+};
+enum : int64_t { FWD_DEFAULT_SEG_LIMIT = 16384 };   // nonzeros per segment, from the sweep of DESIGN.md section 4.7b; GSI_FWD_SEG overrides
+// Validates (GSI_ERR_ARG naming the offending row or entry, before anything is allocated), plans and uploads.
+void fwd_create(Context& c, FwdModel& F, int64_t nobs, int64_t n, const int64_t* rowptr, const int64_t* colidx,
+                const double* vals, const double* weights, int link);
+// out (host, nobs x (K + 3), ld nobs): column c = h(column c of paramstorun) for the basis Z (backend memory, n x K, ld n,
+// fp64 or fp32 by zbits), s and X on the host.  The backend's kernels, or -- when it declines or GSI_FWD_HOST=1 --
+// pcga_params, a download and a host CSR loop.
+void fwd_forward_basis(Context& c, const FwdModel& F, const void* Z, int zbits, int64_t K, const double* s, const double* X,
+                       double delta, double* out);
+// out (host, nobs x ncols, ld ldo): column c = h(P[:, c]) for the host matrix P (n x ncols, ld ldp)
+void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo);
 // throws Error if a kernel raised an asynchronous flag
 void check_async_errors(Context& c);
 

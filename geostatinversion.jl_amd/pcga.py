@@ -2,7 +2,9 @@
 (src/lsqr.jl) and `rga` (src/GeostatInversion.jl:101-103).  The forward model is user code and runs
 on the host exactly as the reference's `pmap` does; the package's own n-sized algebra (the
 perturbation batch and the update s = X*beta + sum xis[i]*dot(eta_i, xi_bar)) and pcgalsqr's
-saddle-point LSQR (PCGALowRankMatrix products, IterativeSolvers defaults) run on the GPU."""
+saddle-point LSQR (PCGALowRankMatrix products, IterativeSolvers defaults) run on the GPU.  One class of forward models
+can run there too: a `LinearForwardModel` (sparse H, optional weights and exp link) beside a `DeviceBasis` is evaluated on
+the device straight from the resident basis, and the perturbation batch is never formed."""
 import numpy as np
 
 from . import _lib as L
@@ -68,6 +70,21 @@ class DeviceBasis:
                                                    X.ctypes.data_as(L.c_dp), float(delta), L.dptr(out)), self.ctx.lib)
         return out
 
+    def forward(self, fwd, s, X, delta):
+        """The nobs x (K+3) results of direct.jl:38-46 / lsqr.jl:36-51 for a `LinearForwardModel`: column c is the model on
+        column c of `params(s, X, delta)`, computed on the device from s, X and the resident basis -- the batch is never formed
+        and only the results cross the host link (`gsi_pcga_forward_basis`)."""
+        if fwd.ctx is not self.ctx:
+            raise ValueError("the forward model and the basis live on different contexts")
+        out = np.empty((fwd.nobs, self.K + 3), order="F")
+        s = np.ascontiguousarray(s, dtype=np.float64)
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if s.shape != (self.n,) or X.shape != (self.n,):
+            raise ValueError("s and X must have the basis' n entries")
+        L.check(self.ctx.lib.gsi_pcga_forward_basis(self.ctx.h, self.h, fwd.h, s.ctypes.data_as(L.c_dp),
+                                                    X.ctypes.data_as(L.c_dp), float(delta), L.dptr(out)), self.ctx.lib)
+        return out
+
     def update(self, X, beta_bar, etas, xi_bar):
         E = np.asfortranarray(np.stack(etas, axis=1))
         X = np.ascontiguousarray(X, dtype=np.float64)
@@ -120,6 +137,110 @@ class _Basis:
         return out
 
 
+class LinearForwardModel:
+    """A forward model that lives on the device: h(s)[r] = sum_t H.data[t] g(w[j_t] s[j_t]) over the nonzeros of row r of the
+    sparse matrix H (nobs x n), with g the identity (`link="identity"`) or exp (`link="exp"`) and w the optional `weights`.
+    Point samples, block averages, ray integrals, the reference's `p .* x` test model (test/testrpcga.jl:110-112), and the
+    same on exp(s).  H: anything with `.tocsr()` giving `.indptr`, `.indices`, `.data`, `.shape`, or the tuple
+    `(indptr, indices, data, shape)`.
+
+    Passed to `pcgadirect` / `pcgalsqr` / `rga` with a `DeviceBasis` on the same context, the K+3 model runs of an iteration
+    are computed on the device from the resident basis (`DeviceBasis.forward`).  It is also an ordinary callable on a host
+    vector, `fwd(s)`, so every other path takes it as it takes any forward model."""
+
+    LINKS = {"identity": 0, "exp": 1, 0: 0, 1: 1}
+    FORMS = ["none", "lane", "wave", "host"]
+
+    def __init__(self, H, weights=None, link="identity", ctx=None):
+        import ctypes as C
+        if isinstance(H, tuple):
+            indptr, indices, data, shape = H
+        else:
+            H = H.tocsr()
+            indptr, indices, data, shape = H.indptr, H.indices, H.data, H.shape
+        if link not in self.LINKS:
+            raise ValueError("link must be 'identity' or 'exp'")
+        self.ctx = ctx or default_context()
+        nobs, n = int(shape[0]), int(shape[1])
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int64)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if indptr.shape != (max(nobs, 0) + 1,):
+            raise ValueError("indptr must have nobs + 1 entries")
+        if indices.shape != data.shape or indices.ndim != 1 or indices.size < int(indptr[-1]):
+            raise ValueError("indices and data must be 1-D, of equal length, and hold indptr[-1] entries")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (n,):
+                raise ValueError("weights must have n entries")
+        p64 = C.POINTER(C.c_int64)
+        h = C.c_void_p()
+        L.check(self.ctx.lib.gsi_fwd_linear_create(self.ctx.h, C.byref(h), nobs, n, indptr.ctypes.data_as(p64),
+                                                   indices.ctypes.data_as(p64), L.dptr(data),
+                                                   L.dptr(w) if w is not None else None, self.LINKS[link]), self.ctx.lib)
+        self.h = h
+        self.nobs, self.n, self.nnz = nobs, n, int(indptr[-1])
+        self.link = "exp" if self.LINKS[link] else "identity"
+        self.ctx._children.append(self)   # destroyed before the context is
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.gsi_fwd_destroy(self.h)
+            self.h = None
+            if self in self.ctx._children:
+                self.ctx._children.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """`gsi_fwd_info`: [nobs, n, nnz, segments, split rows, form of the last product (0 none yet, 1 lane-per-output,
+        2 wave-per-segment, 3 host path), products on the host path, products in total]."""
+        import ctypes as C
+        out = (C.c_int64 * 8)()
+        L.check(self.ctx.lib.gsi_fwd_info(self.h, out, 8), self.ctx.lib)
+        return [int(v) for v in out]
+
+    def apply(self, P):
+        """h of every column of the host matrix P (n x ncols): nobs x ncols."""
+        P = L.fmat(P, "P")
+        if P.shape[0] != self.n:
+            raise ValueError("P must have n rows")
+        out = np.empty((self.nobs, P.shape[1]), order="F")
+        L.check(self.ctx.lib.gsi_fwd_apply(self.ctx.h, self.h, L.dptr(P), self.n, P.shape[1], L.dptr(out), self.nobs),
+                self.ctx.lib)
+        return out
+
+    def __call__(self, s):
+        return self.apply(np.asarray(s, dtype=np.float64).reshape(-1, 1))[:, 0]
+
+
+class _ReducedForwardModel:
+    """S @ fwd(.) for `rga` (GeostatInversion.jl:101-103) with the model kept on the device: S multiplies the small results."""
+
+    def __init__(self, fwd, S):
+        self.fwd, self.S = fwd, S
+
+    def __call__(self, x):
+        return self.S @ self.fwd(x)
+
+
+def _device_forward(forwardmodel, basis):
+    """(model, S or None) if this iteration head can run on the device, else None."""
+    S = None
+    if isinstance(forwardmodel, _ReducedForwardModel):
+        forwardmodel, S = forwardmodel.fwd, forwardmodel.S
+    if not isinstance(forwardmodel, LinearForwardModel) or not isinstance(basis, DeviceBasis):
+        return None
+    if getattr(basis, "gather", None) is not None or forwardmodel.ctx is not basis.ctx:
+        return None
+    return forwardmodel, S
+
+
 def _as_basis(xis, ctx):
     return xis if isinstance(xis, DeviceBasis) else _Basis(xis, ctx)
 
@@ -127,6 +248,15 @@ def _as_basis(xis, ctx):
 def _iteration_head(forwardmodel, basis, s, X, delta):
     """direct.jl:38-46 / lsqr.jl:36-51."""
     K = basis.K
+    dev = _device_forward(forwardmodel, basis)
+    if dev is not None:                                               # a sparse model beside a resident basis: no batch
+        R = basis.forward(dev[0], s, X, delta)
+        if dev[1] is not None:
+            R = dev[1] @ R
+        results = [np.ascontiguousarray(R[:, i]) for i in range(K + 3)]
+        hs = results[K + 2]
+        etas = [(results[i] - hs) / delta for i in range(K)]
+        return etas, (results[K] - hs) / delta, (results[K + 1] - hs) / delta, hs
     P = basis.params(s, X, delta)                                     # paramstorun
     if getattr(basis, "gather", None) is not None:                    # row-sharded basis: whole vectors for the forward model
         P = basis.gather(P)
@@ -198,7 +328,9 @@ def rga(forwardmodel, s0, X, xis, R, y, S, *, maxiters=5, delta=SQRT_EPS, xtol=1
     """`rga(...; pcgafunc=pcgadirect, callback)`  (GeostatInversion.jl:101-103)."""
     S = np.asarray(S, dtype=np.float64)
     Rd = R.toarray() if hasattr(R, "toarray") else np.asarray(R, dtype=np.float64)
-    return pcgafunc(lambda x: S @ forwardmodel(x), s0, X, xis, S @ Rd @ S.T, S @ np.asarray(y, dtype=np.float64),
+    reduced = _ReducedForwardModel(forwardmodel, S) if isinstance(forwardmodel, LinearForwardModel) \
+        else (lambda x: S @ forwardmodel(x))
+    return pcgafunc(reduced, s0, X, xis, S @ Rd @ S.T, S @ np.asarray(y, dtype=np.float64),
                     maxiters=maxiters, delta=delta, xtol=xtol, callback=callback)
 
 

@@ -21,6 +21,7 @@ import Random
 import Libdl
 import LinearAlgebra
 import Distributed
+import SparseArrays
 
 const libgsi = get(ENV, "GSI_HIP_LIB", joinpath(@__DIR__, "..", "geostatinversion.jl_amd", "libgsi_hip.so"))
 
@@ -442,6 +443,65 @@ function update(b::DeviceBasis, X::Vector{Float64}, beta_bar::Float64, etas::Mat
 	return s
 end
 
+"A forward model resident on the device: h(s)[r] = sum_t H[r, j_t] g(w[j_t] s[j_t]) over the nonzeros of row r of the sparse H
+(nobs x n), g = identity (`link = :identity`) or exp (`link = :exp`), w = `weights` (nothing: ones).  With a `DeviceBasis` the
+`pcgadirect` / `pcgalsqr` / `rga` methods below compute the K+3 model runs of an iteration (direct.jl:38-46, lsqr.jl:36-51) on
+the device from the resident basis; `fwd(s)` applies it to a host vector like any forward model.  The library wants CSR: it is
+the CSC of the transpose, with the 1-based indices made 0-based."
+mutable struct LinearForwardModel
+	h::Ptr{Cvoid}
+	c::Context
+	nobs::Int
+	n::Int
+	function LinearForwardModel(H::SparseArrays.SparseMatrixCSC; weights::Union{Nothing,Vector{Float64}}=nothing,
+			link::Symbol=:identity, c::Context=ctx())
+		Ht = SparseArrays.sparse(transpose(H))                                          # n x nobs: column r = row r of H
+		rowptr = Vector{Int64}(Ht.colptr .- 1)
+		colidx = Vector{Int64}(Ht.rowval .- 1)
+		vals = Vector{Float64}(Ht.nzval)
+		w = weights === nothing ? C_NULL : weights                                      # NULL: ones
+		r = Ref{Ptr{Cvoid}}(C_NULL)
+		check(ccall((:gsi_fwd_linear_create, libgsi), Cint,
+			(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Cint),
+			c.h, r, size(H, 1), size(H, 2), rowptr, colidx, vals, w, link == :exp ? 1 : 0))
+		f = new(r[], c, size(H, 1), size(H, 2))
+		finalizer(f) do x
+			x.h != C_NULL && ccall((:gsi_fwd_destroy, libgsi), Cint, (Ptr{Cvoid},), x.h)
+			x.h = C_NULL
+		end
+		return f
+	end
+end
+"[nobs, n, nnz, segments, split rows, form of the last product, products on the host path, products in total]"
+function info(f::LinearForwardModel)
+	out = zeros(Int64, 8)
+	check(ccall((:gsi_fwd_info, libgsi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64), f.h, out, length(out)))
+	return out
+end
+"h of every column of the host matrix P (n x ncols)"
+function apply(f::LinearForwardModel, P::Matrix{Float64})
+	out = Matrix{Float64}(undef, f.nobs, size(P, 2))
+	check(ccall((:gsi_fwd_apply, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64),
+		f.c.h, f.h, P, stride(P, 2), size(P, 2), out, f.nobs))
+	return out
+end
+(f::LinearForwardModel)(s::Vector{Float64}) = vec(apply(f, reshape(s, :, 1)))
+"The nobs x (K+3) results of direct.jl:38-46 / lsqr.jl:36-51, computed on the device; the batch is never formed."
+function forward(b::DeviceBasis, f::LinearForwardModel, s::Vector{Float64}, X::Vector{Float64}, delta::Float64)
+	out = Matrix{Float64}(undef, f.nobs, b.K + 3)
+	check(ccall((:gsi_pcga_forward_basis, libgsi), Cint,
+		(Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}),
+		b.Z.c.h, b.h, f.h, s, X, delta, out))
+	return out
+end
+"S * fwd(.) for `rga` with the model kept on the device: S multiplies the small results"
+struct ReducedForwardModel
+	fwd::LinearForwardModel
+	S::Matrix{Float64}
+end
+(r::ReducedForwardModel)(s::Vector{Float64}) = r.S * r.fwd(s)
+const DeviceForwardModel = Union{LinearForwardModel, ReducedForwardModel}
+
 "`PCGALowRankMatrix(etas, HX, R)` (lowrank.jl:32-36) resident on the device; `A * x` and `lsqr(A, b)` run there."
 mutable struct PCGALowRankMatrix
 	h::Ptr{Cvoid}
@@ -648,7 +708,17 @@ function iterationhead(forwardmodel::Function, s::Vector, X::Vector, xis::Device
 	return etas, HX, Hs, hs
 end
 
-function pcgadirect(forwardmodel::Function, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector;
+function headfromresults(results::Matrix{Float64}, K::Int, delta)
+	hs = results[:, K + 3]
+	etas = (results[:, 1:K] .- hs) ./ delta
+	return etas, (results[:, K + 1] - hs) / delta, (results[:, K + 2] - hs) / delta, hs
+end
+iterationhead(f::LinearForwardModel, s::Vector, X::Vector, xis::DeviceBasis, delta) =
+	headfromresults(forward(xis, f, s, X, delta), length(xis), delta)
+iterationhead(r::ReducedForwardModel, s::Vector, X::Vector, xis::DeviceBasis, delta) =
+	headfromresults(r.S * forward(xis, r.fwd, s, X, delta), length(xis), delta)
+
+function pcgadirect(forwardmodel::Union{Function, DeviceForwardModel}, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector;
 		maxiters::Int=5, delta::Float64=sqrt(eps(Float64)), xtol::Float64=1e-6, callback=(s, obs_cal)->nothing)
 	s, converged, iters = s0, false, 0
 	while !converged && iters < maxiters
@@ -664,7 +734,7 @@ function pcgadirect(forwardmodel::Function, s0::Vector, X::Vector, xis::DeviceBa
 	return s
 end
 
-function pcgalsqr(forwardmodel::Function, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector;
+function pcgalsqr(forwardmodel::Union{Function, DeviceForwardModel}, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector;
 		maxiters::Int=5, delta::Float64=sqrt(eps(Float64)), xtol::Float64=1e-6)
 	s, converged, iters = s0, false, 0
 	while !converged && iters < maxiters
@@ -683,5 +753,7 @@ const pcga = pcgadirect                                                         
 "`rga(forwardmodel, s0, X, xis, R, y, S; ...)`  (GeostatInversion.jl:101-103)"
 rga(forwardmodel::Function, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector, S; pcgafunc=pcgadirect, kwargs...) =
 	pcgafunc(x->S * forwardmodel(x), s0, X, xis, S * R * S', S * y; kwargs...)
+rga(forwardmodel::LinearForwardModel, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector, S; pcgafunc=pcgadirect, kwargs...) =
+	pcgafunc(ReducedForwardModel(forwardmodel, Matrix{Float64}(S)), s0, X, xis, S * R * S', S * y; kwargs...)
 
 end # module
