@@ -91,6 +91,8 @@ SIGNATURES = {
     "gsi_pcgamat_destroy": (C.c_int, [c_vp]),
     "gsi_pcgamat_mul": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),
     "gsi_pcgamat_lsqr": (C.c_int, [c_vp, c_vp, c_dp, c_dp, C.POINTER(c_i64)]),
+    "gsi_pcgamat_solve": (C.c_int, [c_vp, c_vp, c_dp, c_dp, C.POINTER(c_i64)]),
+    "gsi_chol_lower": (C.c_int, [c_vp, c_dp, c_i64, c_i64, c_dp, C.POINTER(c_i64)]),
     "gsi_basis_create": (C.c_int, [c_vp, C.POINTER(c_vp), c_vp, c_i64, C.c_int]),
     "gsi_basis_destroy": (C.c_int, [c_vp]),
     "gsi_pcga_params_basis": (C.c_int, [c_vp, c_vp, c_dp, c_dp, C.c_double, c_dp]),

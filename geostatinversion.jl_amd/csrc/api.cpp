@@ -1172,6 +1172,36 @@ int gsi_pcgamat_lsqr(gsi_ctx* ctx, const gsi_pcgamat* mat, const double* b, doub
   });
 }
 
+int gsi_pcgamat_solve(gsi_ctx* ctx, const gsi_pcgamat* mat, const double* b, double* x_out, int64_t* info_out) {
+  int64_t info2[2] = {0, 0};
+  const int st = guarded([&] {
+    REQUIRE(ctx && mat && b && x_out, "gsi_pcgamat_solve: NULL argument");
+    REQUIRE(mat->ctx == ctx, "gsi_pcgamat_solve: the matrix belongs to another context");
+    if (mat->A.nobs > 32768)
+      throw Error(GSI_ERR_ARG, "gsi_pcgamat_solve: nobs = " + std::to_string(mat->A.nobs) +
+                                   " is beyond the 32768 the direct solver takes (its workspace is (nobs + 2) x nobs doubles)");
+    mat->A.solve(b, x_out, info2);
+    check_async_errors(ctx->c);
+  });
+  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
+  return st;
+}
+
+int gsi_chol_lower(gsi_ctx* ctx, const double* A, int64_t n, int64_t lda, double* L_out, int64_t* info_out) {
+  int64_t info2[2] = {0, 0};
+  const int st = guarded([&] {
+    REQUIRE(ctx && A && L_out, "gsi_chol_lower: NULL argument");
+    REQUIRE(n >= 1 && lda >= n, "gsi_chol_lower: need n >= 1 and lda >= n");
+    REQUIRE(n <= 32768, "gsi_chol_lower: n is beyond 32768");
+    chol_lower_host_matrix(ctx->c, A, n, lda, L_out, info2);
+    check_async_errors(ctx->c);
+    if (info2[0] != 0)
+      throw Error(GSI_ERR_NOT_POSDEF, "PosDefException: matrix is not positive definite; Cholesky failed at " + std::to_string(info2[0]));
+  });
+  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
+  return st;
+}
+
 // ---- xi-basis objects ------------------------------------------------------------------
 int gsi_basis_create(gsi_ctx* ctx, gsi_basis** basis, const gsi_mat* Z, int64_t K, int precision) {
   return guarded([&] {

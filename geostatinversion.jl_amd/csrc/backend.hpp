@@ -382,6 +382,20 @@ class Backend {
   // ran, and pipeline.cpp forms the batch with pcga_params and multiplies on the host.
   virtual int fwd_products(const FwdProduct& a) { (void)a; return 0; }
 
+  // ---- pcgadirect's saddle-point system by Cholesky ----
+  // The m x n trapezoid A (m >= n, ld; lower triangle of the top n x n read) <- [L; (L^-1 B')'] in place, B = rows n .. m-1.
+  // Returns 0, the 1-based column at which the matrix stopped being positive definite (A is then partly factored), or
+  // -1: "not mine", nothing ran, and pipeline.cpp factors on the host (saddle_host.hpp).
+  virtual int64_t chol_lower(double* A, int64_t m, int64_t n, int64_t ld) { (void)A; (void)m; (void)n; (void)ld; return -1; }
+  // x (nobs + 1) = [(E E' + R) HX; HX' 0] \ b with E nobs x K (ld nobs), R dense (ld nobs) or its diagonal: formation,
+  // chol_lower with HX' and b1' carried as rows nobs, nobs + 1, beta = (w'v - b2) / (w'w), xi = L^-T (v - beta w).
+  // Returns as chol_lower does; *singular <- w'w is zero or beta is not finite (x is then not meaningful).
+  virtual int64_t saddle_solve(const double* E, int64_t nobs, int64_t K, const double* HX, const double* R, bool r_diag,
+                               const double* b, double* x, bool* singular) {
+    (void)E; (void)nobs; (void)K; (void)HX; (void)R; (void)r_diag; (void)b; (void)x; (void)singular;
+    return -1;
+  }
+
   // error flags raised asynchronously by kernels (zero pivot, non-posdef); checked and
   // cleared by the pipeline at the end of each entry point. Returns GSI_* code or 0.
   virtual int take_error(std::string* msg) = 0;

@@ -1481,6 +1481,44 @@ class HipBackend : public HipDevice {
     return form;
   }
 
+  // The blocked Cholesky and the saddle-point solve (chol_saddle.hip).  The pivot flag has a slot
+  // of its own behind the error words: the caller gets the column as a return value, not through take_error.
+  int64_t chol_lower(double* A, int64_t m, int64_t n, int64_t ld) override {
+    bind();
+    if (n < 1 || m < n || ld < m || n >= ((int64_t)1 << 31)) throw Error(GSI_ERR_ARG, "chol_lower: need 1 <= n <= m <= ld, n < 2^31");
+    HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOL_LOWER, 0, sizeof(int32_t), st_));
+    hipk::cs_chol_lower(st_, A, m, n, ld, flags_ + FLAG_CHOL_LOWER);
+    check_launch("chol_lower");
+    return read_flag(FLAG_CHOL_LOWER);
+  }
+  int64_t saddle_solve(const double* E, int64_t nobs, int64_t K, const double* HX, const double* R, bool r_diag, const double* b,
+                       double* x, bool* singular) override {
+    bind();
+    const int64_t ld = nobs + 2;
+    Scratch W(this, (size_t)ld * nobs);
+    HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOL_LOWER, 0, sizeof(int32_t), st_));
+    phase_begin(PH_SMALL_GEMM);                              // (profiling: the formation counts as a small product ...
+    hipk::cs_syrk_lower(st_, W.p, ld, nobs, nobs, E, nobs, K, 1.0, 0.0, R, nobs, r_diag ? 2 : 1, flags_ + FLAG_CHOL_LOWER);
+    hipk::cs_set_rows(st_, W.p, ld, nobs, HX, b);
+    phase_end(PH_SMALL_GEMM);
+    phase_begin(PH_OTHER);                                   // ... the factorization as "other": tools/pcga_direct_bench.py)
+    hipk::cs_chol_lower(st_, W.p, nobs + 2, nobs, ld, flags_ + FLAG_CHOL_LOWER);
+    phase_end(PH_OTHER);
+    check_launch("saddle_solve: factorization");
+    const int64_t col = read_flag(FLAG_CHOL_LOWER);
+    *singular = false;
+    if (col != 0) return col;
+    hipk::cs_schur(st_, W.p, ld, nobs, b, x, scal_);
+    grow(ws_blas2_, sizeof(double) * hipk::cs_backsolve_workspace_doubles());
+    hipk::cs_backsolve(st_, W.p, nobs, ld, x, (double*)ws_blas2_.p);
+    check_launch("saddle_solve: substitution");
+    double out3[3] = {0.0, 0.0, 0.0};
+    HIP_CHECK(hipMemcpyAsync(out3, scal_, sizeof(out3), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    *singular = (out3[2] == 0.0);
+    return 0;
+  }
+
   // The persistent leaf kernel spins on records of ALL its workgroups: the grid must fit the chip at this kernel's
   // occupancy (registers, LDS, waves).  Queried once per instantiation; a panel that does not fit takes the streamed leaves.
   bool lu2_fits(int bs, int rpt, int grid) {
@@ -1719,6 +1757,7 @@ class HipBackend : public HipDevice {
     FLAG_WAIT_PHASE = 2, FLAG_WAIT_SLOT = 3, FLAG_WAIT_EPOCH = 4, FLAG_WAIT_WHO = 5,   // what a timed-out LU workgroup waited for
     FLAG_ERROR_WORDS = 8, FLAG_SVD_ROTATIONS = 8,     // (behind the error words:) the Jacobi SVD's rotation counter
     FLAG_CHOLQR = 9,             // the verdict of a CholeskyQR attempt: non-zero = this tier does not apply (read_flag)
+    FLAG_CHOL_LOWER = 10,        // chol_lower / saddle_solve: 0 or the 1-based column of the first bad pivot (read_flag)
     FLAG_COUNT = 16
   };
   int32_t* flags_ = nullptr;

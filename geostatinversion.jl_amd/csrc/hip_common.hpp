@@ -300,4 +300,17 @@ void fwd_wave(hipStream_t st, const FwdProduct& a);
 // out[r, c] = the partial sums of row r's segments, added in segment order (only when rows were split)
 void fwd_reduce(hipStream_t st, const FwdProduct& a);
 
+// ---- chol_saddle.hip: blocked Cholesky and the saddle-point solve of pcgadirect ----
+// C (mc x nc lower trapezoid, mc >= nc) = beta C + alpha P P' (+ R): rmode 0 none, 1 dense lower (ld ldr), 2 diagonal entries.
+// P: mc x k.  flag: the factorization's pivot flag -- nothing is done once it is non-zero.
+void cs_syrk_lower(hipStream_t st, double* C, int64_t ldc, int64_t mc, int64_t nc, const double* P, int64_t ldp, int64_t k,
+                   double alpha, double beta, const double* R, int64_t ldr, int rmode, const int32_t* flag);
+// the m x n trapezoid A (m >= n, lower triangle of the top n x n read) <- [L; (L^-1 B')'] in place, blocks of 64 columns;
+// *flag (zero on entry) <- the 1-based column of the first pivot that is not a positive finite number
+void cs_chol_lower(hipStream_t st, double* A, int64_t m, int64_t n, int64_t ld, int32_t* flag);
+void cs_set_rows(hipStream_t st, double* W, int64_t ld, int64_t nobs, const double* HX, const double* b);
+void cs_schur(hipStream_t st, const double* W, int64_t ld, int64_t nobs, const double* b, double* x, double* out3);
+size_t cs_backsolve_workspace_doubles();
+void cs_backsolve(hipStream_t st, const double* A, int64_t n, int64_t ld, double* x, double* part);
+
 }}  // namespace gsi::hipk

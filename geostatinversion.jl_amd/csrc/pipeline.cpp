@@ -12,6 +12,7 @@
 //                QR of the stack, local fix-up Q_g <- Q_g * Q2_g
 #include "pipeline.hpp"
 #include "lsqr_state.hpp"
+#include "saddle_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1139,6 +1140,80 @@ void PcgaLowRank::mul(const double* x, double* y) const {
   else be->gemv_n(nobs, nobs, 1.0, R.p, nobs, x, 1.0, y);
   be->gemv_n(nobs, 1, 1.0, HX.p, nobs, x + nobs, 1.0, y);                         // + HX x[end]
   be->gemv_t(nobs, 1, 1.0, HX.p, nobs, x, y + nobs);                              // dot(HX, xs)
+}
+
+// ---- the saddle-point system by Cholesky ------------------------------------------------------
+namespace {
+bool saddle_host_forced() {
+  const char* e = getenv("GSI_SADDLE_HOST");
+  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
+}
+std::string not_posdef_message(int64_t col) {
+  return "PosDefException: matrix is not positive definite; Cholesky failed at " + std::to_string(col);
+}
+const char* const kSaddleSingular =
+    "SingularException: the saddle-point matrix [(HQH + R) HX; HX' 0] is singular (HX' (HQH + R)^-1 HX is zero or not finite)";
+}  // namespace
+
+void PcgaLowRank::solve(const double* b, double* x, int64_t* info2) const {
+  Backend* be = ctx->be.get();
+  const int64_t n1 = nobs + 1;
+  info2[0] = 0;
+  info2[1] = 0;
+  if (!saddle_host_forced()) {
+    Buf bd(be, (size_t)n1), xd(be, (size_t)n1);
+    be->upload2d(bd.p, n1, b, n1, n1, 1);
+    bool singular = false;
+    const int64_t col = be->saddle_solve(E.p, nobs, K, HX.p, R.p, r_diag, bd.p, xd.p, &singular);
+    if (col != -1) {
+      info2[1] = 1;
+      if (col > 0) {
+        info2[0] = col;
+        throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
+      }
+      if (singular) throw Error(GSI_ERR_SINGULAR, kSaddleSingular);
+      be->download2d(x, n1, xd.p, n1, n1, 1);
+      return;
+    }
+  }
+  // the host path: the operands as gsi_pcgamat_create stored them, downloaded, and the same algebra (saddle_host.hpp)
+  info2[1] = 3;
+  std::vector<double> Eh((size_t)nobs * K), HXh((size_t)nobs), Rh(r_diag ? (size_t)nobs : (size_t)nobs * nobs);
+  be->download2d(Eh.data(), nobs, E.p, nobs, nobs, K);
+  be->download2d(HXh.data(), nobs, HX.p, nobs, nobs, 1);
+  if (r_diag) be->download2d(Rh.data(), nobs, R.p, nobs, nobs, 1);
+  else be->download2d(Rh.data(), nobs, R.p, nobs, nobs, nobs);
+  const int64_t col = saddle_host::solve(Eh.data(), nobs, K, HXh.data(), Rh.data(), r_diag, b, x);
+  if (col > 0) {
+    info2[0] = col;
+    throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
+  }
+  if (col != 0) throw Error(GSI_ERR_SINGULAR, kSaddleSingular);
+}
+
+void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda, double* L, int64_t* info2) {
+  Backend* be = c.be.get();
+  info2[0] = 0;
+  info2[1] = 0;
+  int64_t col = -1;
+  if (!saddle_host_forced()) {
+    Buf W(be, (size_t)n * n);
+    be->upload2d(W.p, n, A, lda, n, n);
+    col = be->chol_lower(W.p, n, n, n);
+    if (col != -1) {
+      info2[1] = 1;
+      be->download2d(L, n, W.p, n, n, n);
+    }
+  }
+  if (col == -1) {
+    info2[1] = 3;
+    for (int64_t j = 0; j < n; ++j)
+      for (int64_t i = 0; i < n; ++i) L[i + j * n] = A[i + j * lda];
+    col = saddle_host::chol_lower(L, n, n, n);
+  }
+  info2[0] = col;
+  for (int64_t j = 1; j < n; ++j)
+    for (int64_t i = 0; i < j; ++i) L[i + j * n] = 0.0;
 }
 
 int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double epsilon, int64_t r,

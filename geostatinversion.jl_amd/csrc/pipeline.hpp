@@ -141,7 +141,15 @@ struct PcgaLowRank {
   Buf E, HX, R;        // E: nobs x K (eta_i as columns); R: nobs x nobs dense, or nobs values when r_diag
   bool r_diag = false;
   void mul(const double* x, double* y) const;   // x, y: nobs + 1
+  // x = A \ b (host vectors, nobs + 1) by Cholesky of HQH + R (direct.jl:56-58 for a positive definite HQH + R; DESIGN.md
+  // section 4.7c).  info2[0]: 0 or the 1-based column at which HQH + R stopped being positive definite; info2[1]: 1 the
+  // backend's kernels, 3 the host path (the backend declined, or GSI_SADDLE_HOST=1).  Throws GSI_ERR_NOT_POSDEF or
+  // GSI_ERR_SINGULAR (w'w == 0 or a non-finite beta) with info2 filled.
+  void solve(const double* b, double* x, int64_t* info2) const;
 };
+// cholesky(Symmetric(A, :L)).L of a host matrix (n x n, lda) into L (n x n, ld n, strictly upper triangle zero); info2 as above.
+// A failed factorization fills info2, leaves L unspecified and does not throw.
+void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda, double* L, int64_t* info2);
 // A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
 // vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
 // double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.

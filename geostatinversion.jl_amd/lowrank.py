@@ -166,3 +166,17 @@ class PCGALowRankMatrix:
         L.check(self.ctx.lib.gsi_pcgamat_lsqr(self.ctx.h, self.h, bv.ctypes.data_as(L.c_dp), x.ctypes.data_as(L.c_dp),
                                               C.byref(it)), self.ctx.lib)
         return (x, it.value) if return_iterations else x
+
+    def solve(self, b, *, return_info=False):
+        """`bigA \\ b` by Cholesky of HQH + R on the device (`gsi_pcgamat_solve`; direct.jl:56-58 for a positive definite
+        HQH + R).  Raises `GsiError` with code 7 when HQH + R is not positive definite and 3 when the saddle-point matrix is
+        singular (HX = 0).  `return_info=True` also returns `[column, path]`: the 1-based column of a failed factorization
+        (0: none) and 1 for the device path, 3 for the host path."""
+        bv = np.ascontiguousarray(b, dtype=np.float64)
+        if bv.shape != (self.nobs + 1,):
+            raise ValueError("dimension mismatch")
+        x = np.empty(self.nobs + 1)
+        info = (C.c_int64 * 2)()
+        L.check(self.ctx.lib.gsi_pcgamat_solve(self.ctx.h, self.h, bv.ctypes.data_as(L.c_dp), x.ctypes.data_as(L.c_dp), info),
+                self.ctx.lib)
+        return (x, [int(info[0]), int(info[1])]) if return_info else x

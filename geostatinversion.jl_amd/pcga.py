@@ -276,24 +276,46 @@ def _global_norm(basis, d):
 
 
 def pcgadirect(forwardmodel, s0, X, xis, R, y, *, maxiters=5, delta=SQRT_EPS, xtol=1e-6,
-               callback=lambda s, obs_cal: None, ctx=None):
+               callback=lambda s, obs_cal: None, ctx=None, solver="pinv"):
     """`pcgadirect(forwardmodel, s0, X, xis, R, y; maxiters=5, delta=sqrt(eps), xtol=1e-6, callback)`
-    (direct.jl:21-67)."""
+    (direct.jl:21-67).
+
+    `solver="pinv"` (the default) solves the saddle-point system of direct.jl:56-58 as the reference does, with a
+    pseudo-inverse of the dense (nobs+1)^2 matrix on the host.  `solver="cholesky"` solves it on the device by a Cholesky
+    factorization of HQH + R (`PCGALowRankMatrix.solve`), which needs HQH + R positive definite --
+    true whenever R is.  An iteration whose factorization fails (status 7) or whose system is singular (status 3) is solved
+    with the pseudo-inverse instead; `pcgadirect.last_fallbacks` counts those iterations of the last call.  Through `rga`:
+    `rga(..., pcgafunc=functools.partial(pcgadirect, solver="cholesky"))`."""
+    if solver not in ("pinv", "cholesky"):
+        raise ValueError("solver must be 'pinv' or 'cholesky'")
     basis = _as_basis(xis, ctx)
     s = np.asarray(s0, dtype=np.float64)
     X = np.asarray(X, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     Rd = R.toarray() if hasattr(R, "toarray") else np.asarray(R, dtype=np.float64)
     converged, it = False, 0
+    pcgadirect.last_fallbacks = 0
     while not converged and it < maxiters:
         olds = s
         etas, HX, Hs, hs = _iteration_head(forwardmodel, basis, s, X, delta)
         callback(s, hs)                                               # :47
-        E = np.stack(etas, axis=1)
-        HQH = E @ E.T                                                 # :49-53
         b = np.concatenate([y - hs + Hs, np.zeros(1)])                # :56
-        bigA = np.block([[HQH + Rd, HX[:, None]], [HX[None, :], np.zeros((1, 1))]])   # :57
-        x = np.linalg.pinv(bigA) @ b                                  # :58
+        x = None
+        if solver == "cholesky":
+            bigA = PCGALowRankMatrix(etas, HX, R, ctx=basis.ctx)
+            try:
+                x = bigA.solve(b)
+            except L.GsiError as e:
+                if e.code not in (3, 7):
+                    raise
+                pcgadirect.last_fallbacks += 1
+            finally:
+                bigA.close()
+        if x is None:
+            E = np.stack(etas, axis=1)
+            HQH = E @ E.T                                             # :49-53
+            bigA = np.block([[HQH + Rd, HX[:, None]], [HX[None, :], np.zeros((1, 1))]])   # :57
+            x = np.linalg.pinv(bigA) @ b                              # :58
         s = basis.update(X, x[-1], etas, x[:-1])                      # :59-65
         if _global_norm(basis, s - olds) < xtol:
             converged = True
@@ -334,4 +356,5 @@ def rga(forwardmodel, s0, X, xis, R, y, S, *, maxiters=5, delta=SQRT_EPS, xtol=1
                     maxiters=maxiters, delta=delta, xtol=xtol, callback=callback)
 
 
+pcgadirect.last_fallbacks = 0
 pcga = pcgadirect     # GeostatInversion.jl:105

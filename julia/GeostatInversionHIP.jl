@@ -540,6 +540,24 @@ function lsqr(A::PCGALowRankMatrix, b::Vector{Float64})
 		A.c.h, A.h, b, x, C_NULL))
 	return x
 end
+"`A \\ b` by Cholesky of HQH + R on the device (`gsi_pcgamat_solve`; direct.jl:56-58 for a positive definite HQH + R).
+Throws `PosDefException` when HQH + R is not positive definite and `SingularException` when HX = 0."
+function solve(A::PCGALowRankMatrix, b::Vector{Float64})
+	x = Vector{Float64}(undef, A.nobs + 1)
+	info = zeros(Int64, 2)
+	check(ccall((:gsi_pcgamat_solve, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+		A.c.h, A.h, b, x, info))
+	return x
+end
+"`cholesky(Symmetric(A, :L)).L` by the blocked device factorization (`gsi_chol_lower`)"
+function chol_lower(A::Matrix{Float64}; c::Context=ctx())
+	n = size(A, 1)
+	Lout = Matrix{Float64}(undef, n, n)
+	info = zeros(Int64, 2)
+	check(ccall((:gsi_chol_lower, libgsi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int64}),
+		c.h, A, n, stride(A, 2), Lout, info))
+	return Lout
+end
 
 # ---- RandMatFact ------------------------------------------------------------------------------------
 module RandMatFact
@@ -718,14 +736,33 @@ iterationhead(f::LinearForwardModel, s::Vector, X::Vector, xis::DeviceBasis, del
 iterationhead(r::ReducedForwardModel, s::Vector, X::Vector, xis::DeviceBasis, delta) =
 	headfromresults(r.S * forward(xis, r.fwd, s, X, delta), length(xis), delta)
 
+"Iterations of the last `pcgadirect(...; solver=:cholesky)` call that fell back to the pseudo-inverse."
+const last_fallbacks = Ref(0)
+"`pcgadirect(...; solver=:pinv)` as the reference (direct.jl:21-67); `solver=:cholesky` solves the saddle-point system on the
+device (`solve(::PCGALowRankMatrix, b)`).  Through `rga`: `rga(...; pcgafunc=pcgadirect, solver=:cholesky)` (keywords are passed on)."
 function pcgadirect(forwardmodel::Union{Function, DeviceForwardModel}, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector;
-		maxiters::Int=5, delta::Float64=sqrt(eps(Float64)), xtol::Float64=1e-6, callback=(s, obs_cal)->nothing)
+		maxiters::Int=5, delta::Float64=sqrt(eps(Float64)), xtol::Float64=1e-6, callback=(s, obs_cal)->nothing,
+		solver::Symbol=:pinv)
+	solver in (:pinv, :cholesky) || error("solver must be :pinv or :cholesky")
 	s, converged, iters = s0, false, 0
+	last_fallbacks[] = 0
 	while !converged && iters < maxiters
 		etas, HX, Hs, hs = iterationhead(forwardmodel, s, X, xis, delta)
 		callback(s, hs)
-		bigA = [(etas * etas' + R) HX; transpose(HX) 0.0]                               # direct.jl:57
-		x = LinearAlgebra.pinv(Matrix(bigA)) * [y - hs + Hs; 0.0]                        # :56,58
+		b = [y - hs + Hs; 0.0]                                                          # direct.jl:56
+		x = nothing
+		if solver == :cholesky                # Cholesky of HQH + R on the device; a failed iteration falls back to pinv
+			try
+				x = solve(PCGALowRankMatrix(etas, HX, R; c=xis.Z.c), b)
+			catch e
+				(e isa LinearAlgebra.PosDefException || e isa LinearAlgebra.SingularException) || rethrow()
+				last_fallbacks[] += 1
+			end
+		end
+		if x === nothing
+			bigA = [(etas * etas' + R) HX; transpose(HX) 0.0]                           # direct.jl:57
+			x = LinearAlgebra.pinv(Matrix(bigA)) * b                                    # :58
+		end
 		snew = update(xis, X, x[end], etas, x[1:end - 1])                                # :59-65
 		converged = LinearAlgebra.norm(snew - s) < xtol
 		s = snew
