@@ -43,6 +43,11 @@ SIGNATURES = {
                                    C.c_uint64, c_i64]),
     "gsi_op_lowrank_fftrf": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_double,
                                        c_i64, C.c_uint64, c_i64, c_i64]),
+    "gsi_fftrf_interpolate": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.POINTER(c_i64), c_dp, c_i64, c_dp, c_i64]),
+    "gsi_fftrf_fields_at": (C.c_int, [c_vp, c_vp, C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_double, c_dp, c_i64,
+                                      C.c_uint64, c_i64, c_dp, c_i64, c_dp, c_i64]),
+    "gsi_op_lowrank_fftrf_at": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_double,
+                                          c_i64, C.c_uint64, c_dp, c_i64, c_dp, c_i64, c_i64]),
     "gsi_op_dense_gridcov": (C.c_int, [c_vp, C.POINTER(c_vp), c_i64, c_i64, C.c_double, C.c_int, c_i64, c_i64]),
     "gsi_op_gridcov_implicit": (C.c_int, [c_vp, C.POINTER(c_vp), c_i64, c_i64, C.c_double, c_i64, c_i64]),
     "gsi_op_gridcov_implicit_kind": (C.c_int, [c_vp, C.POINTER(c_vp), c_i64, c_i64, C.c_double, C.c_int, c_i64, c_i64]),

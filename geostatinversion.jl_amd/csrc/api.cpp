@@ -10,6 +10,7 @@
 #include "../../include/gsi_hip.h"
 #include "pipeline.hpp"
 #include "pointcov.hpp"
+#include "fftrf_points.hpp"
 
 using namespace gsi;
 
@@ -334,6 +335,67 @@ int gsi_op_lowrank_fftrf(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N,
     // the sampler's normalising write goes straight into the operator's padded buffer
     ctx->c.be->fftrf_fields(A.data.p, A.ld, row0, n_local, numfields, ndims, N, k0, dk, beta, nullptr, 0, seed, 0);
     ctx->c.be->center_rows(A.data.p, n_local, numfields, A.ld);   // lowrank.jl:17-27
+    *op = o.release();
+  });
+}
+
+// The plan of the points [row0, row0 + m_local) on the grid N (fftrf_points.hpp), made before the grid limits of the sampler
+// are looked at: refusals become GSI_ERR_ARG before anything is allocated on the device.
+static void make_points_plan(int ndims, const int64_t* N, const double* points, int64_t m, const double* box, int64_t row0,
+                             int64_t m_local, FftrfPointsPlan* plan) {
+  REQUIRE(points != nullptr, "FFTRF points: points is NULL");
+  const char* why = fftrf_points_plan(ndims, N, points, m, box, row0, m_local, plan);
+  if (why) throw Error(GSI_ERR_ARG, why);
+}
+
+int gsi_fftrf_interpolate(gsi_ctx* ctx, gsi_mat* out, const gsi_mat* grid, int ndims, const int64_t* N, const double* points,
+                          int64_t m, const double* box, int64_t row0) {
+  return guarded([&] {
+    REQUIRE(ctx && out && grid && out->ctx == ctx && grid->ctx == ctx, "bad argument");
+    FftrfPointsPlan plan;
+    make_points_plan(ndims, N, points, m, box, row0, out->rows, &plan);
+    int64_t n = 0, mtot = 0;
+    check_fftrf_grid(ndims, N, 0.0, 1.0, 0.0, &n, &mtot);
+    REQUIRE(grid->rows == n, "FFTRF interpolate: grid must have n = prod(N) rows");
+    REQUIRE(out->cols == grid->cols, "FFTRF interpolate: out and grid must have one column per field");
+    ctx->c.be->fftrf_interpolate(out->buf.p, out->rows, out->cols, grid->buf.p, grid->rows, plan);
+  });
+}
+
+int gsi_fftrf_fields_at(gsi_ctx* ctx, gsi_mat* out, int ndims, const int64_t* N, double k0, double dk, double beta,
+                        const double* phi, int64_t ldphi, uint64_t seed, int64_t field0, const double* points, int64_t m,
+                        const double* box, int64_t row0) {
+  return guarded([&] {
+    REQUIRE(ctx && out && out->ctx == ctx, "bad argument");
+    FftrfPointsPlan plan;
+    make_points_plan(ndims, N, points, m, box, row0, out->rows, &plan);
+    int64_t n = 0, mtot = 0;
+    check_fftrf_grid(ndims, N, k0, dk, beta, &n, &mtot);
+    REQUIRE(phi == nullptr || ldphi >= mtot, "FFTRF fields: ldphi must be at least Mtot = 2^ndims n");
+    REQUIRE(phi != nullptr || field0 >= 0, "FFTRF fields: field0 must be >= 0");
+    ctx->c.be->fftrf_fields_at(out->buf.p, out->rows, out->cols, ndims, N, k0, dk, beta, phi, ldphi, seed, field0, plan);
+  });
+}
+
+int gsi_op_lowrank_fftrf_at(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, double k0, double dk, double beta,
+                            int64_t numfields, uint64_t seed, const double* points, int64_t m, const double* box,
+                            int64_t row0, int64_t m_local) {
+  return guarded([&] {
+    REQUIRE(ctx && op, "NULL argument");
+    *op = nullptr;
+    FftrfPointsPlan plan;
+    make_points_plan(ndims, N, points, m, box, row0, m_local, &plan);
+    int64_t n = 0, mtot = 0;
+    check_fftrf_grid(ndims, N, k0, dk, beta, &n, &mtot);
+    REQUIRE(numfields >= 2, "LowRankCovMatrix needs numfields >= 2 sample fields");
+    check_shard(ctx->c, m, row0, m_local);
+    std::unique_ptr<gsi_op> o(new gsi_op());
+    Operator& A = o->op;
+    A.ctx = &ctx->c; A.kind = OP_LOWRANK; A.m = m; A.n = m; A.row0 = row0; A.mloc = m_local; A.N = numfields;
+    A.ld = m_local > 0 ? ((m_local + 15) / 16) * 16 : 16;
+    A.data = Buf(ctx->c.be.get(), (size_t)A.ld * numfields);
+    ctx->c.be->fftrf_fields_at(A.data.p, A.ld, numfields, ndims, N, k0, dk, beta, nullptr, 0, seed, 0, plan);
+    ctx->c.be->center_rows(A.data.p, m_local, numfields, A.ld);   // lowrank.jl:17-27
     *op = o.release();
   });
 }

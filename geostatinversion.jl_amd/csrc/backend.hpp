@@ -53,6 +53,8 @@ struct FwdProduct {
   int64_t ncols() const { return plain ? K : K + 3; }
 };
 
+struct FftrfPointsPlan;   // fftrf_points.hpp
+
 // All pointers below are "backend memory" (HBM for the HIP backend), column-major fp64.
 class Backend {
  public:
@@ -336,6 +338,22 @@ class Backend {
     (void)dst; (void)ldd; (void)row0; (void)nloc; (void)nf; (void)ndims; (void)N; (void)k0; (void)dk; (void)beta; (void)phi;
     (void)ldphi; (void)seed; (void)field0;
     throw Error(1 /* GSI_ERR_ARG */, "FFTRF fields sampled on the device: not available on this backend");
+  }
+  // FFTRF.interpolate (FFTRF.jl:107-129) on the device (fftrf_interp.hip): the nf structured fields grid[:, c] (vec() order,
+  // leading dimension ldg) at the plan's points, dst[p + c ldd] for p < plan.m_local.  The plan comes from fftrf_points.hpp.
+  virtual void fftrf_interpolate(double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg,
+                                 const FftrfPointsPlan& plan) {
+    (void)dst; (void)ldd; (void)nf; (void)grid; (void)ldg; (void)plan;
+    throw Error(1 /* GSI_ERR_ARG */, "FFTRF interpolation on the device: not available on this backend");
+  }
+  // FFTRF.powerlaw_unstructuredgrid (FFTRF.jl:102-105): fftrf_fields whose every field is interpolated at the plan's points
+  // while it is still in the batch workspace; the n x nf structured matrix is never formed.
+  virtual void fftrf_fields_at(double* dst, int64_t ldd, int64_t nf, int ndims, const int64_t* N, double k0, double dk,
+                               double beta, const double* phi, int64_t ldphi, uint64_t seed, int64_t field0,
+                               const FftrfPointsPlan& plan) {
+    (void)dst; (void)ldd; (void)nf; (void)ndims; (void)N; (void)k0; (void)dk; (void)beta; (void)phi; (void)ldphi; (void)seed;
+    (void)field0; (void)plan;
+    throw Error(1 /* GSI_ERR_ARG */, "FFTRF fields at scattered points on the device: not available on this backend");
   }
   // column norms of Y (m x c) -> host array
   virtual void colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) = 0;

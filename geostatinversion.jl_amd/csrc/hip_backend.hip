@@ -13,6 +13,7 @@
 #include "hip_backend.hpp"
 #include "hip_common.hpp"
 #include "host_staging.hpp"
+#include "fftrf_points.hpp"
 
 namespace gsi {
 
@@ -1346,8 +1347,50 @@ class HipBackend : public HipDevice {
   // at every call, overrides the batch size).  Nothing a field computes depends on the batch it rides in.
   void fftrf_fields(double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf, int ndims, const int64_t* N, double k0,
                     double dk, double beta, const double* phi, int64_t ldphi, uint64_t seed, int64_t field0) override {
+    fftrf_batches(dst, ldd, row0, nloc, nf, ndims, N, k0, dk, beta, phi, ldphi, seed, field0, nullptr);
+  }
+  // The same batches, each field interpolated at the plan's points (fftrf_interp.hip) instead of copied out: the
+  // normalising write goes to the field's own workspace (over its phi, dead after the first pass) and the gather reads it
+  // there.  dst is plan.m_local x nf.
+  void fftrf_fields_at(double* dst, int64_t ldd, int64_t nf, int ndims, const int64_t* N, double k0, double dk, double beta,
+                       const double* phi, int64_t ldphi, uint64_t seed, int64_t field0, const FftrfPointsPlan& plan) override {
+    fftrf_batches(dst, ldd, 0, 0, nf, ndims, N, k0, dk, beta, phi, ldphi, seed, field0, &plan);
+  }
+  void fftrf_interpolate(double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg,
+                         const FftrfPointsPlan& plan) override {
     bind();
-    if (nf <= 0) return;
+    if (nf <= 0 || plan.m_local <= 0) return;
+    Scratch dplan(this, points_plan_doubles(plan));
+    upload_points_plan(plan, dplan.p);
+    for (int64_t f0 = 0; f0 < nf; f0 += 4096) {
+      const int b = (int)((nf - f0 < 4096) ? (nf - f0) : 4096);
+      interp_batch(plan, dplan.p, grid + f0 * ldg, ldg, b, dst + f0 * ldd, ldd);
+    }
+  }
+ private:
+  // the plan on the device: frac (ndims x m_local doubles), then base (m_local int32)
+  static size_t points_plan_doubles(const FftrfPointsPlan& plan) {
+    return (size_t)plan.m_local * plan.ndims + (size_t)(plan.m_local + 1) / 2;
+  }
+  void upload_points_plan(const FftrfPointsPlan& plan, double* d) {
+    const int64_t m = plan.m_local, nfr = m * plan.ndims;
+    upload2d(d, nfr, plan.frac.data(), nfr, nfr, 1);
+    std::vector<double> packed((size_t)(m + 1) / 2, 0.0);
+    std::memcpy(packed.data(), plan.base.data(), sizeof(int32_t) * (size_t)m);
+    upload2d(d + nfr, (int64_t)packed.size(), packed.data(), (int64_t)packed.size(), (int64_t)packed.size(), 1);
+  }
+  void interp_batch(const FftrfPointsPlan& plan, const double* dplan, const double* V, int64_t v_fs, int nb, double* dst,
+                    int64_t ldd) {
+    const int64_t m = plan.m_local;
+    hipk::fftrf_interp(st_, plan.ndims, reinterpret_cast<const int32_t*>(dplan + m * plan.ndims), dplan, m, plan.N[0],
+                       plan.N[0] * plan.N[1], V, v_fs, nb, dst, ldd);
+    check_launch("fftrf_interp");
+  }
+  void fftrf_batches(double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf, int ndims, const int64_t* N, double k0,
+                     double dk, double beta, const double* phi, int64_t ldphi, uint64_t seed, int64_t field0,
+                     const FftrfPointsPlan* at) {
+    bind();
+    if (nf <= 0 || (at && at->m_local <= 0)) return;
     hipk::FftrfGeom g;
     hipk::fftrf_geometry(ndims, N, &g);
     int64_t fs = (int64_t)hipk::fftrf_field_doubles(g);
@@ -1358,6 +1401,8 @@ class HipBackend : public HipDevice {
     if (nb > nf) nb = nf;
     if (nb < 1) nb = 1;
     Scratch plan(this, hipk::fftrf_plan_doubles(g)), ws(this, (size_t)(fs * nb));
+    Scratch dplan(this, at ? points_plan_doubles(*at) : 0);
+    if (at) upload_points_plan(*at, dplan.p);
     hipk::fftrf_plan(st_, g, plan.p);
     for (int64_t f0 = 0; f0 < nf; f0 += nb) {
       const int b = (int)((nf - f0 < nb) ? (nf - f0) : nb);
@@ -1367,10 +1412,17 @@ class HipBackend : public HipDevice {
       } else {
         for (int i = 0; i < b; ++i) hipk::randn_fill(st_, ws.p + (int64_t)i * fs, (size_t)g.Mtot, seed + (uint64_t)(field0 + f0 + i));
       }
-      hipk::fftrf_sample(st_, g, plan.p, ws.p, fs, b, k0, dk, beta, dst + f0 * ldd, ldd, row0, nloc);
-      check_launch("fftrf_sample");
+      if (!at) {
+        hipk::fftrf_sample(st_, g, plan.p, ws.p, fs, b, k0, dk, beta, dst + f0 * ldd, ldd, row0, nloc);
+        check_launch("fftrf_sample");
+      } else {
+        hipk::fftrf_sample(st_, g, plan.p, ws.p, fs, b, k0, dk, beta, ws.p, fs, 0, g.n);   // field i: ws + i fs, n values
+        check_launch("fftrf_sample");
+        interp_batch(*at, dplan.p, ws.p, fs, b, dst + f0 * ldd, ldd);
+      }
     }
   }
+ public:
   void colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) override {
     bind();
     if (c > 64) throw Error(GSI_ERR_ARG, "colnorms: at most 64 columns at a time");

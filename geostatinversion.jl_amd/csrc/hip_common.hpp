@@ -106,6 +106,11 @@ void fftrf_plan(hipStream_t st, const FftrfGeom& g, double* plan);
 // nb fields whose phi sits at ws + b fs (fs even, >= fftrf_field_doubles): dst[(r - row0) + b ldd] for r in [row0, row0 + nloc)
 void fftrf_sample(hipStream_t st, const FftrfGeom& g, const double* plan, double* ws, int64_t fs, int nb, double k0, double dk,
                   double beta, double* dst, int64_t ldd, int64_t row0, int64_t nloc);
+// ---- fftrf_interp.hip: FFTRF.interpolate (FFTRF.jl:107-129), nb structured fields at m scattered points ----
+// base (m), frac (d x m, axis-major): the plan of fftrf_points.hpp on the device; field b at V + b v_fs, vec() order, strides
+// 1, s1, s2 along its axes; dst[p + b ldd] = the nested two-term sums, each product and sum rounded on its own
+void fftrf_interp(hipStream_t st, int d, const int32_t* base, const double* frac, int64_t m, int64_t s1, int64_t s2,
+                  const double* V, int64_t v_fs, int nb, double* dst, int64_t ldd);
 
 // ---- panel_lu_leaf.hip: register-resident leaves (panels of <= 4096 rows per CU, a little more with overflow rows); the
 //      updates between the blocks are panel_lu_blocks.hip's ----

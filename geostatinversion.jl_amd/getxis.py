@@ -75,13 +75,20 @@ def getxis_device(Q, numxis, p, q=3, seed=None, *, Omega=None, ctx=None, precisi
             op.close()
 
 
-def getxis_fftrf(Ns, k0, dk, beta, numfields, numxis, p, q=3, seed=None, *, field_seed=0, Omega=None, ctx=None, device=False):
+def getxis_fftrf(Ns, k0, dk, beta, numfields, numxis, p, q=3, seed=None, *, field_seed=0, Omega=None, ctx=None, device=False,
+                 points=None, box=None):
     """`getxis(() -> FFTRF.powerlaw_structuredgrid(Ns, k0, dk, beta), numfields, numxis, p, q, seed)` with the fields sampled
     on the device and never leaving HBM (`gsi_op_lowrank_fftrf`; field f draws the device stream `field_seed + f`).  `seed`
-    governs Omega exactly as in `getxis`.  Returns the list of xi-vectors, or with `device=True` a `DeviceBasis`."""
+    governs Omega exactly as in `getxis`.  Returns the list of xi-vectors, or with `device=True` a `DeviceBasis`.  With
+    `points` (ndims x m; `box` optional) the sample function is `() -> FFTRF.powerlaw_unstructuredgrid(points, Ns, k0, dk,
+    beta)` and the xi-vectors have m entries (`gsi_op_lowrank_fftrf_at`)."""
     from .context import default_context
-    from .fftrf import lowrank_fftrf_operator
-    op = lowrank_fftrf_operator(ctx or default_context(), Ns, k0, dk, beta, numfields, seed=field_seed)
+    from .fftrf import lowrank_fftrf_operator, _points_args
+    if points is not None or box is not None:
+        if points is None:
+            raise ValueError("box applies to points: pass points as well")
+        _points_args(points, box, len(list(Ns)))
+    op = lowrank_fftrf_operator(ctx or default_context(), Ns, k0, dk, beta, numfields, seed=field_seed, points=points, box=box)
     try:
         if device:
             return getxis_device(op, numxis, p, q, seed, Omega=Omega)

@@ -181,6 +181,65 @@ function lowrank_fftrf_operator(Ns::Vector{Int}, k0::Float64, dk::Float64, beta:
 	return op
 end
 
+"`numfields` fields of `FFTRF.powerlaw_unstructuredgrid(points, Ns, k0, dk, beta)` (FFTRF.jl:102-129) on the device
+(`gsi_fftrf_fields_at`): an m x numfields `DeviceMatrix`, the fields of `fftrf_fields` (same `phi` / `seed` / `field0`)
+interpolated at `points` (d x m) while they are in the sampler's workspace.  `box` (lo of every axis, then hi) replaces the
+points' own extrema."
+function fftrf_fields_at(points::Matrix{Float64}, Ns::Vector{Int}, k0::Float64, dk::Float64, beta::Float64, numfields::Int;
+		phi::Union{Nothing,Matrix{Float64}}=nothing, seed::Integer=0, field0::Int=0,
+		box::Union{Nothing,Vector{Float64}}=nothing, c::Context=ctx())
+	N64 = Int64.(Ns)
+	size(points, 1) == length(Ns) || error("points must be ndims x m")
+	box === nothing || length(box) == 2 * length(Ns) || error("box must hold 2 ndims values")
+	m = size(points, 2)
+	F = DeviceMatrix(m, numfields; c=c)
+	bx = box === nothing ? Ptr{Float64}(C_NULL) : pointer(box)
+	if phi === nothing
+		GC.@preserve box check(ccall((:gsi_fftrf_fields_at, libgsi), Cint,
+			(Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Int64, UInt64, Int64,
+			 Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+			c.h, F.h, length(N64), N64, k0, dk, beta, C_NULL, 0, UInt64(seed), field0, points, m, bx, 0))
+	else
+		size(phi, 2) == numfields || error("phi must have one column per field")
+		GC.@preserve phi box check(ccall((:gsi_fftrf_fields_at, libgsi), Cint,
+			(Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Int64, UInt64, Int64,
+			 Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+			c.h, F.h, length(N64), N64, k0, dk, beta, phi, stride(phi, 2), UInt64(0), 0, points, m, bx, 0))
+	end
+	return F
+end
+
+"`FFTRF.powerlaw_unstructuredgrid(points, Ns, k0, dk, beta)` (FFTRF.jl:102-105): one field at the m points, on the host.
+`phi` = the `randn(size(S))` array of `mulbyphi`; without it the device stream `seed`."
+function powerlaw_unstructuredgrid(points::Matrix{Float64}, Ns::Vector{Int}, k0::Float64, dk::Float64, beta::Float64;
+		phi::Union{Nothing,Array{Float64}}=nothing, seed::Integer=0, box::Union{Nothing,Vector{Float64}}=nothing,
+		c::Context=ctx())
+	ph = phi === nothing ? nothing : reshape(phi, length(phi), 1)
+	F = fftrf_fields_at(points, Ns, k0, dk, beta, 1; phi=ph, seed=seed, box=box, c=c)
+	out = Matrix{Float64}(undef, F.rows, 1)
+	check(ccall((:gsi_mat_download, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64), c.h, F.h, out, F.rows))
+	return vec(out)
+end
+
+"`LowRankCovMatrix` over `numfields` such fields at the m points (`gsi_op_lowrank_fftrf_at`): what
+`getxis(() -> FFTRF.powerlaw_unstructuredgrid(points, Ns, k0, dk, beta), numfields, ...)` builds, m x m, kept in HBM."
+function lowrank_fftrf_operator(points::Matrix{Float64}, Ns::Vector{Int}, k0::Float64, dk::Float64, beta::Float64,
+		numfields::Int; seed::Integer=0, box::Union{Nothing,Vector{Float64}}=nothing, c::Context=ctx())
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	N64 = Int64.(Ns)
+	size(points, 1) == length(Ns) || error("points must be ndims x m")
+	box === nothing || length(box) == 2 * length(Ns) || error("box must hold 2 ndims values")
+	m = size(points, 2)
+	bx = box === nothing ? Ptr{Float64}(C_NULL) : pointer(box)
+	GC.@preserve box check(ccall((:gsi_op_lowrank_fftrf_at, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Cint, Ptr{Int64}, Cdouble, Cdouble, Cdouble, Int64, UInt64, Ptr{Float64}, Int64,
+		 Ptr{Float64}, Int64, Int64),
+		c.h, r, length(N64), N64, k0, dk, beta, numfields, UInt64(seed), points, m, bx, 0, m))
+	op = DeviceOperator(r[], c, m, m)
+	finalizer(finalize_op!, op)
+	return op
+end
+
 "Gaussian covariance exp(-d^2/(2 ell^2)) of an nx x ny unit grid as a matrix-free operator: entries are regenerated
 inside the product kernel, nothing of size n^2 is stored (`gsi_op_gridcov_implicit`).  Usable wherever a Matrix is."
 function GridCovImplicit(nx::Int, ny::Int, ell::Float64; c::Context=ctx())
