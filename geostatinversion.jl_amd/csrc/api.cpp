@@ -1397,6 +1397,64 @@ int gsi_pcga_forward_basis(gsi_ctx* ctx, const gsi_basis* basis, const gsi_fwd* 
   });
 }
 
+// ---- the posterior variance from the resident basis ------------------------------
+int gsi_basis_quadform(gsi_ctx* ctx, const gsi_basis* basis, const double* W, int64_t ldw, int64_t ncols, int upper,
+                       const double* u, double* a_out, double* q_out, double* t_out, int64_t* info_out) {
+  int64_t info2[2] = {0, 0};
+  const int st = guarded([&] {
+    REQUIRE(ctx && basis && W && a_out, "gsi_basis_quadform: NULL argument");
+    REQUIRE((u == nullptr) == (t_out == nullptr), "gsi_basis_quadform: u and t_out go together");
+    REQUIRE(basis->ctx == ctx, "gsi_basis_quadform: the basis belongs to another context");
+    REQUIRE(ncols >= 1 && ldw >= basis->K, "gsi_basis_quadform: need ncols >= 1 and ldw >= K");
+    const void* Z = basis->precision == 64 ? (const void*)basis->Z64 : (const void*)basis->buf32.p;
+    basis_quadform(ctx->c, Z, basis->precision, basis->n, basis->K, W, ldw, ncols, upper != 0, u, a_out, q_out, t_out, info2);
+    check_async_errors(ctx->c);
+  });
+  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
+  return st;
+}
+
+namespace {
+void require_posterior_shape(const gsi_pcgamat* mat, const char* who) {
+  if (!mat->A.r_diag && mat->A.nobs > 32768)
+    throw Error(GSI_ERR_ARG, std::string(who) + ": nobs = " + std::to_string(mat->A.nobs) +
+                                 " with a dense R is beyond the 32768 the Cholesky factorization takes");
+}
+}  // namespace
+
+int gsi_pcgamat_posterior(gsi_ctx* ctx, const gsi_pcgamat* mat, double* W_out, double* u_out, double* gamma_out,
+                          int64_t* info_out) {
+  int64_t info2[2] = {0, 0};
+  const int st = guarded([&] {
+    REQUIRE(ctx && mat && W_out && u_out && gamma_out, "gsi_pcgamat_posterior: NULL argument");
+    REQUIRE(mat->ctx == ctx, "gsi_pcgamat_posterior: the matrix belongs to another context");
+    require_posterior_shape(mat, "gsi_pcgamat_posterior");
+    posterior_factor(mat->A, W_out, u_out, gamma_out, info2);
+    check_async_errors(ctx->c);
+  });
+  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
+  return st;
+}
+
+int gsi_pcga_posterior_variance(gsi_ctx* ctx, const gsi_basis* basis, const gsi_pcgamat* mat, const double* X,
+                                const double* prior, double* var_out, int64_t* info_out) {
+  int64_t info2[2] = {0, 0};
+  const int st = guarded([&] {
+    REQUIRE(ctx && basis && mat && X && var_out, "gsi_pcga_posterior_variance: NULL argument");
+    REQUIRE(basis->ctx == ctx, "gsi_pcga_posterior_variance: the basis belongs to another context");
+    REQUIRE(mat->ctx == ctx, "gsi_pcga_posterior_variance: the matrix belongs to another context");
+    if (mat->A.K != basis->K)
+      throw Error(GSI_ERR_ARG, "gsi_pcga_posterior_variance: the matrix has K = " + std::to_string(mat->A.K) +
+                                   ", the basis K = " + std::to_string(basis->K));
+    require_posterior_shape(mat, "gsi_pcga_posterior_variance");
+    const void* Z = basis->precision == 64 ? (const void*)basis->Z64 : (const void*)basis->buf32.p;
+    posterior_variance(ctx->c, Z, basis->precision, basis->n, basis->K, mat->A, X, prior, var_out, info2);
+    check_async_errors(ctx->c);
+  });
+  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
+  return st;
+}
+
 // ---- measurement ---------------------------------------------------------------------
 int gsi_ctx_profile(gsi_ctx* ctx, int enable) {
   return guarded([&] {

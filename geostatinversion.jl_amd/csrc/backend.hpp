@@ -414,6 +414,23 @@ class Backend {
     return -1;
   }
 
+  // ---- the posterior variance from the resident basis ----
+  // One pass over the rows z_i of the basis Z (n x K, ld ldz; zbits 64: double, 32: float widened per element), every sum in
+  // fp64:  a[i] = |W' z_i|^2 for W (K x ncols, ld ldw; upper: W[k, j] with k > j is zero and never read),
+  // q[i] = |z_i|^2 (q may be null), t[i] = u' z_i (u and t null together).  Z W is never formed.
+  // Returns 1, or 0: "not mine", nothing ran, and pipeline.cpp runs posterior_host.hpp on a downloaded basis.
+  virtual int basis_quadform(const void* Z, int zbits, int64_t n, int64_t ldz, int64_t K, const double* W, int64_t ldw,
+                             int64_t ncols, bool upper, const double* u, double* a, double* q, double* t) {
+    (void)Z; (void)zbits; (void)n; (void)ldz; (void)K; (void)W; (void)ldw; (void)ncols; (void)upper; (void)u; (void)a; (void)q;
+    (void)t;
+    return 0;
+  }
+  // dst (m x c, ld ldd) = diag(d) src (m x c, ld lds): the rows of E and HX scaled by 1 / sqrt(R_jj).  1, or 0: "not mine".
+  virtual int scale_rows(int64_t m, int64_t c, const double* d, const double* src, int64_t lds, double* dst, int64_t ldd) {
+    (void)m; (void)c; (void)d; (void)src; (void)lds; (void)dst; (void)ldd;
+    return 0;
+  }
+
   // error flags raised asynchronously by kernels (zero pivot, non-posdef); checked and
   // cleared by the pipeline at the end of each entry point. Returns GSI_* code or 0.
   virtual int take_error(std::string* msg) = 0;

@@ -1571,6 +1571,23 @@ class HipBackend : public HipDevice {
     return 0;
   }
 
+  // The row pass of the posterior variance (posterior_var.hip).
+  int basis_quadform(const void* Z, int zbits, int64_t n, int64_t ldz, int64_t K, const double* W, int64_t ldw, int64_t ncols,
+                     bool upper, const double* u, double* a, double* q, double* t) override {
+    bind();
+    if (n < 1 || K < 1 || ncols < 1 || ldz < n || ldw < K || (zbits != 64 && zbits != 32) || (u == nullptr) != (t == nullptr))
+      throw Error(GSI_ERR_ARG, "basis_quadform: need n, K, ncols >= 1, ldz >= n, ldw >= K, 32 or 64 bits, u and t together");
+    hipk::pv_quadform(st_, Z, zbits, n, ldz, K, W, ldw, ncols, upper, u, a, q, t);
+    check_launch("basis_quadform");
+    return 1;
+  }
+  int scale_rows(int64_t m, int64_t c, const double* d, const double* src, int64_t lds, double* dst, int64_t ldd) override {
+    bind();
+    hipk::pv_scale_rows(st_, m, c, d, src, lds, dst, ldd);
+    check_launch("scale_rows");
+    return 1;
+  }
+
   // The persistent leaf kernel spins on records of ALL its workgroups: the grid must fit the chip at this kernel's
   // occupancy (registers, LDS, waves).  Queried once per instantiation; a panel that does not fit takes the streamed leaves.
   bool lu2_fits(int bs, int rpt, int grid) {

@@ -318,4 +318,12 @@ void cs_schur(hipStream_t st, const double* W, int64_t ld, int64_t nobs, const d
 size_t cs_backsolve_workspace_doubles();
 void cs_backsolve(hipStream_t st, const double* A, int64_t n, int64_t ld, double* x, double* part);
 
+// ---- posterior_var.hip: the row pass of the posterior variance (Backend::basis_quadform) ----
+// a[i] = |W' z_i|^2, q[i] = |z_i|^2 (q may be null), t[i] = u' z_i (u, t null together) for the rows of Z (n x K, ld ldz,
+// double or float by zbits) and W (K x ncols, ld ldw, device; upper: entries below the diagonal are not read)
+void pv_quadform(hipStream_t st, const void* Z, int zbits, int64_t n, int64_t ldz, int64_t K, const double* W, int64_t ldw,
+                 int64_t ncols, bool upper, const double* u, double* a, double* q, double* t);
+void pv_scale_rows(hipStream_t st, int64_t m, int64_t c, const double* d, const double* src, int64_t lds, double* dst,
+                   int64_t ldd);
+
 }}  // namespace gsi::hipk

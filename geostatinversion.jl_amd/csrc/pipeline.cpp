@@ -13,6 +13,7 @@
 #include "pipeline.hpp"
 #include "lsqr_state.hpp"
 #include "saddle_host.hpp"
+#include "posterior_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1214,6 +1215,206 @@ void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda,
   info2[0] = col;
   for (int64_t j = 1; j < n; ++j)
     for (int64_t i = 0; i < j; ++i) L[i + j * n] = 0.0;
+}
+
+// ---- the posterior variance from the resident basis -------------------------------------------
+namespace {
+bool post_host_forced() {
+  const char* e = getenv("GSI_POST_HOST");
+  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
+}
+const char* const kPostSingular =
+    "SingularException: the posterior needs HX' (HQH + R)^-1 HX positive and finite (HX is zero, or the operands are not finite)";
+
+// The basis on the host, as the values it stores: fp64 as they are, fp32 as the floats of the double-typed allocation.
+void download_basis(Backend* be, const void* Z, int zbits, int64_t n, int64_t K, std::vector<double>& store) {
+  const size_t count = (size_t)n * (size_t)K;
+  const size_t doubles = zbits == 32 ? (count + 1) / 2 : count;
+  store.resize(doubles);
+  be->download2d(store.data(), (int64_t)doubles, (const double*)Z, (int64_t)doubles, (int64_t)doubles, 1);
+}
+
+void quadform_host(Backend* be, const void* Z, int zbits, int64_t n, int64_t K, const double* W, int64_t ldw, int64_t ncols,
+                   bool upper, const double* u, double* a, double* q, double* t) {
+  std::vector<double> store;
+  download_basis(be, Z, zbits, n, K, store);
+  if (zbits == 32)
+    posterior_host::quadform((const float*)(const void*)store.data(), n, n, K, W, ldw, ncols, upper, u, a, q, t);
+  else
+    posterior_host::quadform(store.data(), n, n, K, W, ldw, ncols, upper, u, a, q, t);
+}
+}  // namespace
+
+void basis_quadform(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const double* W, int64_t ldw, int64_t ncols,
+                    bool upper, const double* u, double* a, double* q, double* t, int64_t* info2) {
+  Backend* be = c.be.get();
+  info2[0] = 0;
+  info2[1] = 0;
+  if (!post_host_forced()) {
+    Buf Wd(be, (size_t)K * (size_t)ncols), ud(be, (size_t)K), out(be, (size_t)n * 3);
+    if (upper) {                                       // only the promised part travels: what lies below may be anything
+      std::vector<double> Wu((size_t)K * (size_t)ncols, 0.0);
+      for (int64_t j = 0; j < ncols; ++j)
+        for (int64_t k = 0; k < K && k <= j; ++k) Wu[(size_t)(k + j * K)] = W[k + j * ldw];
+      be->upload2d(Wd.p, K, Wu.data(), K, K, ncols);
+    } else {
+      be->upload2d(Wd.p, K, W, ldw, K, ncols);
+    }
+    if (u) be->upload2d(ud.p, K, u, K, K, 1);
+    double* ad = out.p;
+    double* qd = q ? out.p + n : nullptr;
+    double* td = u ? out.p + 2 * n : nullptr;
+    int ran = 0;
+    {
+      ScopedPhase ph(be, PH_OTHER);                    // (profiling: the row pass alone; tools/pcga_posterior_bench.py)
+      ran = be->basis_quadform(Z, zbits, n, n, K, Wd.p, K, ncols, upper, u ? ud.p : nullptr, ad, qd, td);
+    }
+    if (ran != 0) {
+      info2[1] = 1;
+      be->download2d(a, n, ad, n, n, 1);
+      if (q) be->download2d(q, n, qd, n, n, 1);
+      if (u) be->download2d(t, n, td, n, n, 1);
+      return;
+    }
+  }
+  info2[1] = 3;
+  quadform_host(be, Z, zbits, n, K, W, ldw, ncols, upper, u, a, q, t);
+}
+
+void posterior_factor(const PcgaLowRank& A, double* W, double* u, double* gamma, int64_t* info2, Buf* Wdev, Buf* udev) {
+  Backend* be = A.ctx->be.get();
+  const int64_t nobs = A.nobs, K = A.K;
+  info2[0] = 0;
+  info2[1] = 0;
+  // the backend's path: scale_rows or one chol_lower for B and wt, the TN product for N, chol_lower on [N; I] for W
+  bool mine = !post_host_forced();
+  if (mine) {
+    Buf B(be, (size_t)nobs * (size_t)K), wt(be, (size_t)nobs);
+    if (A.r_diag) {
+      std::vector<double> d((size_t)nobs);
+      be->download2d(d.data(), nobs, A.R.p, nobs, nobs, 1);
+      for (int64_t i = 0; i < nobs; ++i) {
+        if (!(d[(size_t)i] > 0.0) || !std::isfinite(d[(size_t)i])) {
+          info2[0] = i + 1;
+          info2[1] = 1;
+          throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(i + 1));
+        }
+        d[(size_t)i] = 1.0 / std::sqrt(d[(size_t)i]);
+      }
+      Buf dd(be, (size_t)nobs);
+      be->upload2d(dd.p, nobs, d.data(), nobs, nobs, 1);
+      mine = be->scale_rows(nobs, K, dd.p, A.E.p, nobs, B.p, nobs) != 0 &&
+             be->scale_rows(nobs, 1, dd.p, A.HX.p, nobs, wt.p, nobs) != 0;
+    } else {
+      // [R; E'; w'] (nobs + K + 1 rows): the carried rows are transposed on the host, they are (K + 1) x nobs numbers
+      const int64_t kc = K + 1, ld = nobs + kc;
+      std::vector<double> Eh((size_t)nobs * (size_t)kc), C((size_t)kc * (size_t)nobs);
+      be->download2d(Eh.data(), nobs, A.E.p, nobs, nobs, K);
+      be->download2d(Eh.data() + (size_t)nobs * (size_t)K, nobs, A.HX.p, nobs, nobs, 1);
+      for (int64_t j = 0; j < nobs; ++j)
+        for (int64_t cix = 0; cix < kc; ++cix) C[(size_t)(cix + j * kc)] = Eh[(size_t)(j + cix * nobs)];
+      Buf T(be, (size_t)ld * (size_t)nobs);
+      be->copy2d(T.p, ld, A.R.p, nobs, nobs, nobs);
+      be->upload2d(T.p + nobs, ld, C.data(), kc, kc, nobs);
+      const int64_t col = be->chol_lower(T.p, ld, nobs, ld);
+      if (col == -1) {
+        mine = false;
+      } else {
+        if (col > 0) {
+          info2[0] = col;
+          info2[1] = 1;
+          throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
+        }
+        be->download2d(C.data(), kc, T.p + nobs, ld, kc, nobs);
+        for (int64_t j = 0; j < nobs; ++j)
+          for (int64_t cix = 0; cix < kc; ++cix) Eh[(size_t)(j + cix * nobs)] = C[(size_t)(cix + j * kc)];
+        be->upload2d(B.p, nobs, Eh.data(), nobs, nobs, K);
+        be->upload2d(wt.p, nobs, Eh.data() + (size_t)nobs * (size_t)K, nobs, nobs, 1);
+      }
+    }
+    if (mine) {
+      const int64_t ld2 = 2 * K;
+      std::vector<double> T2h((size_t)ld2 * (size_t)K, 0.0);
+      for (int64_t j = 0; j < K; ++j) T2h[(size_t)(j + j * ld2)] = T2h[(size_t)(K + j + j * ld2)] = 1.0;
+      Buf T2(be, (size_t)ld2 * (size_t)K);
+      be->upload2d(T2.p, ld2, T2h.data(), ld2, ld2, K);
+      be->gemm_tn(K, K, nobs, 1.0, B.p, nobs, B.p, nobs, 1.0, T2.p, ld2);          // N = I + B'B
+      const int64_t col = be->chol_lower(T2.p, ld2, K, ld2);
+      if (col == -1) {
+        mine = false;
+      } else {
+        info2[1] = 1;
+        if (col != 0) throw Error(GSI_ERR_SINGULAR, kPostSingular);                // N >= I: only non-finite operands
+        Buf Wd(be, (size_t)K * (size_t)K), r(be, (size_t)K), y(be, (size_t)K), ud(be, (size_t)K);
+        be->copy2d(Wd.p, K, T2.p + K, ld2, K, K);                                  // W = L_N^-T
+        be->gemv_t(nobs, K, 1.0, B.p, nobs, wt.p, r.p);                            // r = B'wt
+        be->gemv_t(K, K, 1.0, Wd.p, K, r.p, y.p);                                  // u = W (W'r)
+        be->gemv_n(K, K, 1.0, Wd.p, K, y.p, 0.0, ud.p);
+        const double ww = be->dot(nobs, wt.p, wt.p);
+        const double g = ww - be->dot(K, r.p, ud.p);
+        if (!(ww > 0.0) || !std::isfinite(g) || !(g > 0.0)) throw Error(GSI_ERR_SINGULAR, kPostSingular);
+        if (gamma) *gamma = g;
+        if (W) {
+          be->download2d(W, K, Wd.p, K, K, K);
+          for (int64_t j = 0; j < K; ++j)
+            for (int64_t i = j + 1; i < K; ++i) W[i + j * K] = 0.0;
+        }
+        if (u) be->download2d(u, K, ud.p, K, K, 1);
+        if (Wdev) *Wdev = std::move(Wd);
+        if (udev) *udev = std::move(ud);
+        return;
+      }
+    }
+  }
+  // the host path: the operands as gsi_pcgamat_create stored them, downloaded, and the same algebra (posterior_host.hpp)
+  info2[1] = 3;
+  std::vector<double> Eh((size_t)nobs * K), HXh((size_t)nobs), Rh(A.r_diag ? (size_t)nobs : (size_t)nobs * nobs);
+  be->download2d(Eh.data(), nobs, A.E.p, nobs, nobs, K);
+  be->download2d(HXh.data(), nobs, A.HX.p, nobs, nobs, 1);
+  if (A.r_diag) be->download2d(Rh.data(), nobs, A.R.p, nobs, nobs, 1);
+  else be->download2d(Rh.data(), nobs, A.R.p, nobs, nobs, nobs);
+  std::vector<double> Wh((size_t)K * (size_t)K), uh((size_t)K);
+  double g = 0.0;
+  const int64_t col = posterior_host::factor(Eh.data(), nobs, K, HXh.data(), Rh.data(), A.r_diag, Wh.data(), uh.data(), &g);
+  if (col > 0) {
+    info2[0] = col;
+    throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
+  }
+  if (col != 0) throw Error(GSI_ERR_SINGULAR, kPostSingular);
+  if (W) std::copy(Wh.begin(), Wh.end(), W);
+  if (u) std::copy(uh.begin(), uh.end(), u);
+  if (gamma) *gamma = g;
+}
+
+void posterior_variance(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const PcgaLowRank& A, const double* X,
+                        const double* prior, double* var, int64_t* info2) {
+  Backend* be = c.be.get();
+  std::vector<double> Wh((size_t)K * (size_t)K), uh((size_t)K), a((size_t)n), q((size_t)n), t((size_t)n);
+  double gamma = 0.0;
+  Buf Wd, ud;
+  posterior_factor(A, Wh.data(), uh.data(), &gamma, info2, &Wd, &ud);
+  bool done = false;
+  if (!post_host_forced() && Wd.p != nullptr) {        // W and u are still on the device: they never leave it for the pass
+    Buf out(be, (size_t)n * 3);
+    int ran = 0;
+    {
+      ScopedPhase ph(be, PH_OTHER);
+      ran = be->basis_quadform(Z, zbits, n, n, K, Wd.p, K, K, true, ud.p, out.p, out.p + n, out.p + 2 * n);
+    }
+    if (ran != 0) {
+      be->download2d(a.data(), n, out.p, n, n, 1);
+      be->download2d(q.data(), n, out.p + n, n, n, 1);
+      be->download2d(t.data(), n, out.p + 2 * n, n, n, 1);
+      info2[1] = 1;
+      done = true;
+    }
+  }
+  if (!done) {
+    int64_t inf[2];
+    basis_quadform(c, Z, zbits, n, K, Wh.data(), K, K, true, uh.data(), a.data(), q.data(), t.data(), inf);
+    info2[1] = inf[1];
+  }
+  posterior_host::finish(n, a.data(), q.data(), t.data(), X, prior, gamma, var);
 }
 
 int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double epsilon, int64_t r,

@@ -150,6 +150,20 @@ struct PcgaLowRank {
 // cholesky(Symmetric(A, :L)).L of a host matrix (n x n, lda) into L (n x n, ld n, strictly upper triangle zero); info2 as above.
 // A failed factorization fills info2, leaves L unspecified and does not throw.
 void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda, double* L, int64_t* info2);
+// ---- the posterior variance from the resident basis.  info2[0]: 0 or the failing column of R;
+//      info2[1]: 1 the backend's kernels, 3 the host path (the backend declined, or GSI_POST_HOST=1, read at each call) ----
+// a[i] = |W' z_i|^2, q[i] = |z_i|^2 (q may be null), t[i] = u' z_i (u, t null together) over the rows of the basis Z
+// (backend memory, n x K, ld n, fp64 or fp32 by zbits).  W (K x ncols, ld ldw), u and the outputs are host arrays.
+void basis_quadform(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const double* W, int64_t ldw, int64_t ncols,
+                    bool upper, const double* u, double* a, double* q, double* t, int64_t* info2);
+// W (K x K upper triangular), u (K), gamma of the capacitance form, from the matrix's E, HX and R; host outputs (any may be
+// null).  Wdev / udev (may be null): on the backend's path W and u are also left there for the row pass (empty on the host
+// path).  Throws GSI_ERR_NOT_POSDEF (info2[0] = column) or GSI_ERR_SINGULAR.
+void posterior_factor(const PcgaLowRank& A, double* W, double* u, double* gamma, int64_t* info2, Buf* Wdev = nullptr,
+                      Buf* udev = nullptr);
+// var (n, host) by the two row formulas of section 4.7d; X (n) and prior (n, or null: the low-rank prior |z_i|^2) on the host
+void posterior_variance(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const PcgaLowRank& A, const double* X,
+                        const double* prior, double* var, int64_t* info2);
 // A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
 // vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
 // double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.

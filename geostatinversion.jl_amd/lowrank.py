@@ -180,3 +180,16 @@ class PCGALowRankMatrix:
         L.check(self.ctx.lib.gsi_pcgamat_solve(self.ctx.h, self.h, bv.ctypes.data_as(L.c_dp), x.ctypes.data_as(L.c_dp), info),
                 self.ctx.lib)
         return (x, [int(info[0]), int(info[1])]) if return_info else x
+
+    def posterior_factor(self, *, return_info=False):
+        """`(W, u, gamma)` of the posterior covariance V = Z W W' Z' + d d' / gamma, d = Z u - X (`gsi_pcgamat_posterior`;
+        DESIGN.md section 4.7d): W = L_N^-T (K x K upper triangular) with N = I + B'B, B = L_R^-1 E; u = N^-1 B' L_R^-1 HX;
+        gamma = HX' (HQH + R)^-1 HX.  Raises `GsiError` with code 7 when R is not positive definite and 3 when HX = 0.
+        `return_info=True` also returns `[column, path]` as `solve` does."""
+        W = np.empty((self.K, self.K), order="F")
+        u = np.empty(self.K)
+        gamma = C.c_double()
+        info = (C.c_int64 * 2)()
+        L.check(self.ctx.lib.gsi_pcgamat_posterior(self.ctx.h, self.h, L.dptr(W), L.dptr(u), C.byref(gamma), info), self.ctx.lib)
+        out = (W, u, gamma.value)
+        return out + ([int(info[0]), int(info[1])],) if return_info else out

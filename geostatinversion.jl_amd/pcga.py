@@ -95,6 +95,32 @@ class DeviceBasis:
                                                    out.ctypes.data_as(L.c_dp)), self.ctx.lib)
         return out
 
+    def quadform(self, W, u=None, *, upper=False, return_info=False):
+        """`(a, q, t)` over the rows z_i of the basis in one pass on the device (`gsi_basis_quadform`; DESIGN.md section
+        4.7d): a[i] = |W' z_i|^2 for the host matrix W (K x ncols), q[i] = |z_i|^2, t[i] = u' z_i (None without `u`).  Z W is
+        never formed.  `upper=True` promises W[k, j] = 0 for k > j: those entries are not read.  Both precisions; every sum
+        is fp64.  `return_info=True` also returns `[0, path]`, path 1 for the device kernel and 3 for the host path."""
+        import ctypes as C
+        W = np.asarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[0] != self.K or W.shape[1] < 1:
+            raise ValueError("W must be K x ncols with ncols >= 1")
+        colmajor = W.strides[0] == 8 and (W.shape[1] == 1 or (W.strides[1] % 8 == 0 and W.strides[1] >= 8 * self.K))
+        if not colmajor:                                               # the leading K rows of a column-major parent pass as they are
+            W = np.asfortranarray(W)
+        ldw = W.strides[1] // 8 if W.shape[1] > 1 else self.K
+        a, q = np.empty(self.n), np.empty(self.n)
+        uv = t = None
+        if u is not None:
+            uv = np.ascontiguousarray(u, dtype=np.float64)
+            if uv.shape != (self.K,):
+                raise ValueError("u must have K entries")
+            t = np.empty(self.n)
+        info = (C.c_int64 * 2)()
+        L.check(self.ctx.lib.gsi_basis_quadform(self.ctx.h, self.h, L.dptr(W), ldw, W.shape[1], 1 if upper else 0,
+                                                L.dptr(uv) if uv is not None else None, L.dptr(a), L.dptr(q),
+                                                L.dptr(t) if t is not None else None, info), self.ctx.lib)
+        return (a, q, t, [int(info[0]), int(info[1])]) if return_info else (a, q, t)
+
 
 class ShardedDeviceBasis(DeviceBasis):
     """A ROW-SHARDED xi-basis (BASELINE configs[4]): this rank's rows of Z as `gsi_randsvd_rows` left them,
@@ -354,6 +380,97 @@ def rga(forwardmodel, s0, X, xis, R, y, S, *, maxiters=5, delta=SQRT_EPS, xtol=1
         else (lambda x: S @ forwardmodel(x))
     return pcgafunc(reduced, s0, X, xis, S @ Rd @ S.T, S @ np.asarray(y, dtype=np.float64),
                     maxiters=maxiters, delta=delta, xtol=xtol, callback=callback)
+
+
+def _posterior_matrix(forwardmodel, basis, s, X, R, delta):
+    """The PCGALowRankMatrix of the linearisation at s (direct.jl:38-46): E = H Z, HX and R on the basis' context."""
+    etas, HX, _, _ = _iteration_head(forwardmodel, basis, np.asarray(s, dtype=np.float64), X, delta)
+    return PCGALowRankMatrix(etas, HX, R, ctx=basis.ctx)
+
+
+def posterior_variance(forwardmodel, s, X, xis, R, *, delta=SQRT_EPS, prior_variance=None, ctx=None, return_info=False):
+    """The posterior variance of the field at the linearisation point `s` (usually the estimate `pcgadirect` returned), for
+    the prior s ~ N(X beta, Q), Q ~ Z Z' with Z the xis and beta unknown, and the error covariance R:
+
+        v_i = |W' z_i|^2 + (u' z_i - X_i)^2 / gamma                     (prior variance taken as |z_i|^2, the low-rank one)
+        v_i = prior_i - |z_i|^2 + |W' z_i|^2 + (u' z_i - X_i)^2 / gamma  (`prior_variance` = the true prior variances)
+
+    with (W, u, gamma) = `PCGALowRankMatrix.posterior_factor()`.  The n-sized work is one pass over the resident basis on the
+    device (`gsi_pcga_posterior_variance`); a host `xis` list is uploaded into a temporary `DeviceBasis`.  A
+    `LinearForwardModel` beside a `DeviceBasis` is linearised on the device.  R must be positive definite (`GsiError` code 7
+    otherwise) and HX non-zero (code 3).  `return_info=True` also returns `[column, path]`, path 1 for the device kernel and 3
+    for the host path.  Row-sharded bases are not supported."""
+    import ctypes as C
+    if isinstance(xis, DeviceBasis) and getattr(xis, "gather", None) is not None:
+        raise NotImplementedError("posterior_variance: a row-sharded basis is not supported")
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    temp = None
+    if isinstance(xis, DeviceBasis):
+        basis = xis
+    else:
+        from .context import DeviceMatrix
+        cx = ctx or default_context()
+        Zm = DeviceMatrix.from_host(cx, np.stack([np.asarray(x, dtype=np.float64) for x in xis], axis=1))
+        basis = DeviceBasis(Zm, Zm.shape[1])
+        temp = (basis, Zm)
+    bigA = None
+    try:
+        if X.shape != (basis.n,):
+            raise ValueError("X must have the basis' n entries")
+        prior = None
+        if prior_variance is not None:
+            prior = np.ascontiguousarray(prior_variance, dtype=np.float64)
+            if prior.shape != (basis.n,):
+                raise ValueError("prior_variance must have the basis' n entries")
+        bigA = _posterior_matrix(forwardmodel, basis, s, X, R, delta)
+        var = np.empty(basis.n)
+        info = (C.c_int64 * 2)()
+        lib = basis.ctx.lib
+        L.check(lib.gsi_pcga_posterior_variance(basis.ctx.h, basis.h, bigA.h, L.dptr(X),
+                                                L.dptr(prior) if prior is not None else None, L.dptr(var), info), lib)
+    finally:
+        if bigA is not None:
+            bigA.close()
+        if temp is not None:
+            temp[0].close()
+            temp[1].close()
+    return (var, [int(info[0]), int(info[1])]) if return_info else var
+
+
+def posterior_realizations(forwardmodel, s_hat, X, xis, R, num, *, delta=SQRT_EPS, seed=None, omega=None, ctx=None):
+    """`num` conditional realisations around the estimate `s_hat`, as the columns of an n x num array:
+
+        s_c = s_hat + Z (W omega_1 + u omega_2 / sqrt(gamma)) - X omega_2 / sqrt(gamma),   omega_1 ~ N(0, I_K), omega_2 ~ N(0, 1)
+
+    whose covariance is the posterior covariance Z W W' Z' + d d' / gamma.  `omega` ((K + 1) x num: omega_1 over omega_2)
+    defaults to `RandMatFact.randn(K + 1, num)` (after `RandMatFact.seed(seed)` when `seed` is given); with `omega` given the
+    result is deterministic.  Each column is one pass over the basis (`DeviceBasis.update`)."""
+    from . import randmatfact
+    basis = _as_basis(xis, ctx)
+    if getattr(basis, "gather", None) is not None:
+        raise NotImplementedError("posterior_realizations: a row-sharded basis is not supported")
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    s_hat = np.asarray(s_hat, dtype=np.float64)
+    K = basis.K
+    num = int(num)
+    if omega is None:
+        if seed is not None:
+            randmatfact.seed(seed)
+        omega = randmatfact.randn(K + 1, num)
+    omega = np.asarray(omega, dtype=np.float64)
+    if omega.shape != (K + 1, num):
+        raise ValueError("omega must be (K + 1) x num")
+    bigA = _posterior_matrix(forwardmodel, basis, s_hat, X, R, delta)
+    try:
+        W, u, gamma = bigA.posterior_factor()
+    finally:
+        bigA.close()
+    eye = [np.ascontiguousarray(c) for c in np.eye(K)]
+    out = np.empty((basis.n, num), order="F")
+    for c in range(num):
+        w2 = omega[K, c] / np.sqrt(gamma)
+        out[:, c] = s_hat + basis.update(X, -w2, eye, W @ omega[:K, c] + u * w2)
+    return out
 
 
 pcgadirect.last_fallbacks = 0

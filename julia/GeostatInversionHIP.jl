@@ -846,6 +846,39 @@ end
 
 const pcga = pcgadirect                                                                  # GeostatInversion.jl:105
 
+"`(a, q, t)` over the rows z_i of the basis in one pass on the device: a[i] = |W' z_i|^2, q[i] = |z_i|^2, t[i] = u' z_i
+(`gsi_basis_quadform`).  `upper = true` promises W[k, j] = 0 for k > j: those entries are not read."
+function quadform(b::DeviceBasis, W::Matrix{Float64}, u::Vector{Float64}; upper::Bool=false)
+	a, q, t = Vector{Float64}(undef, b.n), Vector{Float64}(undef, b.n), Vector{Float64}(undef, b.n)
+	info = zeros(Int64, 2)
+	check(ccall((:gsi_basis_quadform, libgsi), Cint,
+		(Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+		b.Z.c.h, b.h, W, stride(W, 2), size(W, 2), upper ? 1 : 0, u, a, q, t, info))
+	return a, q, t
+end
+"`(W, u, gamma)` of the posterior covariance Z W W' Z' + d d' / gamma, d = Z u - X (`gsi_pcgamat_posterior`)."
+function posteriorfactor(A::PCGALowRankMatrix, K::Int)
+	W, u, gamma = Matrix{Float64}(undef, K, K), Vector{Float64}(undef, K), Ref{Float64}(0.0)
+	info = zeros(Int64, 2)
+	check(ccall((:gsi_pcgamat_posterior, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+		A.c.h, A.h, W, u, gamma, info))
+	return W, u, gamma[]
+end
+"The posterior variance of the field at the linearisation point `s`, for the prior s ~ N(X beta, Z Z') with beta unknown and
+the error covariance R: v_i = |W' z_i|^2 + (u' z_i - X_i)^2 / gamma, plus priorvariance_i - |z_i|^2 when the true prior
+variances are given.  One pass over the resident basis on the device (`gsi_pcga_posterior_variance`)."
+function posteriorvariance(forwardmodel::Union{Function, DeviceForwardModel}, s::Vector, X::Vector, xis::DeviceBasis, R;
+		delta::Float64=sqrt(eps(Float64)), priorvariance::Union{Nothing, Vector{Float64}}=nothing)
+	etas, HX, Hs, hs = iterationhead(forwardmodel, s, X, xis, delta)
+	A = PCGALowRankMatrix(etas, HX, R; c=xis.Z.c)
+	v = Vector{Float64}(undef, xis.n)
+	info = zeros(Int64, 2)
+	check(ccall((:gsi_pcga_posterior_variance, libgsi), Cint,
+		(Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+		xis.Z.c.h, xis.h, A.h, X, priorvariance === nothing ? C_NULL : priorvariance, v, info))
+	return v
+end
+
 "`rga(forwardmodel, s0, X, xis, R, y, S; ...)`  (GeostatInversion.jl:101-103)"
 rga(forwardmodel::Function, s0::Vector, X::Vector, xis::DeviceBasis, R, y::Vector, S; pcgafunc=pcgadirect, kwargs...) =
 	pcgafunc(x->S * forwardmodel(x), s0, X, xis, S * R * S', S * y; kwargs...)
