@@ -1,5 +1,5 @@
 // api.cpp -- the C ABI of include/gsi_hip.h: argument checking, host<->device staging and
-// error translation around pipeline.cpp.  No C++ exception crosses the boundary.
+// error translation around pipeline.cpp and pcga.cpp.  No C++ exception crosses the boundary.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/gsi_hip.h"
-#include "pipeline.hpp"
+#include "pcga.hpp"
 #include "pointcov.hpp"
 #include "fftrf_points.hpp"
 
@@ -40,6 +40,7 @@ struct gsi_basis {
   const double* Z64;
   Buf buf32;
   gsi_mat* owner = nullptr;   // precision 64: the matrix whose buffer Z64 points into, kept alive by this basis
+  BasisRef ref() const { return BasisRef{precision == 32 ? (const void*)buf32.p : (const void*)Z64, precision, n, K}; }
 };
 
 struct gsi_fwd {
@@ -69,6 +70,16 @@ int guarded(F&& f) {
   } catch (...) {
     return fail(GSI_ERR_INTERNAL, "unknown error");
   }
+}
+
+// guarded(f) for the entry points that report which path ran: info_out (may be null) receives {column, path} as f left them,
+// also when f threw
+template <class F>
+int with_info(int64_t* info_out, F&& f) {
+  PathInfo info;
+  const int st = guarded([&] { f(info); });
+  if (info_out) { info_out[0] = info.column; info_out[1] = info.path; }
+  return st;
 }
 
 // Runs f; if it fails because the backend lost a resource it no longer depends on (Backend::retryable_failure: the
@@ -1091,30 +1102,6 @@ int gsi_gemm_view(gsi_ctx* ctx, int form, int trans, int64_t m, int64_t l, int64
 }
 
 // ---- consumers -----------------------------------------------------------------------
-namespace {
-void pcga_params_impl(Context& c, const double* Zdev, int64_t n, int64_t K, const double* s, const double* X,
-                      double delta, double* out) {
-  Backend* be = c.be.get();
-  Buf O(be, (size_t)n * (K + 3)), sv(be, (size_t)n), Xv(be, (size_t)n);
-  be->upload2d(sv.p, n, s, n, n, 1);
-  be->upload2d(Xv.p, n, X, n, n, 1);
-  be->pcga_params(Zdev, n, K, sv.p, Xv.p, delta, O.p);           // direct.jl:39-45 / lsqr.jl:37-43
-  be->download2d(out, n, O.p, n, n, K + 3);
-}
-void pcga_update_impl(Context& c, const double* Zdev, int64_t n, int64_t K, const double* X, double beta_bar,
-                      const double* etas, int64_t nobs, const double* xi_bar, double* s_out) {
-  Backend* be = c.be.get();
-  Buf E(be, (size_t)nobs * K), xb(be, (size_t)nobs), w(be, (size_t)K), sd(be, (size_t)n), Xd(be, (size_t)n);
-  be->upload2d(E.p, nobs, etas, nobs, nobs, K);
-  be->upload2d(xb.p, nobs, xi_bar, nobs, nobs, 1);
-  be->upload2d(Xd.p, n, X, n, n, 1);
-  be->gemm_tn(K, 1, nobs, 1.0, E.p, nobs, xb.p, nobs, 0.0, w.p, K);     // w_i = dot(eta_i, xi_bar)
-  be->scal_copy(n, beta_bar, Xd.p, sd.p);                               // s = X * beta_bar      direct.jl:61
-  be->gemm_nn(n, 1, K, 1.0, Zdev, n, w.p, K, 1.0, sd.p, n);             // s += sum_i xis[i]*w_i  direct.jl:62-65
-  be->download2d(s_out, n, sd.p, n, n, 1);
-}
-}  // namespace
-
 int gsi_pcga_params(gsi_ctx* ctx, const double* Z, int64_t n, int64_t K, const double* s, const double* X,
                     double delta, double* out) {
   return guarded([&] {
@@ -1122,7 +1109,7 @@ int gsi_pcga_params(gsi_ctx* ctx, const double* Z, int64_t n, int64_t K, const d
     REQUIRE(n >= 1 && K >= 1, "bad shape");
     Buf Zd(ctx->c.be.get(), (size_t)n * K);
     ctx->c.be->upload2d(Zd.p, n, Z, n, n, K);
-    pcga_params_impl(ctx->c, Zd.p, n, K, s, X, delta, out);
+    basis_params(ctx->c, BasisRef{Zd.p, 64, n, K}, s, X, delta, out);
   });
 }
 
@@ -1133,7 +1120,7 @@ int gsi_pcga_update(gsi_ctx* ctx, const double* Z, int64_t n, int64_t K, const d
     REQUIRE(n >= 1 && K >= 1 && nobs >= 1, "bad shape");
     Buf Zd(ctx->c.be.get(), (size_t)n * K);
     ctx->c.be->upload2d(Zd.p, n, Z, n, n, K);
-    pcga_update_impl(ctx->c, Zd.p, n, K, X, beta_bar, etas, nobs, xi_bar, s_out);
+    basis_update(ctx->c, BasisRef{Zd.p, 64, n, K}, X, beta_bar, etas, nobs, xi_bar, s_out);
   });
 }
 
@@ -1142,7 +1129,7 @@ int gsi_pcga_params_dev(gsi_ctx* ctx, const gsi_mat* basis, int64_t K, const dou
   return guarded([&] {
     REQUIRE(ctx && basis && s && X && out, "NULL argument");
     REQUIRE(basis->ctx == ctx && K >= 1 && K <= basis->cols, "bad basis / K");
-    pcga_params_impl(ctx->c, basis->buf.p, basis->rows, K, s, X, delta, out);
+    basis_params(ctx->c, BasisRef{basis->buf.p, 64, basis->rows, K}, s, X, delta, out);
   });
 }
 
@@ -1151,7 +1138,7 @@ int gsi_pcga_update_dev(gsi_ctx* ctx, const gsi_mat* basis, int64_t K, const dou
   return guarded([&] {
     REQUIRE(ctx && basis && X && etas && xi_bar && s_out, "NULL argument");
     REQUIRE(basis->ctx == ctx && K >= 1 && K <= basis->cols && nobs >= 1, "bad basis / K / nobs");
-    pcga_update_impl(ctx->c, basis->buf.p, basis->rows, K, X, beta_bar, etas, nobs, xi_bar, s_out);
+    basis_update(ctx->c, BasisRef{basis->buf.p, 64, basis->rows, K}, X, beta_bar, etas, nobs, xi_bar, s_out);
   });
 }
 
@@ -1235,33 +1222,26 @@ int gsi_pcgamat_lsqr(gsi_ctx* ctx, const gsi_pcgamat* mat, const double* b, doub
 }
 
 int gsi_pcgamat_solve(gsi_ctx* ctx, const gsi_pcgamat* mat, const double* b, double* x_out, int64_t* info_out) {
-  int64_t info2[2] = {0, 0};
-  const int st = guarded([&] {
+  return with_info(info_out, [&](PathInfo& info) {
     REQUIRE(ctx && mat && b && x_out, "gsi_pcgamat_solve: NULL argument");
     REQUIRE(mat->ctx == ctx, "gsi_pcgamat_solve: the matrix belongs to another context");
     if (mat->A.nobs > 32768)
       throw Error(GSI_ERR_ARG, "gsi_pcgamat_solve: nobs = " + std::to_string(mat->A.nobs) +
                                    " is beyond the 32768 the direct solver takes (its workspace is (nobs + 2) x nobs doubles)");
-    mat->A.solve(b, x_out, info2);
+    mat->A.solve(b, x_out, info);
     check_async_errors(ctx->c);
   });
-  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
-  return st;
 }
 
 int gsi_chol_lower(gsi_ctx* ctx, const double* A, int64_t n, int64_t lda, double* L_out, int64_t* info_out) {
-  int64_t info2[2] = {0, 0};
-  const int st = guarded([&] {
+  return with_info(info_out, [&](PathInfo& info) {
     REQUIRE(ctx && A && L_out, "gsi_chol_lower: NULL argument");
     REQUIRE(n >= 1 && lda >= n, "gsi_chol_lower: need n >= 1 and lda >= n");
     REQUIRE(n <= 32768, "gsi_chol_lower: n is beyond 32768");
-    chol_lower_host_matrix(ctx->c, A, n, lda, L_out, info2);
+    chol_lower_host_matrix(ctx->c, A, n, lda, L_out, info);
     check_async_errors(ctx->c);
-    if (info2[0] != 0)
-      throw Error(GSI_ERR_NOT_POSDEF, "PosDefException: matrix is not positive definite; Cholesky failed at " + std::to_string(info2[0]));
+    throw_chol_outcome(info, info.column, false, nullptr);
   });
-  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
-  return st;
 }
 
 // ---- xi-basis objects ------------------------------------------------------------------
@@ -1297,36 +1277,14 @@ int gsi_pcga_params_basis(gsi_ctx* ctx, const gsi_basis* basis, const double* s,
                           double* out) {
   return guarded([&] {
     REQUIRE(ctx && basis && s && X && out && basis->ctx == ctx, "bad argument");
-    if (basis->precision == 64) {
-      pcga_params_impl(ctx->c, basis->Z64, basis->n, basis->K, s, X, delta, out);
-      return;
-    }
-    Backend* be = ctx->c.be.get();
-    const int64_t n = basis->n, K = basis->K;
-    Buf O(be, (size_t)n * (K + 3)), sv(be, (size_t)n), Xv(be, (size_t)n);
-    be->upload2d(sv.p, n, s, n, n, 1);
-    be->upload2d(Xv.p, n, X, n, n, 1);
-    be->pcga_params_f32(basis->buf32.p, n, K, sv.p, Xv.p, delta, O.p);
-    be->download2d(out, n, O.p, n, n, K + 3);
+    basis_params(ctx->c, basis->ref(), s, X, delta, out);
   });
 }
 int gsi_pcga_update_basis(gsi_ctx* ctx, const gsi_basis* basis, const double* X, double beta_bar, const double* etas,
                           int64_t nobs, const double* xi_bar, double* s_out) {
   return guarded([&] {
     REQUIRE(ctx && basis && X && etas && xi_bar && s_out && basis->ctx == ctx && nobs >= 1, "bad argument");
-    if (basis->precision == 64) {
-      pcga_update_impl(ctx->c, basis->Z64, basis->n, basis->K, X, beta_bar, etas, nobs, xi_bar, s_out);
-      return;
-    }
-    Backend* be = ctx->c.be.get();
-    const int64_t n = basis->n, K = basis->K;
-    Buf E(be, (size_t)nobs * K), xb(be, (size_t)nobs), w(be, (size_t)K), sd(be, (size_t)n), Xd(be, (size_t)n);
-    be->upload2d(E.p, nobs, etas, nobs, nobs, K);
-    be->upload2d(xb.p, nobs, xi_bar, nobs, nobs, 1);
-    be->upload2d(Xd.p, n, X, n, n, 1);
-    be->gemm_tn(K, 1, nobs, 1.0, E.p, nobs, xb.p, nobs, 0.0, w.p, K);          // w_i = dot(eta_i, xi_bar)
-    be->basis_gemv_f32(basis->buf32.p, n, K, w.p, beta_bar, Xd.p, sd.p);      // s = X beta_bar + sum_i xis[i] w_i
-    be->download2d(s_out, n, sd.p, n, n, 1);
+    basis_update(ctx->c, basis->ref(), X, beta_bar, etas, nobs, xi_bar, s_out);
   });
 }
 int gsi_basis_download_col(gsi_ctx* ctx, const gsi_basis* basis, int64_t col, double* host) {
@@ -1391,8 +1349,7 @@ int gsi_pcga_forward_basis(gsi_ctx* ctx, const gsi_basis* basis, const gsi_fwd* 
     if (fwd->m.n != basis->n)
       throw Error(GSI_ERR_ARG, "gsi_pcga_forward_basis: the forward model has n = " + std::to_string(fwd->m.n) +
                                    ", the basis n = " + std::to_string(basis->n));
-    const void* Z = basis->precision == 64 ? (const void*)basis->Z64 : (const void*)basis->buf32.p;
-    fwd_forward_basis(ctx->c, fwd->m, Z, basis->precision, basis->K, s, X, delta, results_out);
+    fwd_forward_basis(ctx->c, fwd->m, basis->ref(), s, X, delta, results_out);
     check_async_errors(ctx->c);
   });
 }
@@ -1400,18 +1357,14 @@ int gsi_pcga_forward_basis(gsi_ctx* ctx, const gsi_basis* basis, const gsi_fwd* 
 // ---- the posterior variance from the resident basis ------------------------------
 int gsi_basis_quadform(gsi_ctx* ctx, const gsi_basis* basis, const double* W, int64_t ldw, int64_t ncols, int upper,
                        const double* u, double* a_out, double* q_out, double* t_out, int64_t* info_out) {
-  int64_t info2[2] = {0, 0};
-  const int st = guarded([&] {
+  return with_info(info_out, [&](PathInfo& info) {
     REQUIRE(ctx && basis && W && a_out, "gsi_basis_quadform: NULL argument");
     REQUIRE((u == nullptr) == (t_out == nullptr), "gsi_basis_quadform: u and t_out go together");
     REQUIRE(basis->ctx == ctx, "gsi_basis_quadform: the basis belongs to another context");
     REQUIRE(ncols >= 1 && ldw >= basis->K, "gsi_basis_quadform: need ncols >= 1 and ldw >= K");
-    const void* Z = basis->precision == 64 ? (const void*)basis->Z64 : (const void*)basis->buf32.p;
-    basis_quadform(ctx->c, Z, basis->precision, basis->n, basis->K, W, ldw, ncols, upper != 0, u, a_out, q_out, t_out, info2);
+    basis_quadform(ctx->c, basis->ref(), W, ldw, ncols, upper != 0, u, a_out, q_out, t_out, info);
     check_async_errors(ctx->c);
   });
-  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
-  return st;
 }
 
 namespace {
@@ -1424,22 +1377,18 @@ void require_posterior_shape(const gsi_pcgamat* mat, const char* who) {
 
 int gsi_pcgamat_posterior(gsi_ctx* ctx, const gsi_pcgamat* mat, double* W_out, double* u_out, double* gamma_out,
                           int64_t* info_out) {
-  int64_t info2[2] = {0, 0};
-  const int st = guarded([&] {
+  return with_info(info_out, [&](PathInfo& info) {
     REQUIRE(ctx && mat && W_out && u_out && gamma_out, "gsi_pcgamat_posterior: NULL argument");
     REQUIRE(mat->ctx == ctx, "gsi_pcgamat_posterior: the matrix belongs to another context");
     require_posterior_shape(mat, "gsi_pcgamat_posterior");
-    posterior_factor(mat->A, W_out, u_out, gamma_out, info2);
+    posterior_factor(mat->A, W_out, u_out, gamma_out, info);
     check_async_errors(ctx->c);
   });
-  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
-  return st;
 }
 
 int gsi_pcga_posterior_variance(gsi_ctx* ctx, const gsi_basis* basis, const gsi_pcgamat* mat, const double* X,
                                 const double* prior, double* var_out, int64_t* info_out) {
-  int64_t info2[2] = {0, 0};
-  const int st = guarded([&] {
+  return with_info(info_out, [&](PathInfo& info) {
     REQUIRE(ctx && basis && mat && X && var_out, "gsi_pcga_posterior_variance: NULL argument");
     REQUIRE(basis->ctx == ctx, "gsi_pcga_posterior_variance: the basis belongs to another context");
     REQUIRE(mat->ctx == ctx, "gsi_pcga_posterior_variance: the matrix belongs to another context");
@@ -1447,12 +1396,9 @@ int gsi_pcga_posterior_variance(gsi_ctx* ctx, const gsi_basis* basis, const gsi_
       throw Error(GSI_ERR_ARG, "gsi_pcga_posterior_variance: the matrix has K = " + std::to_string(mat->A.K) +
                                    ", the basis K = " + std::to_string(basis->K));
     require_posterior_shape(mat, "gsi_pcga_posterior_variance");
-    const void* Z = basis->precision == 64 ? (const void*)basis->Z64 : (const void*)basis->buf32.p;
-    posterior_variance(ctx->c, Z, basis->precision, basis->n, basis->K, mat->A, X, prior, var_out, info2);
+    posterior_variance(ctx->c, basis->ref(), mat->A, X, prior, var_out, info);
     check_async_errors(ctx->c);
   });
-  if (info_out) { info_out[0] = info2[0]; info_out[1] = info2[1]; }
-  return st;
 }
 
 // ---- measurement ---------------------------------------------------------------------

@@ -397,13 +397,13 @@ class Backend {
 
   // ---- sparse forward model on the device (FwdProduct above) ----
   // Returns the form that computed a.out -- 1: one lane per output, 2: one wave per segment -- or 0: "not mine", nothing
-  // ran, and pipeline.cpp forms the batch with pcga_params and multiplies on the host.
+  // ran, and pcga.cpp forms the batch with pcga_params and multiplies on the host.
   virtual int fwd_products(const FwdProduct& a) { (void)a; return 0; }
 
   // ---- pcgadirect's saddle-point system by Cholesky ----
   // The m x n trapezoid A (m >= n, ld; lower triangle of the top n x n read) <- [L; (L^-1 B')'] in place, B = rows n .. m-1.
   // Returns 0, the 1-based column at which the matrix stopped being positive definite (A is then partly factored), or
-  // -1: "not mine", nothing ran, and pipeline.cpp factors on the host (saddle_host.hpp).
+  // -1: "not mine", nothing ran, and pcga.cpp factors on the host (saddle_host.hpp).
   virtual int64_t chol_lower(double* A, int64_t m, int64_t n, int64_t ld) { (void)A; (void)m; (void)n; (void)ld; return -1; }
   // x (nobs + 1) = [(E E' + R) HX; HX' 0] \ b with E nobs x K (ld nobs), R dense (ld nobs) or its diagonal: formation,
   // chol_lower with HX' and b1' carried as rows nobs, nobs + 1, beta = (w'v - b2) / (w'w), xi = L^-T (v - beta w).
@@ -418,7 +418,7 @@ class Backend {
   // One pass over the rows z_i of the basis Z (n x K, ld ldz; zbits 64: double, 32: float widened per element), every sum in
   // fp64:  a[i] = |W' z_i|^2 for W (K x ncols, ld ldw; upper: W[k, j] with k > j is zero and never read),
   // q[i] = |z_i|^2 (q may be null), t[i] = u' z_i (u and t null together).  Z W is never formed.
-  // Returns 1, or 0: "not mine", nothing ran, and pipeline.cpp runs posterior_host.hpp on a downloaded basis.
+  // Returns 1, or 0: "not mine", nothing ran, and pcga.cpp runs posterior_host.hpp on a downloaded basis.
   virtual int basis_quadform(const void* Z, int zbits, int64_t n, int64_t ldz, int64_t K, const double* W, int64_t ldw,
                              int64_t ncols, bool upper, const double* u, double* a, double* q, double* t) {
     (void)Z; (void)zbits; (void)n; (void)ldz; (void)K; (void)W; (void)ldw; (void)ncols; (void)upper; (void)u; (void)a; (void)q;

@@ -1,5 +1,5 @@
 // fwd_plan.hpp -- the segment table of a sparse forward model (gsi_fwd).  Host only, no backend:
-// the kernels of pcga_forward.hip, the host path of pipeline.cpp and a stand-alone test program read the same table.
+// the kernels of pcga_forward.hip, the host path of pcga.cpp and a stand-alone test program read the same table.
 //
 // The nonzeros of the CSR rows are cut into SEGMENTS of at most `limit` nonzeros.  A row of at most `limit` nonzeros
 // (an empty one too) is one segment; a longer row of L nonzeros becomes ceil(L / limit) segments of nearly equal length,

@@ -1,0 +1,90 @@
+// pcga.hpp -- the PCGA consumers over a gsi::Backend (DESIGN.md sections 4.7 - 4.7d): the saddle-point matrix and its
+// Cholesky solve, the posterior variance from the resident basis, the sparse forward model, and the two products of the
+// iteration with that basis.  Each consumer asks the backend first; when it answers "not mine", or the consumer's
+// GSI_*_HOST switch is set (read at each call), the operands are downloaded and the host restatement runs.  No kernel code here.
+#pragma once
+#include "pipeline.hpp"
+#include "fwd_plan.hpp"
+
+namespace gsi {
+
+// What ran, as the C ABI's info_out[2] reports it: column is 0 or the 1-based column at which a Cholesky factorization stopped
+// being positive definite; path is PATH_BACKEND for the backend's kernels, PATH_HOST for the host path (the backend declined,
+// or the switch was set), 0 when neither was reached.
+struct PathInfo {
+  int64_t column = 0;
+  int64_t path = 0;
+};
+enum : int64_t { PATH_BACKEND = 1, PATH_HOST = 3 };
+// GSI_ERR_NOT_POSDEF naming col (recorded in info.column) when col > 0; else GSI_ERR_SINGULAR with singular_text when
+// `singular`; else nothing
+void throw_chol_outcome(PathInfo& info, int64_t col, bool singular, const char* singular_text);
+
+// The resident xi-basis: Z in backend memory, n x K, ld n; bits 64: double, 32: float in a double-typed allocation.
+struct BasisRef {
+  const void* Z;
+  int bits;
+  int64_t n, K;
+};
+// out (host, n x (K + 3), ld n) = paramstorun of direct.jl:39-45 / lsqr.jl:37-43; s and X on the host
+void basis_params(Context& c, BasisRef Z, const double* s, const double* X, double delta, double* out);
+// s_out (host, n) = X beta_bar + sum_i xis[i] dot(eta_i, xi_bar)  (direct.jl:59-65); X, etas (nobs x K, ld nobs), xi_bar on the host
+void basis_update(Context& c, BasisRef Z, const double* X, double beta_bar, const double* etas, int64_t nobs,
+                  const double* xi_bar, double* s_out);
+
+// PCGALowRankMatrix(etas, HX, R)  (lowrank.jl:32-36, 83-97): [(HQH + R) HX; HX' 0], HQH = sum eta_i eta_i' kept implicit.
+struct PcgaLowRank {
+  Context* ctx = nullptr;
+  int64_t nobs = 0, K = 0;
+  Buf E, HX, R;        // E: nobs x K (eta_i as columns); R: nobs x nobs dense, or nobs values when r_diag
+  bool r_diag = false;
+  void mul(const double* x, double* y) const;   // x, y: nobs + 1
+  // x = A \ b (host vectors, nobs + 1) by Cholesky of HQH + R (direct.jl:56-58 for a positive definite HQH + R; DESIGN.md
+  // section 4.7c; GSI_SADDLE_HOST).  Throws GSI_ERR_NOT_POSDEF or GSI_ERR_SINGULAR (w'w == 0 or a non-finite beta) with info filled.
+  void solve(const double* b, double* x, PathInfo& info) const;
+};
+// cholesky(Symmetric(A, :L)).L of a host matrix (n x n, lda) into L (n x n, ld n, strictly upper triangle zero).
+// A failed factorization fills info, leaves L unspecified and does not throw.
+void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda, double* L, PathInfo& info);
+
+// ---- the posterior variance from the resident basis (GSI_POST_HOST) ----
+// a[i] = |W' z_i|^2, q[i] = |z_i|^2 (q may be null), t[i] = u' z_i (u, t null together) over the rows of the basis.
+// W (K x ncols, ld ldw), u and the outputs are host arrays.
+void basis_quadform(Context& c, BasisRef Z, const double* W, int64_t ldw, int64_t ncols, bool upper, const double* u,
+                    double* a, double* q, double* t, PathInfo& info);
+// W (K x K upper triangular), u (K), gamma of the capacitance form, from the matrix's E, HX and R; host outputs (any may be
+// null).  Wdev / udev (may be null): on the backend's path W and u are also left there for the row pass (empty on the host
+// path).  Throws GSI_ERR_NOT_POSDEF (info.column = the failing column of R) or GSI_ERR_SINGULAR.
+void posterior_factor(const PcgaLowRank& A, double* W, double* u, double* gamma, PathInfo& info, Buf* Wdev = nullptr,
+                      Buf* udev = nullptr);
+// var (n, host) by the two row formulas of section 4.7d; X (n) and prior (n, or null: the low-rank prior |z_i|^2) on the host
+void posterior_variance(Context& c, BasisRef Z, const PcgaLowRank& A, const double* X, const double* prior, double* var,
+                        PathInfo& info);
+
+// A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
+// vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
+// double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.
+struct FwdModel {
+  Context* ctx = nullptr;
+  int64_t nobs = 0, n = 0, nnz = 0, seg_limit = 0;
+  int link = 0;
+  std::vector<int64_t> rowptr;
+  std::vector<int32_t> colidx;
+  std::vector<double> vals, w;     // w empty: ones
+  FwdPlan plan;
+  Buf d_segptr, d_rowseg, d_colidx, d_vals, d_w;
+  // what ran (gsi_fwd_info): form of the last product (0 none yet, 1 lane-per-output, 2 wave-per-segment, 3 host path),
+  // products that took the host path, products in total
+  mutable int64_t last_form = 0, host_products = 0, products = 0;
+};
+enum : int64_t { FWD_DEFAULT_SEG_LIMIT = 16384 };   // nonzeros per segment, from the sweep of DESIGN.md section 4.7b; GSI_FWD_SEG overrides
+// Validates (GSI_ERR_ARG naming the offending row or entry, before anything is allocated), plans and uploads.
+void fwd_create(Context& c, FwdModel& F, int64_t nobs, int64_t n, const int64_t* rowptr, const int64_t* colidx,
+                const double* vals, const double* weights, int link);
+// out (host, nobs x (K + 3), ld nobs): column c = h(column c of paramstorun) for the basis, s and X on the host.  The
+// backend's kernels, or -- when it declines or GSI_FWD_HOST=1 -- basis_params and a host CSR loop.
+void fwd_forward_basis(Context& c, const FwdModel& F, BasisRef Z, const double* s, const double* X, double delta, double* out);
+// out (host, nobs x ncols, ld ldo): column c = h(P[:, c]) for the host matrix P (n x ncols, ld ldp)
+void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo);
+
+}  // namespace gsi

@@ -12,8 +12,6 @@
 //                QR of the stack, local fix-up Q_g <- Q_g * Q2_g
 #include "pipeline.hpp"
 #include "lsqr_state.hpp"
-#include "saddle_host.hpp"
-#include "posterior_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1131,292 +1129,6 @@ int64_t lowrank_solve(const Operator& A, const double* b, double* x) {
   return lsqr(c, L, b, x, A.N);                        // maxiter = length(A.samples)   lowrank.jl:142
 }
 
-// v[1:end-1] = R xs + sum_i eta_i dot(eta_i, xs) + HX x[end];  v[end] = dot(HX, xs)      lowrank.jl:83-97
-void PcgaLowRank::mul(const double* x, double* y) const {
-  Backend* be = ctx->be.get();
-  Buf t(be, (size_t)K);
-  be->gemv_t(nobs, K, 1.0, E.p, nobs, x, t.p);                                    // t_i = dot(eta_i, xs)
-  be->gemv_n(nobs, K, 1.0, E.p, nobs, t.p, 0.0, y);                               // sum_i eta_i t_i
-  if (r_diag) be->diag_mul_add(nobs, R.p, x, y);                                  // + R xs
-  else be->gemv_n(nobs, nobs, 1.0, R.p, nobs, x, 1.0, y);
-  be->gemv_n(nobs, 1, 1.0, HX.p, nobs, x + nobs, 1.0, y);                         // + HX x[end]
-  be->gemv_t(nobs, 1, 1.0, HX.p, nobs, x, y + nobs);                              // dot(HX, xs)
-}
-
-// ---- the saddle-point system by Cholesky ------------------------------------------------------
-namespace {
-bool saddle_host_forced() {
-  const char* e = getenv("GSI_SADDLE_HOST");
-  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
-}
-std::string not_posdef_message(int64_t col) {
-  return "PosDefException: matrix is not positive definite; Cholesky failed at " + std::to_string(col);
-}
-const char* const kSaddleSingular =
-    "SingularException: the saddle-point matrix [(HQH + R) HX; HX' 0] is singular (HX' (HQH + R)^-1 HX is zero or not finite)";
-}  // namespace
-
-void PcgaLowRank::solve(const double* b, double* x, int64_t* info2) const {
-  Backend* be = ctx->be.get();
-  const int64_t n1 = nobs + 1;
-  info2[0] = 0;
-  info2[1] = 0;
-  if (!saddle_host_forced()) {
-    Buf bd(be, (size_t)n1), xd(be, (size_t)n1);
-    be->upload2d(bd.p, n1, b, n1, n1, 1);
-    bool singular = false;
-    const int64_t col = be->saddle_solve(E.p, nobs, K, HX.p, R.p, r_diag, bd.p, xd.p, &singular);
-    if (col != -1) {
-      info2[1] = 1;
-      if (col > 0) {
-        info2[0] = col;
-        throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
-      }
-      if (singular) throw Error(GSI_ERR_SINGULAR, kSaddleSingular);
-      be->download2d(x, n1, xd.p, n1, n1, 1);
-      return;
-    }
-  }
-  // the host path: the operands as gsi_pcgamat_create stored them, downloaded, and the same algebra (saddle_host.hpp)
-  info2[1] = 3;
-  std::vector<double> Eh((size_t)nobs * K), HXh((size_t)nobs), Rh(r_diag ? (size_t)nobs : (size_t)nobs * nobs);
-  be->download2d(Eh.data(), nobs, E.p, nobs, nobs, K);
-  be->download2d(HXh.data(), nobs, HX.p, nobs, nobs, 1);
-  if (r_diag) be->download2d(Rh.data(), nobs, R.p, nobs, nobs, 1);
-  else be->download2d(Rh.data(), nobs, R.p, nobs, nobs, nobs);
-  const int64_t col = saddle_host::solve(Eh.data(), nobs, K, HXh.data(), Rh.data(), r_diag, b, x);
-  if (col > 0) {
-    info2[0] = col;
-    throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
-  }
-  if (col != 0) throw Error(GSI_ERR_SINGULAR, kSaddleSingular);
-}
-
-void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda, double* L, int64_t* info2) {
-  Backend* be = c.be.get();
-  info2[0] = 0;
-  info2[1] = 0;
-  int64_t col = -1;
-  if (!saddle_host_forced()) {
-    Buf W(be, (size_t)n * n);
-    be->upload2d(W.p, n, A, lda, n, n);
-    col = be->chol_lower(W.p, n, n, n);
-    if (col != -1) {
-      info2[1] = 1;
-      be->download2d(L, n, W.p, n, n, n);
-    }
-  }
-  if (col == -1) {
-    info2[1] = 3;
-    for (int64_t j = 0; j < n; ++j)
-      for (int64_t i = 0; i < n; ++i) L[i + j * n] = A[i + j * lda];
-    col = saddle_host::chol_lower(L, n, n, n);
-  }
-  info2[0] = col;
-  for (int64_t j = 1; j < n; ++j)
-    for (int64_t i = 0; i < j; ++i) L[i + j * n] = 0.0;
-}
-
-// ---- the posterior variance from the resident basis -------------------------------------------
-namespace {
-bool post_host_forced() {
-  const char* e = getenv("GSI_POST_HOST");
-  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
-}
-const char* const kPostSingular =
-    "SingularException: the posterior needs HX' (HQH + R)^-1 HX positive and finite (HX is zero, or the operands are not finite)";
-
-// The basis on the host, as the values it stores: fp64 as they are, fp32 as the floats of the double-typed allocation.
-void download_basis(Backend* be, const void* Z, int zbits, int64_t n, int64_t K, std::vector<double>& store) {
-  const size_t count = (size_t)n * (size_t)K;
-  const size_t doubles = zbits == 32 ? (count + 1) / 2 : count;
-  store.resize(doubles);
-  be->download2d(store.data(), (int64_t)doubles, (const double*)Z, (int64_t)doubles, (int64_t)doubles, 1);
-}
-
-void quadform_host(Backend* be, const void* Z, int zbits, int64_t n, int64_t K, const double* W, int64_t ldw, int64_t ncols,
-                   bool upper, const double* u, double* a, double* q, double* t) {
-  std::vector<double> store;
-  download_basis(be, Z, zbits, n, K, store);
-  if (zbits == 32)
-    posterior_host::quadform((const float*)(const void*)store.data(), n, n, K, W, ldw, ncols, upper, u, a, q, t);
-  else
-    posterior_host::quadform(store.data(), n, n, K, W, ldw, ncols, upper, u, a, q, t);
-}
-}  // namespace
-
-void basis_quadform(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const double* W, int64_t ldw, int64_t ncols,
-                    bool upper, const double* u, double* a, double* q, double* t, int64_t* info2) {
-  Backend* be = c.be.get();
-  info2[0] = 0;
-  info2[1] = 0;
-  if (!post_host_forced()) {
-    Buf Wd(be, (size_t)K * (size_t)ncols), ud(be, (size_t)K), out(be, (size_t)n * 3);
-    if (upper) {                                       // only the promised part travels: what lies below may be anything
-      std::vector<double> Wu((size_t)K * (size_t)ncols, 0.0);
-      for (int64_t j = 0; j < ncols; ++j)
-        for (int64_t k = 0; k < K && k <= j; ++k) Wu[(size_t)(k + j * K)] = W[k + j * ldw];
-      be->upload2d(Wd.p, K, Wu.data(), K, K, ncols);
-    } else {
-      be->upload2d(Wd.p, K, W, ldw, K, ncols);
-    }
-    if (u) be->upload2d(ud.p, K, u, K, K, 1);
-    double* ad = out.p;
-    double* qd = q ? out.p + n : nullptr;
-    double* td = u ? out.p + 2 * n : nullptr;
-    int ran = 0;
-    {
-      ScopedPhase ph(be, PH_OTHER);                    // (profiling: the row pass alone; tools/pcga_posterior_bench.py)
-      ran = be->basis_quadform(Z, zbits, n, n, K, Wd.p, K, ncols, upper, u ? ud.p : nullptr, ad, qd, td);
-    }
-    if (ran != 0) {
-      info2[1] = 1;
-      be->download2d(a, n, ad, n, n, 1);
-      if (q) be->download2d(q, n, qd, n, n, 1);
-      if (u) be->download2d(t, n, td, n, n, 1);
-      return;
-    }
-  }
-  info2[1] = 3;
-  quadform_host(be, Z, zbits, n, K, W, ldw, ncols, upper, u, a, q, t);
-}
-
-void posterior_factor(const PcgaLowRank& A, double* W, double* u, double* gamma, int64_t* info2, Buf* Wdev, Buf* udev) {
-  Backend* be = A.ctx->be.get();
-  const int64_t nobs = A.nobs, K = A.K;
-  info2[0] = 0;
-  info2[1] = 0;
-  // the backend's path: scale_rows or one chol_lower for B and wt, the TN product for N, chol_lower on [N; I] for W
-  bool mine = !post_host_forced();
-  if (mine) {
-    Buf B(be, (size_t)nobs * (size_t)K), wt(be, (size_t)nobs);
-    if (A.r_diag) {
-      std::vector<double> d((size_t)nobs);
-      be->download2d(d.data(), nobs, A.R.p, nobs, nobs, 1);
-      for (int64_t i = 0; i < nobs; ++i) {
-        if (!(d[(size_t)i] > 0.0) || !std::isfinite(d[(size_t)i])) {
-          info2[0] = i + 1;
-          info2[1] = 1;
-          throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(i + 1));
-        }
-        d[(size_t)i] = 1.0 / std::sqrt(d[(size_t)i]);
-      }
-      Buf dd(be, (size_t)nobs);
-      be->upload2d(dd.p, nobs, d.data(), nobs, nobs, 1);
-      mine = be->scale_rows(nobs, K, dd.p, A.E.p, nobs, B.p, nobs) != 0 &&
-             be->scale_rows(nobs, 1, dd.p, A.HX.p, nobs, wt.p, nobs) != 0;
-    } else {
-      // [R; E'; w'] (nobs + K + 1 rows): the carried rows are transposed on the host, they are (K + 1) x nobs numbers
-      const int64_t kc = K + 1, ld = nobs + kc;
-      std::vector<double> Eh((size_t)nobs * (size_t)kc), C((size_t)kc * (size_t)nobs);
-      be->download2d(Eh.data(), nobs, A.E.p, nobs, nobs, K);
-      be->download2d(Eh.data() + (size_t)nobs * (size_t)K, nobs, A.HX.p, nobs, nobs, 1);
-      for (int64_t j = 0; j < nobs; ++j)
-        for (int64_t cix = 0; cix < kc; ++cix) C[(size_t)(cix + j * kc)] = Eh[(size_t)(j + cix * nobs)];
-      Buf T(be, (size_t)ld * (size_t)nobs);
-      be->copy2d(T.p, ld, A.R.p, nobs, nobs, nobs);
-      be->upload2d(T.p + nobs, ld, C.data(), kc, kc, nobs);
-      const int64_t col = be->chol_lower(T.p, ld, nobs, ld);
-      if (col == -1) {
-        mine = false;
-      } else {
-        if (col > 0) {
-          info2[0] = col;
-          info2[1] = 1;
-          throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
-        }
-        be->download2d(C.data(), kc, T.p + nobs, ld, kc, nobs);
-        for (int64_t j = 0; j < nobs; ++j)
-          for (int64_t cix = 0; cix < kc; ++cix) Eh[(size_t)(j + cix * nobs)] = C[(size_t)(cix + j * kc)];
-        be->upload2d(B.p, nobs, Eh.data(), nobs, nobs, K);
-        be->upload2d(wt.p, nobs, Eh.data() + (size_t)nobs * (size_t)K, nobs, nobs, 1);
-      }
-    }
-    if (mine) {
-      const int64_t ld2 = 2 * K;
-      std::vector<double> T2h((size_t)ld2 * (size_t)K, 0.0);
-      for (int64_t j = 0; j < K; ++j) T2h[(size_t)(j + j * ld2)] = T2h[(size_t)(K + j + j * ld2)] = 1.0;
-      Buf T2(be, (size_t)ld2 * (size_t)K);
-      be->upload2d(T2.p, ld2, T2h.data(), ld2, ld2, K);
-      be->gemm_tn(K, K, nobs, 1.0, B.p, nobs, B.p, nobs, 1.0, T2.p, ld2);          // N = I + B'B
-      const int64_t col = be->chol_lower(T2.p, ld2, K, ld2);
-      if (col == -1) {
-        mine = false;
-      } else {
-        info2[1] = 1;
-        if (col != 0) throw Error(GSI_ERR_SINGULAR, kPostSingular);                // N >= I: only non-finite operands
-        Buf Wd(be, (size_t)K * (size_t)K), r(be, (size_t)K), y(be, (size_t)K), ud(be, (size_t)K);
-        be->copy2d(Wd.p, K, T2.p + K, ld2, K, K);                                  // W = L_N^-T
-        be->gemv_t(nobs, K, 1.0, B.p, nobs, wt.p, r.p);                            // r = B'wt
-        be->gemv_t(K, K, 1.0, Wd.p, K, r.p, y.p);                                  // u = W (W'r)
-        be->gemv_n(K, K, 1.0, Wd.p, K, y.p, 0.0, ud.p);
-        const double ww = be->dot(nobs, wt.p, wt.p);
-        const double g = ww - be->dot(K, r.p, ud.p);
-        if (!(ww > 0.0) || !std::isfinite(g) || !(g > 0.0)) throw Error(GSI_ERR_SINGULAR, kPostSingular);
-        if (gamma) *gamma = g;
-        if (W) {
-          be->download2d(W, K, Wd.p, K, K, K);
-          for (int64_t j = 0; j < K; ++j)
-            for (int64_t i = j + 1; i < K; ++i) W[i + j * K] = 0.0;
-        }
-        if (u) be->download2d(u, K, ud.p, K, K, 1);
-        if (Wdev) *Wdev = std::move(Wd);
-        if (udev) *udev = std::move(ud);
-        return;
-      }
-    }
-  }
-  // the host path: the operands as gsi_pcgamat_create stored them, downloaded, and the same algebra (posterior_host.hpp)
-  info2[1] = 3;
-  std::vector<double> Eh((size_t)nobs * K), HXh((size_t)nobs), Rh(A.r_diag ? (size_t)nobs : (size_t)nobs * nobs);
-  be->download2d(Eh.data(), nobs, A.E.p, nobs, nobs, K);
-  be->download2d(HXh.data(), nobs, A.HX.p, nobs, nobs, 1);
-  if (A.r_diag) be->download2d(Rh.data(), nobs, A.R.p, nobs, nobs, 1);
-  else be->download2d(Rh.data(), nobs, A.R.p, nobs, nobs, nobs);
-  std::vector<double> Wh((size_t)K * (size_t)K), uh((size_t)K);
-  double g = 0.0;
-  const int64_t col = posterior_host::factor(Eh.data(), nobs, K, HXh.data(), Rh.data(), A.r_diag, Wh.data(), uh.data(), &g);
-  if (col > 0) {
-    info2[0] = col;
-    throw Error(GSI_ERR_NOT_POSDEF, not_posdef_message(col));
-  }
-  if (col != 0) throw Error(GSI_ERR_SINGULAR, kPostSingular);
-  if (W) std::copy(Wh.begin(), Wh.end(), W);
-  if (u) std::copy(uh.begin(), uh.end(), u);
-  if (gamma) *gamma = g;
-}
-
-void posterior_variance(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const PcgaLowRank& A, const double* X,
-                        const double* prior, double* var, int64_t* info2) {
-  Backend* be = c.be.get();
-  std::vector<double> Wh((size_t)K * (size_t)K), uh((size_t)K), a((size_t)n), q((size_t)n), t((size_t)n);
-  double gamma = 0.0;
-  Buf Wd, ud;
-  posterior_factor(A, Wh.data(), uh.data(), &gamma, info2, &Wd, &ud);
-  bool done = false;
-  if (!post_host_forced() && Wd.p != nullptr) {        // W and u are still on the device: they never leave it for the pass
-    Buf out(be, (size_t)n * 3);
-    int ran = 0;
-    {
-      ScopedPhase ph(be, PH_OTHER);
-      ran = be->basis_quadform(Z, zbits, n, n, K, Wd.p, K, K, true, ud.p, out.p, out.p + n, out.p + 2 * n);
-    }
-    if (ran != 0) {
-      be->download2d(a.data(), n, out.p, n, n, 1);
-      be->download2d(q.data(), n, out.p + n, n, n, 1);
-      be->download2d(t.data(), n, out.p + 2 * n, n, n, 1);
-      info2[1] = 1;
-      done = true;
-    }
-  }
-  if (!done) {
-    int64_t inf[2];
-    basis_quadform(c, Z, zbits, n, K, Wh.data(), K, K, true, uh.data(), a.data(), q.data(), t.data(), inf);
-    info2[1] = inf[1];
-  }
-  posterior_host::finish(n, a.data(), q.data(), t.data(), X, prior, gamma, var);
-}
-
 int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double epsilon, int64_t r,
                              double* Q_host) {
   Context& c = *A.ctx;
@@ -1465,155 +1177,6 @@ int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double 
   }
   if (j > 0) be->download2d(Q_host, m, Qfull.p, m, m, j);   // return Qfull[:, 1:j]           :47
   return j;
-}
-
-// ---- the sparse forward model (gsi_fwd) ------------------------------------------------------
-namespace {
-template <class T>
-void upload_as_doubles(Backend* be, Buf& dst, const T* src, size_t count) {
-  // integers travel as the bytes of a double-typed allocation: every transfer is a byte copy
-  const size_t nd = (count * sizeof(T) + sizeof(double) - 1) / sizeof(double);
-  std::vector<double> stage(std::max<size_t>(nd, 1), 0.0);
-  if (count) std::memcpy(stage.data(), src, count * sizeof(T));
-  dst = Buf(be, stage.size());
-  be->upload2d(dst.p, (int64_t)stage.size(), stage.data(), (int64_t)stage.size(), (int64_t)stage.size(), 1);
-}
-
-bool fwd_host_forced() {
-  const char* e = getenv("GSI_FWD_HOST");
-  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
-}
-
-// out[:, c] = h(P[:, c]) on the host, nonzeros of a row in storage order
-void fwd_host_csr(const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo) {
-  const bool has_w = !F.w.empty();
-  for (int64_t c = 0; c < ncols; ++c) {
-    const double* p = P + c * ldp;
-    for (int64_t r = 0; r < F.nobs; ++r) {
-      double acc = 0.0;
-      for (int64_t t = F.rowptr[(size_t)r]; t < F.rowptr[(size_t)r + 1]; ++t) {
-        const int64_t j = F.colidx[(size_t)t];
-        double a = (has_w ? F.w[(size_t)j] : 1.0) * p[j];
-        if (F.link) a = std::exp(a);
-        acc += F.vals[(size_t)t] * a;
-      }
-      out[r + c * ldo] = acc;
-    }
-  }
-}
-
-void fwd_fill(const FwdModel& F, FwdProduct& a) {
-  a.nobs = F.nobs; a.n = F.n; a.nnz = F.nnz; a.nseg = F.plan.nseg(); a.maxlen = F.plan.maxlen;
-  a.segptr = reinterpret_cast<const int64_t*>(F.d_segptr.p);
-  a.rowseg = F.plan.nsplit ? reinterpret_cast<const int64_t*>(F.d_rowseg.p) : nullptr;
-  a.colidx = reinterpret_cast<const int32_t*>(F.d_colidx.p);
-  a.vals = F.d_vals.p;
-  a.w = F.w.empty() ? nullptr : F.d_w.p;
-  a.link = F.link;
-}
-}  // namespace
-
-void fwd_create(Context& c, FwdModel& F, int64_t nobs, int64_t n, const int64_t* rowptr, const int64_t* colidx,
-                const double* vals, const double* weights, int link) {
-  auto bad = [](const std::string& m) { throw Error(GSI_ERR_ARG, "gsi_fwd_linear_create: " + m); };
-  if (nobs < 1 || n < 1) bad("nobs = " + std::to_string(nobs) + ", n = " + std::to_string(n) + ": both must be at least 1");
-  if (n >= ((int64_t)1 << 31)) bad("n = " + std::to_string(n) + " does not fit the 32-bit column indices (n < 2^31)");
-  if (link != 0 && link != 1) bad("link = " + std::to_string(link) + " (0: identity, 1: exp)");
-  if (!rowptr) bad("rowptr is NULL");
-  if (rowptr[0] != 0) bad("rowptr[0] = " + std::to_string(rowptr[0]) + ", not 0 (offsets are 0-based)");
-  for (int64_t r = 0; r < nobs; ++r)
-    if (rowptr[r + 1] < rowptr[r])
-      bad("rowptr decreases at row " + std::to_string(r) + ": " + std::to_string(rowptr[r]) + " -> " +
-          std::to_string(rowptr[r + 1]));
-  const int64_t nnz = rowptr[nobs];
-  if (nnz > 0 && (!colidx || !vals)) bad("colidx / vals is NULL");
-  for (int64_t r = 0; r < nobs; ++r)
-    for (int64_t t = rowptr[r]; t < rowptr[r + 1]; ++t)
-      if (colidx[t] < 0 || colidx[t] >= n)
-        bad("entry " + std::to_string(t) + " (row " + std::to_string(r) + ") has column index " + std::to_string(colidx[t]) +
-            " outside [0, " + std::to_string(n) + ")");
-  int64_t limit = FWD_DEFAULT_SEG_LIMIT;
-  if (const char* e = getenv("GSI_FWD_SEG")) {
-    if (e[0] != '\0') {
-      limit = atoll(e);
-      if (limit < 1) bad(std::string("GSI_FWD_SEG = '") + e + "': a segment holds at least one nonzero");
-    }
-  }
-  F.ctx = &c; F.nobs = nobs; F.n = n; F.nnz = nnz; F.link = link; F.seg_limit = limit;
-  F.rowptr.assign(rowptr, rowptr + nobs + 1);
-  F.colidx.resize((size_t)nnz);
-  for (int64_t t = 0; t < nnz; ++t) F.colidx[(size_t)t] = (int32_t)colidx[t];
-  F.vals.assign(vals, vals + nnz);
-  if (weights) F.w.assign(weights, weights + n);
-  F.plan = fwd_plan(rowptr, nobs, limit);
-  Backend* be = c.be.get();
-  upload_as_doubles(be, F.d_segptr, F.plan.segptr.data(), F.plan.segptr.size());
-  if (F.plan.nsplit) upload_as_doubles(be, F.d_rowseg, F.plan.rowseg.data(), F.plan.rowseg.size());
-  upload_as_doubles(be, F.d_colidx, F.colidx.data(), F.colidx.size());
-  F.d_vals = Buf(be, std::max<size_t>((size_t)nnz, 1));
-  if (nnz) be->upload2d(F.d_vals.p, nnz, F.vals.data(), nnz, nnz, 1);
-  if (weights) {
-    F.d_w = Buf(be, (size_t)n);
-    be->upload2d(F.d_w.p, n, F.w.data(), n, n, 1);
-  }
-}
-
-void fwd_forward_basis(Context& c, const FwdModel& F, const void* Z, int zbits, int64_t K, const double* s, const double* X,
-                       double delta, double* out) {
-  Backend* be = c.be.get();
-  const int64_t n = F.n, nobs = F.nobs, nc = K + 3;
-  F.products += 1;
-  Buf sv(be, (size_t)n), Xv(be, (size_t)n);
-  be->upload2d(sv.p, n, s, n, n, 1);
-  be->upload2d(Xv.p, n, X, n, n, 1);
-  if (!fwd_host_forced()) {
-    Buf O(be, (size_t)nobs * nc), part;
-    if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * nc);
-    FwdProduct a;
-    fwd_fill(F, a);
-    a.Z = Z; a.zbits = zbits; a.ldz = n; a.K = K; a.plain = false;
-    a.s = sv.p; a.X = Xv.p; a.delta = delta;
-    a.out = O.p; a.ldo = nobs; a.partial = part.p;
-    const int form = be->fwd_products(a);
-    if (form != 0) {
-      be->download2d(out, nobs, O.p, nobs, nobs, nc);
-      F.last_form = form;
-      return;
-    }
-  }
-  // the host path: the batch as direct.jl:39-45 forms it, downloaded, and the model applied column by column
-  Buf Pd(be, (size_t)n * nc);
-  if (zbits == 32) be->pcga_params_f32(Z, n, K, sv.p, Xv.p, delta, Pd.p);
-  else be->pcga_params((const double*)Z, n, K, sv.p, Xv.p, delta, Pd.p);
-  std::vector<double> P((size_t)n * nc);
-  be->download2d(P.data(), n, Pd.p, n, n, nc);
-  fwd_host_csr(F, P.data(), n, nc, out, nobs);
-  F.host_products += 1;
-  F.last_form = 3;
-}
-
-void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo) {
-  Backend* be = c.be.get();
-  const int64_t n = F.n, nobs = F.nobs;
-  F.products += 1;
-  if (!fwd_host_forced()) {
-    Buf Pd(be, (size_t)n * ncols), O(be, (size_t)nobs * ncols), part;
-    if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * ncols);
-    be->upload2d(Pd.p, n, P, ldp, n, ncols);
-    FwdProduct a;
-    fwd_fill(F, a);
-    a.Z = Pd.p; a.zbits = 64; a.ldz = n; a.K = ncols; a.plain = true;
-    a.out = O.p; a.ldo = nobs; a.partial = part.p;
-    const int form = be->fwd_products(a);
-    if (form != 0) {
-      be->download2d(out, ldo, O.p, nobs, nobs, ncols);
-      F.last_form = form;
-      return;
-    }
-  }
-  fwd_host_csr(F, P, ldp, ncols, out, ldo);
-  F.host_products += 1;
-  F.last_form = 3;
 }
 
 }  // namespace gsi

@@ -7,7 +7,6 @@
 #include <memory>
 #include <vector>
 #include "backend.hpp"
-#include "fwd_plan.hpp"
 
 namespace gsi {
 
@@ -134,63 +133,6 @@ struct LsqrOperator {
 int64_t lsqr(Context& c, const LsqrOperator& A, const double* b, double* x, int64_t maxiter);
 // x = A \ b for a LowRankCovMatrix: lsqr with maxiter = number of samples  (lowrank.jl:141-144); b, x replicated (n)
 int64_t lowrank_solve(const Operator& A, const double* b, double* x);
-// PCGALowRankMatrix(etas, HX, R)  (lowrank.jl:32-36, 83-97): [(HQH + R) HX; HX' 0], HQH = sum eta_i eta_i' kept implicit.
-struct PcgaLowRank {
-  Context* ctx = nullptr;
-  int64_t nobs = 0, K = 0;
-  Buf E, HX, R;        // E: nobs x K (eta_i as columns); R: nobs x nobs dense, or nobs values when r_diag
-  bool r_diag = false;
-  void mul(const double* x, double* y) const;   // x, y: nobs + 1
-  // x = A \ b (host vectors, nobs + 1) by Cholesky of HQH + R (direct.jl:56-58 for a positive definite HQH + R; DESIGN.md
-  // section 4.7c).  info2[0]: 0 or the 1-based column at which HQH + R stopped being positive definite; info2[1]: 1 the
-  // backend's kernels, 3 the host path (the backend declined, or GSI_SADDLE_HOST=1).  Throws GSI_ERR_NOT_POSDEF or
-  // GSI_ERR_SINGULAR (w'w == 0 or a non-finite beta) with info2 filled.
-  void solve(const double* b, double* x, int64_t* info2) const;
-};
-// cholesky(Symmetric(A, :L)).L of a host matrix (n x n, lda) into L (n x n, ld n, strictly upper triangle zero); info2 as above.
-// A failed factorization fills info2, leaves L unspecified and does not throw.
-void chol_lower_host_matrix(Context& c, const double* A, int64_t n, int64_t lda, double* L, int64_t* info2);
-// ---- the posterior variance from the resident basis.  info2[0]: 0 or the failing column of R;
-//      info2[1]: 1 the backend's kernels, 3 the host path (the backend declined, or GSI_POST_HOST=1, read at each call) ----
-// a[i] = |W' z_i|^2, q[i] = |z_i|^2 (q may be null), t[i] = u' z_i (u, t null together) over the rows of the basis Z
-// (backend memory, n x K, ld n, fp64 or fp32 by zbits).  W (K x ncols, ld ldw), u and the outputs are host arrays.
-void basis_quadform(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const double* W, int64_t ldw, int64_t ncols,
-                    bool upper, const double* u, double* a, double* q, double* t, int64_t* info2);
-// W (K x K upper triangular), u (K), gamma of the capacitance form, from the matrix's E, HX and R; host outputs (any may be
-// null).  Wdev / udev (may be null): on the backend's path W and u are also left there for the row pass (empty on the host
-// path).  Throws GSI_ERR_NOT_POSDEF (info2[0] = column) or GSI_ERR_SINGULAR.
-void posterior_factor(const PcgaLowRank& A, double* W, double* u, double* gamma, int64_t* info2, Buf* Wdev = nullptr,
-                      Buf* udev = nullptr);
-// var (n, host) by the two row formulas of section 4.7d; X (n) and prior (n, or null: the low-rank prior |z_i|^2) on the host
-void posterior_variance(Context& c, const void* Z, int zbits, int64_t n, int64_t K, const PcgaLowRank& A, const double* X,
-                        const double* prior, double* var, int64_t* info2);
-// A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
-// vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
-// double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.
-struct FwdModel {
-  Context* ctx = nullptr;
-  int64_t nobs = 0, n = 0, nnz = 0, seg_limit = 0;
-  int link = 0;
-  std::vector<int64_t> rowptr;
-  std::vector<int32_t> colidx;
-  std::vector<double> vals, w;     // w empty: ones
-  FwdPlan plan;
-  Buf d_segptr, d_rowseg, d_colidx, d_vals, d_w;
-  // what ran (gsi_fwd_info): form of the last product (0 none yet, 1 lane-per-output, 2 wave-per-segment, 3 host path),
-  // products that took the host path, products in total
-  mutable int64_t last_form = 0, host_products = 0, products = 0;
-};
-enum : int64_t { FWD_DEFAULT_SEG_LIMIT = 16384 };   // nonzeros per segment, from the sweep of DESIGN.md section 4.7b; GSI_FWD_SEG overrides
-// Validates (GSI_ERR_ARG naming the offending row or entry, before anything is allocated), plans and uploads.
-void fwd_create(Context& c, FwdModel& F, int64_t nobs, int64_t n, const int64_t* rowptr, const int64_t* colidx,
-                const double* vals, const double* weights, int link);
-// out (host, nobs x (K + 3), ld nobs): column c = h(column c of paramstorun) for the basis Z (backend memory, n x K, ld n,
-// fp64 or fp32 by zbits), s and X on the host.  The backend's kernels, or -- when it declines or GSI_FWD_HOST=1 --
-// pcga_params, a download and a host CSR loop.
-void fwd_forward_basis(Context& c, const FwdModel& F, const void* Z, int zbits, int64_t K, const double* s, const double* X,
-                       double delta, double* out);
-// out (host, nobs x ncols, ld ldo): column c = h(P[:, c]) for the host matrix P (n x ncols, ld ldp)
-void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo);
 // throws Error if a kernel raised an asynchronous flag
 void check_async_errors(Context& c);
 

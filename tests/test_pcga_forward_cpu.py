@@ -1,5 +1,5 @@
 """The sparse forward model (gsi_fwd, LinearForwardModel) without a GPU: argument checking, the
-host path of pipeline.cpp on the CPU reference backend against numpy, the counters, pcgadirect / pcgalsqr / rga end to end,
+host path of pcga.cpp on the CPU reference backend against numpy, the counters, pcgadirect / pcgalsqr / rga end to end,
 and the segment planner as a stand-alone program under the address and undefined-behaviour sanitizers."""
 import ctypes as C
 import os

@@ -1,6 +1,6 @@
 """The posterior variance (gsi_basis_quadform, gsi_pcgamat_posterior, gsi_pcga_posterior_variance, posterior_variance,
 posterior_realizations) without a GPU: on the CPU reference library the backend declines, so this is
-the host path of pipeline.cpp (posterior_host.hpp) and the whole API around it, with info[1] == 3 -- the row sums to the bounds
+the host path of pcga.cpp (posterior_host.hpp) and the whole API around it, with info[1] == 3 -- the row sums to the bounds
 of posterior_cases.py and exactly on integers, the variance against the dense saddle-point formula in extended precision, the
 factor, the observed-point property, the realisations, the errors, and the host path as a stand-alone program under the
 address and undefined-behaviour sanitizers."""

@@ -214,3 +214,42 @@ def test_errors(gsi, ctx):
     assert ctx.lib.gsi_basis_quadform(ctx.h, basis.h, dp(W), 3, 3, 0, dp(a), dp(a), None, None, None) == 1   # u without t_out
     assert ctx.lib.gsi_pcga_posterior_variance(ctx.h, basis.h, None, dp(a), None, dp(a), None) == 1
     pc.close_basis(basis)
+
+
+# ---- 11: the variance and the row sums are one row pass ----------------------------------------------------------------------
+@pytest.mark.parametrize("precision", [64, 32])
+def test_variance_and_quadform_share_the_row_pass(gsi, ctx, precision):
+    """gsi_pcga_posterior_variance and gsi_basis_quadform with the same triangular W and u (those of gsi_pcgamat_posterior)
+    run the same row pass: the a, q and t behind the variance are the bits gsi_basis_quadform returns.  The variance is
+    a + (t - X)^2 / gamma, plus prior - q with a prior; X = t makes the second term vanish and leaves a, prior = q makes the
+    prior term vanish (the difference of two nearby doubles is exact, so another q would show), and X = 0 is compared with
+    the same formula evaluated in the same order on the row sums."""
+    import scipy.sparse as sp
+    n, K, nobs = 257, 33, 40
+    Z, _ = pc.kernel_inputs(n, K, False)
+    rng = np.random.default_rng(33)
+    A = gsi.PCGALowRankMatrix([rng.standard_normal(nobs) for _ in range(K)], rng.standard_normal(nobs),
+                              sp.diags(rng.uniform(0.5, 1.5, nobs), format="csc"), ctx=ctx)
+    basis, _ = pc.make_basis(gsi, ctx, Z, precision)
+    dp = gsi._lib.dptr
+
+    def variance(X, prior):
+        v = np.empty(n)
+        info = (C.c_int64 * 2)()
+        st = ctx.lib.gsi_pcga_posterior_variance(ctx.h, basis.h, A.h, dp(X), dp(prior) if prior is not None else None, dp(v), info)
+        assert st == 0 and list(info) == [0, DEVICE], (st, list(info))
+        return v
+
+    try:
+        W, u, gamma, info = A.posterior_factor(return_info=True)
+        assert info == [0, DEVICE]
+        a, q, t, info = basis.quadform(W, u, upper=True, return_info=True)
+        assert info == [0, DEVICE]
+        assert np.array_equal(variance(t, None), a)
+        assert np.array_equal(variance(t, q), a)
+        assert np.array_equal(variance(np.zeros(n), None), a + t * t / gamma)
+        shifted = q + 1.0
+        assert np.array_equal(variance(np.zeros(n), shifted), (shifted - q) + (a + t * t / gamma))
+    finally:
+        A.close()
+        pc.close_basis(basis)

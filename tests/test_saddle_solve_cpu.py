@@ -1,5 +1,5 @@
 """The direct saddle-point solver (gsi_pcgamat_solve, gsi_chol_lower, pcgadirect(solver="cholesky"))
-without a GPU: on the CPU reference library the backend declines, so this is the host path of pipeline.cpp
+without a GPU: on the CPU reference library the backend declines, so this is the host path of pcga.cpp
 (saddle_host.hpp) and the whole API around it -- argument checks, exact factors and failure columns, the singular system,
 manufactured systems against the bar of saddle_cases.py, pcgadirect end to end and with a forced fallback, and the host path
 as a stand-alone program under the address and undefined-behaviour sanitizers."""
