@@ -357,8 +357,6 @@ class Backend {
   }
   // column norms of Y (m x c) -> host array
   virtual void colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) = 0;
-  // y <- y - Q (Q' y) for Q m x j (classical Gram-Schmidt step of Alg 4.2), y length m
-  // and out = y/||y|| if normalize_into != null
   virtual void axpy(int64_t n, double a, const double* x, double* y) = 0;
   virtual double dot(int64_t n, const double* x, const double* y) = 0;
   virtual double nrm2(int64_t n, const double* x) = 0;

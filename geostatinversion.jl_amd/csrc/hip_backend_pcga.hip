@@ -1,0 +1,174 @@
+// hip_backend_pcga.hip -- HipBackend's solver side: column norms, the BLAS-1/2 helpers, the LSQR steps, and what the PCGA
+// consumers (pcga.cpp) run on the device: the parameter products, the sparse forward model, the saddle-point solve, the
+// posterior variance's row pass.
+#include <cmath>
+#include <cstdlib>
+#include "hip_backend_impl.hpp"
+
+namespace gsi {
+
+void HipBackend::colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) {
+  bind();
+  if (c > 64) throw Error(GSI_ERR_ARG, "colnorms: at most 64 columns at a time");
+  hipk::colnorms_sq(st_, Y, m, c, ld, scal_);
+  HIP_CHECK(hipMemcpyAsync(host_out, scal_, sizeof(double) * c, hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  for (int64_t i = 0; i < c; ++i) host_out[i] = std::sqrt(host_out[i]);
+}
+void HipBackend::axpy(int64_t n, double a, const double* x, double* y) { bind(); hipk::axpy(st_, n, a, x, y); }
+double HipBackend::dot(int64_t n, const double* x, const double* y) {
+  bind();
+  hipk::dot_dev(st_, n, x, y, scal_);
+  double v = 0.0;
+  HIP_CHECK(hipMemcpyAsync(&v, scal_, sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  return v;
+}
+double HipBackend::nrm2(int64_t n, const double* x) { return std::sqrt(dot(n, x, x)); }
+void HipBackend::scal_copy(int64_t n, double a, const double* x, double* y) {
+  bind();
+  hipk::scal_copy(st_, n, a, x, y);
+}
+void HipBackend::pcga_params(const double* Z, int64_t n, int64_t K, const double* s, const double* X, double delta,
+                             double* out) {
+  bind();
+  hipk::pcga_params(st_, Z, n, K, s, X, delta, out);
+  check_launch("pcga_params");
+}
+void HipBackend::gemv_n(int64_t m, int64_t k, double alpha, const double* A, int64_t lda, const double* x, double beta,
+                        double* y) {
+  bind();
+  hipk::gemv_n(st_, m, k, alpha, A, lda, x, beta, y);
+  check_launch("gemv_n");
+}
+void HipBackend::gemv_t(int64_t m, int64_t k, double alpha, const double* A, int64_t lda, const double* x, double* y) {
+  bind();
+  grow(ws_blas2_, sizeof(double) * hipk::gemv_t_workspace_doubles(k));
+  hipk::gemv_t(st_, m, k, alpha, A, lda, x, y, (double*)ws_blas2_.p);
+  check_launch("gemv_t");
+}
+void HipBackend::project_out(int64_t m, int64_t ncols, const double* q, double* Y, int64_t ld) {
+  bind();
+  if (ncols > 64) throw Error(GSI_ERR_ARG, "project_out: at most 64 columns at a time");
+  grow(ws_blas2_, sizeof(double) * hipk::gemv_t_workspace_doubles(ncols));
+  hipk::project_out(st_, m, ncols, q, Y, ld, (double*)ws_blas2_.p);
+  check_launch("project_out");
+}
+void HipBackend::scal(int64_t n, double a, double* x) { bind(); hipk::scal(st_, n, a, x); }
+void HipBackend::diag_mul_add(int64_t n, const double* d, const double* x, double* y) {
+  bind();
+  hipk::diag_mul_add(st_, n, d, x, y);
+}
+void HipBackend::lsqr_begin(int64_t n, const double* w, double* work) {
+  bind();
+  hipk::lsqr_begin(st_, n, w, work);
+  check_launch("lsqr_begin");
+}
+void HipBackend::lsqr_step_u(int64_t m, const double* t, double* u, double* work) {
+  bind();
+  hipk::lsqr_step_u(st_, m, t, u, work);
+  check_launch("lsqr_step_u");
+}
+void HipBackend::lsqr_step_v(int64_t n, const double* t, double* v, double* w, double* x, double* work) {
+  bind();
+  hipk::lsqr_step_v(st_, n, t, v, w, x, work);
+  check_launch("lsqr_step_v");
+}
+void HipBackend::f64_to_f32(const double* src, void* dst32, size_t count) {
+  bind();
+  hipk::f64_to_f32(st_, src, (float*)dst32, count);
+  check_launch("f64_to_f32");
+}
+void HipBackend::pcga_params_f32(const void* Z32, int64_t n, int64_t K, const double* s, const double* X, double delta,
+                                 double* out) {
+  bind();
+  hipk::pcga_params_f32(st_, (const float*)Z32, n, K, s, X, delta, out);
+  check_launch("pcga_params_f32");
+}
+void HipBackend::basis_gemv_f32(const void* Z32, int64_t n, int64_t K, const double* w, double beta, const double* X,
+                                double* y) {
+  bind();
+  if (K > 8000) throw Error(GSI_ERR_ARG, "basis_gemv_f32: K too large for the LDS-resident weights");
+  hipk::basis_gemv_f32(st_, (const float*)Z32, n, K, w, beta, X, y);
+  check_launch("basis_gemv_f32");
+}
+// The sparse forward model (pcga_forward.hip).  The form follows the mean segment length: FWD_WAVE_MIN nonzeros and more
+// go one wave per segment, shorter ones one lane per output (the crossover of the sweep in profiles/pcga_forward.json:
+// 4096 rays of 16 cells run 0.65 ms in the wave form against 0.83 ms, rays of 4 cells 0.66 against 0.62;
+// DESIGN.md section 4.7b).  GSI_FWD_FORM=lane|wave, read at every call, overrides.
+static constexpr int64_t FWD_WAVE_MIN = 16;
+int HipBackend::fwd_products(const FwdProduct& a) {
+  bind();
+  int form = (a.nseg > 0 && a.nnz / a.nseg >= FWD_WAVE_MIN) ? 2 : 1;
+  if (const char* e = getenv("GSI_FWD_FORM")) {
+    const std::string f(e);
+    if (f == "lane") form = 1;
+    else if (f == "wave") form = 2;
+    else if (!f.empty()) throw Error(GSI_ERR_ARG, "GSI_FWD_FORM must be lane or wave, not '" + f + "'");
+  }
+  if (form == 1) hipk::fwd_lane(st_, a);
+  else hipk::fwd_wave(st_, a);
+  check_launch(form == 1 ? "fwd_lane" : "fwd_wave");
+  if (a.rowseg) {
+    hipk::fwd_reduce(st_, a);
+    check_launch("fwd_reduce");
+  }
+  return form;
+}
+
+// The blocked Cholesky and the saddle-point solve (chol_saddle.hip).  The pivot flag has a slot
+// of its own behind the error words: the caller gets the column as a return value, not through take_error.
+int64_t HipBackend::chol_lower(double* A, int64_t m, int64_t n, int64_t ld) {
+  bind();
+  if (n < 1 || m < n || ld < m || n >= ((int64_t)1 << 31)) throw Error(GSI_ERR_ARG, "chol_lower: need 1 <= n <= m <= ld, n < 2^31");
+  HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOL_LOWER, 0, sizeof(int32_t), st_));
+  hipk::cs_chol_lower(st_, A, m, n, ld, flags_ + FLAG_CHOL_LOWER);
+  check_launch("chol_lower");
+  return read_flag(FLAG_CHOL_LOWER);
+}
+int64_t HipBackend::saddle_solve(const double* E, int64_t nobs, int64_t K, const double* HX, const double* R, bool r_diag, const double* b,
+                                 double* x, bool* singular) {
+  bind();
+  const int64_t ld = nobs + 2;
+  Scratch W(this, (size_t)ld * nobs);
+  HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOL_LOWER, 0, sizeof(int32_t), st_));
+  phase_begin(PH_SMALL_GEMM);                              // (profiling: the formation counts as a small product ...
+  hipk::cs_syrk_lower(st_, W.p, ld, nobs, nobs, E, nobs, K, 1.0, 0.0, R, nobs, r_diag ? 2 : 1, flags_ + FLAG_CHOL_LOWER);
+  hipk::cs_set_rows(st_, W.p, ld, nobs, HX, b);
+  phase_end(PH_SMALL_GEMM);
+  phase_begin(PH_OTHER);                                   // ... the factorization as "other": tools/pcga_direct_bench.py)
+  hipk::cs_chol_lower(st_, W.p, nobs + 2, nobs, ld, flags_ + FLAG_CHOL_LOWER);
+  phase_end(PH_OTHER);
+  check_launch("saddle_solve: factorization");
+  const int64_t col = read_flag(FLAG_CHOL_LOWER);
+  *singular = false;
+  if (col != 0) return col;
+  hipk::cs_schur(st_, W.p, ld, nobs, b, x, scal_);
+  grow(ws_blas2_, sizeof(double) * hipk::cs_backsolve_workspace_doubles());
+  hipk::cs_backsolve(st_, W.p, nobs, ld, x, (double*)ws_blas2_.p);
+  check_launch("saddle_solve: substitution");
+  double out3[3] = {0.0, 0.0, 0.0};
+  HIP_CHECK(hipMemcpyAsync(out3, scal_, sizeof(out3), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  *singular = (out3[2] == 0.0);
+  return 0;
+}
+
+// The row pass of the posterior variance (posterior_var.hip).
+int HipBackend::basis_quadform(const void* Z, int zbits, int64_t n, int64_t ldz, int64_t K, const double* W, int64_t ldw, int64_t ncols,
+                               bool upper, const double* u, double* a, double* q, double* t) {
+  bind();
+  if (n < 1 || K < 1 || ncols < 1 || ldz < n || ldw < K || (zbits != 64 && zbits != 32) || (u == nullptr) != (t == nullptr))
+    throw Error(GSI_ERR_ARG, "basis_quadform: need n, K, ncols >= 1, ldz >= n, ldw >= K, 32 or 64 bits, u and t together");
+  hipk::pv_quadform(st_, Z, zbits, n, ldz, K, W, ldw, ncols, upper, u, a, q, t);
+  check_launch("basis_quadform");
+  return 1;
+}
+int HipBackend::scale_rows(int64_t m, int64_t c, const double* d, const double* src, int64_t lds, double* dst, int64_t ldd) {
+  bind();
+  hipk::pv_scale_rows(st_, m, c, d, src, lds, dst, ldd);
+  check_launch("scale_rows");
+  return 1;
+}
+
+}  // namespace gsi

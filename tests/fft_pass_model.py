@@ -4,8 +4,8 @@ test_fft_pass_kernels_gpu.py, and the exact integer reference of those cases.  N
 passes(Ns, l) mirrors, with every GSI_FFT_* knob at its default (GSI_FFT_TB=16, GSI_FFT_B0=64, GSI_FFT_B1=140,
 GSI_FFT_MIN_T=4, GSI_FFT_LINE_SYNC=1, GSI_FFT_W_MB unset):
 
-  csrc/hip_backend.hip  fftcov_new_plan     :415-423  singleton axes squeezed, M_a = next power of two >= 2 N_a
-                                            :433-436  nb_max: pairs per batch, (256 MB | 2 GB) / (16 Mtot), at most 64
+  csrc/hip_backend_products.hip  fftcov_new_plan  :132-140  singleton axes squeezed, M_a = next power of two >= 2 N_a
+                                            :150-153  nb_max: pairs per batch, (256 MB | 2 GB) / (16 Mtot), at most 64
   csrc/fft_cov.hip      fft_cov_apply       :723-732  batches of nb_max pairs; d - 1 forward passes, the fused one, d - 1 back
                         fft_pass            :618-629  Ma, nin / nout, estride, R1 / R2 (the later axes, restricted)
                                             :631-652  the layout: lb, kind, OS

@@ -1,6 +1,6 @@
 """Every CholeskyQR kernel instantiation at its dispatch edges, with the tier that ran checked (RandMatFact.jl:57-58, :86).
 
-The thin QR tries three tiers (hip_backend.hip, qr_thinQ): CholeskyQR2, shifted CholeskyQR3, Householder.  A wrong Gram or
+The thin QR tries three tiers (hip_backend_panels.hip, qr_thinQ): CholeskyQR2, shifted CholeskyQR3, Householder.  A wrong Gram or
 triangular-product kernel usually just fails the round-two orthogonality check (cq_orth_check_kernel, 0.1) and the library
 moves on to a slower tier that returns a correct Q -- so a test that checks only Q and R does not see it.  Every case here
 asserts the counter deltas of a FRESH context (no fall-back hint left by an earlier panel of the same height) as well as
@@ -198,7 +198,7 @@ def test_scholqr3_second_tier(gsi, m, l):
     assert np.abs(s - sref).max() < 1e-13 * sref[0]
 
 
-# ---- svd(B) without the thin Q (hip_backend.hip, svd_tall_fused): the same first-tier shapes ---------------------------
+# ---- svd(B) without the thin Q (hip_backend_panels.hip, svd_tall_fused): the same first-tier shapes ---------------------------
 @pytest.mark.parametrize("m,l", FIRST_TIER)
 def test_svd_tall_fused_first_tier(gsi, m, l):
     W = int_panel(m, l)
@@ -216,7 +216,7 @@ def test_svd_tall_fused_first_tier(gsi, m, l):
     assert np.abs(V.T @ V - np.eye(l)).max() < 1e-12
 
 
-# ---- the hint the three first-tier callers share (hip_backend.hip, cholqr2_try / skip_tier1_by_height_) -----------------
+# ---- the hint the three first-tier callers share (hip_backend_panels.hip, cholqr2_try / skip_tier1_by_height_) -----------------
 def test_first_tier_hint_shared_by_callers(gsi):
     """A failed first tier in svd_tall_fused leaves the hint qr_thinQ reads: eight factorizations of that height start at
     the second tier (the svd_tall's own generic QR is the first of them), the ninth probes from the top again; a panel of

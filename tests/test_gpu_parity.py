@@ -554,7 +554,7 @@ def test_randsvd_wide_sketch(gsi, ctx, n, K, p, q):
     A = B @ np.diag(np.logspace(0, -3, n)) @ B.T          # SPD, slowly decaying spectrum
     Omega = rng.standard_normal((n, K + p))
     # Own context: in the shared one, an earlier panel of the same height (1500 rows) that needed the shifted tier
-    # makes the next eight factorizations of that height start at the second tier (hip_backend.hip, skip_tier1_);
+    # makes the next eight factorizations of that height start at the second tier (hip_backend_panels.hip, skip_tier1_);
     # in the whole -m gpu run this call then ran shifted CholeskyQR3 twice and CholeskyQR2 never.
     c = gsi.Context(0)
     try:

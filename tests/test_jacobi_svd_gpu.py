@@ -31,7 +31,7 @@ used here:
                                                                     (200, 160)    18.61          0.040           2e-06
   forced widths 8 / 4 / 2, l in {1, 2, 15, 16, 17, 40, 41, 96} at n = 2 l + 4: model / bound between 0.01 and 0.25.
 
-Which tier hands R to the Jacobi kernel is the QR gate's decision (hip_backend.hip, qr_thinQ), not the test's: n >= 2 l only
+Which tier hands R to the Jacobi kernel is the QR gate's decision (hip_backend_panels.hip, qr_thinQ), not the test's: n >= 2 l only
 ADMITS a panel to the Cholesky tiers.  Their guards look at the UNSCALED panel, so a column grading of 2^40 fails
 CholeskyQR2's although CholeskyQR2 on such a panel would be accurate (Cholesky is invariant under column scaling; the
 float64 model above is exactly that chain).  Every case asserts the relative bound on whichever tier ran, except the shifted
