@@ -48,6 +48,15 @@ struct gsi_fwd {
   FwdModel m;
 };
 
+struct gsi_sampler {
+  gsi_ctx* ctx;
+  void* plan = nullptr;       // the backend's (Backend::gridcov_sampler_create)
+  int ndims;
+  int64_t N[3], M[3], n, Mtot;
+  double info[4];
+  ~gsi_sampler() { if (plan) ctx->c.be->gridcov_sampler_destroy(plan); }
+};
+
 namespace {
 thread_local std::string g_last_error;
 
@@ -615,6 +624,112 @@ int gsi_op_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, i
 int gsi_op_fft_gridcov_table(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, const double* table,
                              const double* table_mirror, double nugget) {
   return guarded([&] { make_fft_gridcov(ctx, op, ndims, N, 0, nullptr, 0.0, 1.0, nugget, table, table_mirror, true); });
+}
+
+// ---- Gaussian fields with a grid covariance function (circulant embedding; Backend::gridcov_sampler_*) ----
+int gsi_gridcov_sampler_create(gsi_ctx* ctx, gsi_sampler** sampler, int ndims, const int64_t* N, const int64_t* embed, int kind,
+                               const double* ell, double theta, double sigma2, double nugget, double neg_tol, double* info) {
+  double inf4[4] = {NAN, NAN, NAN, NAN};
+  const int st = guarded([&] {
+    REQUIRE(ctx && sampler, "gridcov sampler: ctx or sampler is NULL");
+    *sampler = nullptr;
+    REQUIRE(ndims == 2 || ndims == 3, "gridcov sampler: ndims must be 2 or 3");
+    REQUIRE(N != nullptr, "gridcov sampler: N is NULL");
+    std::unique_ptr<gsi_sampler> s(new gsi_sampler());
+    s->ctx = ctx; s->ndims = ndims; s->n = 1; s->Mtot = 1;
+    for (int a = 0; a < 3; ++a) { s->N[a] = 1; s->M[a] = 1; }
+    for (int a = 0; a < ndims; ++a) {
+      REQUIRE(N[a] >= 1, "gridcov sampler: every N[a] must be >= 1");
+      // (before the default embedding is formed: 2 N[a] must not overflow, and no torus holds more than 4096 box points)
+      REQUIRE(N[a] <= 4096, "gridcov sampler: N[a] must be <= 4096 (the torus needs embed[a] >= 2 N[a], and embed[a] <= 8192)");
+      s->N[a] = N[a];
+      s->n *= N[a];
+    }
+    REQUIRE(s->n >= 2, "gridcov sampler: a field needs n = prod(N) >= 2 points");
+    for (int a = 0; a < ndims; ++a) {
+      int64_t M = 2;
+      while (M < 2 * N[a]) M <<= 1;                    // the operator's embedding (fft_embed_size)
+      if (embed) M = embed[a];
+      REQUIRE(M >= 1 && (M & (M - 1)) == 0, "gridcov sampler: every embed[a] must be a power of two");
+      REQUIRE(M >= 2 * N[a], "gridcov sampler: every embed[a] must be >= 2 N[a]");
+      REQUIRE(M <= 8192, "gridcov sampler: every embed[a] must be <= 8192 (a line must fit LDS)");
+      s->M[a] = M;
+      s->Mtot *= M;
+      REQUIRE(s->Mtot < ((int64_t)1 << 31), "gridcov sampler: Mtot = prod(embed) must be < 2^31");
+    }
+    REQUIRE(kind >= 0 && kind < pointcov::NUM_KINDS, "gridcov sampler: kind 0 Gaussian, 1 exponential, 2 Matern 3/2, 3 Matern 5/2");
+    REQUIRE(ell, "gridcov sampler: ell is NULL");
+    double ell3[3] = {1.0, 1.0, 1.0};
+    for (int a = 0; a < ndims; ++a) {
+      REQUIRE(std::isfinite(ell[a]) && ell[a] > 0.0, "gridcov sampler: every ell[a] must be finite and > 0");
+      ell3[a] = ell[a];
+    }
+    REQUIRE(std::isfinite(sigma2) && sigma2 > 0.0, "gridcov sampler: sigma2 must be finite and > 0");
+    REQUIRE(std::isfinite(nugget) && nugget >= 0.0, "gridcov sampler: nugget must be finite and >= 0");
+    REQUIRE(std::isfinite(theta), "gridcov sampler: theta must be finite");
+    REQUIRE(theta == 0.0 || ndims == 2, "gridcov sampler: theta (a rotation) is for 2-D grids only");
+    REQUIRE(neg_tol >= 0.0 && neg_tol <= 1.0, "gridcov sampler: neg_tol must be in [0, 1]");      // (NaN fails both)
+    // with a communicator every rank builds the plan: fields are generated whole and each rank keeps its rows
+    s->plan = ctx->c.be->gridcov_sampler_create(ndims, s->N, s->M, kind, ell3, theta, sigma2, nugget, neg_tol, inf4);
+    for (int i = 0; i < 4; ++i) s->info[i] = inf4[i];
+    *sampler = s.release();
+  });
+  if (info) for (int i = 0; i < 4; ++i) info[i] = inf4[i];           // also when the plan was refused (GSI_ERR_NOT_POSDEF)
+  return st;
+}
+
+int gsi_gridcov_sampler_info(const gsi_sampler* sampler, int64_t* M, double* info) {
+  return guarded([&] {
+    REQUIRE(sampler, "gridcov sampler: sampler is NULL");
+    if (M) for (int a = 0; a < 3; ++a) M[a] = sampler->M[a];
+    if (info) for (int i = 0; i < 4; ++i) info[i] = sampler->info[i];
+  });
+}
+
+int gsi_gridcov_sampler_spectrum(gsi_ctx* ctx, const gsi_sampler* sampler, double* lam_out) {
+  return guarded([&] {
+    REQUIRE(ctx && sampler && sampler->ctx == ctx, "gridcov sampler: ctx or sampler is NULL, or the sampler belongs to another context");
+    REQUIRE(lam_out, "gridcov sampler: lam_out is NULL");
+    ctx->c.be->gridcov_sampler_spectrum(sampler->plan, lam_out);
+  });
+}
+
+int gsi_gridcov_sampler_destroy(gsi_sampler* sampler) {
+  return guarded([&] { delete sampler; });
+}
+
+int gsi_gridcov_fields(gsi_ctx* ctx, const gsi_sampler* sampler, gsi_mat* fields, const double* eps, int64_t ldeps, uint64_t seed,
+                       int64_t field0) {
+  return guarded([&] {
+    REQUIRE(ctx && sampler && sampler->ctx == ctx, "gridcov fields: ctx or sampler is NULL, or the sampler belongs to another context");
+    REQUIRE(fields && fields->ctx == ctx, "gridcov fields: fields is NULL or belongs to another context");
+    REQUIRE(fields->rows == sampler->n, "gridcov fields: fields must have n = prod(N) rows");
+    REQUIRE(eps == nullptr || ldeps >= sampler->Mtot, "gridcov fields: ldeps must be at least Mtot = prod(embed)");
+    REQUIRE(eps != nullptr || (field0 >= 0 && field0 % 2 == 0), "gridcov fields: field0 must be even and >= 0 (a pair is one transform)");
+    ctx->c.be->gridcov_sampler_fields(sampler->plan, fields->buf.p, fields->rows, 0, sampler->n, fields->cols, eps, ldeps, seed,
+                                      field0);
+  });
+}
+
+int gsi_op_lowrank_gridcov(gsi_ctx* ctx, gsi_op** op, const gsi_sampler* sampler, int64_t numfields, uint64_t seed, int64_t row0,
+                           int64_t n_local) {
+  return guarded([&] {
+    REQUIRE(ctx && op, "NULL argument");
+    *op = nullptr;
+    REQUIRE(sampler && sampler->ctx == ctx, "gridcov fields: sampler is NULL or belongs to another context");
+    REQUIRE(numfields >= 2, "LowRankCovMatrix needs numfields >= 2 sample fields");
+    const int64_t n = sampler->n;
+    check_shard(ctx->c, n, row0, n_local);
+    std::unique_ptr<gsi_op> o(new gsi_op());
+    Operator& A = o->op;
+    A.ctx = &ctx->c; A.kind = OP_LOWRANK; A.m = n; A.n = n; A.row0 = row0; A.mloc = n_local; A.N = numfields;
+    A.ld = n_local > 0 ? ((n_local + 15) / 16) * 16 : 16;
+    A.data = Buf(ctx->c.be.get(), (size_t)A.ld * numfields);
+    // the sampler's last pass writes straight into the operator's padded buffer
+    ctx->c.be->gridcov_sampler_fields(sampler->plan, A.data.p, A.ld, row0, n_local, numfields, nullptr, 0, seed, 0);
+    ctx->c.be->center_rows(A.data.p, n_local, numfields, A.ld);   // lowrank.jl:17-27
+    *op = o.release();
+  });
 }
 
 int gsi_op_destroy(gsi_op* op) {

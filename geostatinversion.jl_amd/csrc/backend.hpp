@@ -355,6 +355,31 @@ class Backend {
     (void)field0; (void)plan;
     throw Error(1 /* GSI_ERR_ARG */, "FFTRF fields at scattered points on the device: not available on this backend");
   }
+  // Gaussian fields with a grid covariance FUNCTION by circulant embedding (gsi_gridcov_sampler_* in include/gsi_hip.h,
+  // gridcov_sample.hip): the plan of the grid N (ndims axes, the others 1) on the torus M -- the spectrum lambda of the torus
+  // covariance sigma2 k(r) (+ nugget) and its clamped square root.  info[4] = neg_mass, lambda_min, lambda_max, clamped
+  // count, filled whenever the spectrum was computed; neg_mass > neg_tol throws GSI_ERR_NOT_POSDEF and leaves nothing
+  // allocated.  Arguments are validated by the caller.  Opaque plan.
+  virtual void* gridcov_sampler_create(int ndims, const int64_t N[3], const int64_t M[3], int kind, const double ell[3],
+                                       double theta, double sigma2, double nugget, double neg_tol, double info[4]) {
+    (void)ndims; (void)N; (void)M; (void)kind; (void)ell; (void)theta; (void)sigma2; (void)nugget; (void)neg_tol; (void)info;
+    throw Error(1 /* GSI_ERR_ARG */, "grid covariance fields sampled on the device: not supported by this backend");
+  }
+  virtual void gridcov_sampler_destroy(void* plan) { (void)plan; }
+  // lambda (Mtot values, torus order, unclamped, nugget included) -> HOST array
+  virtual void gridcov_sampler_spectrum(void* plan, double* lam_host) {
+    (void)plan; (void)lam_host;
+    throw Error(1 /* GSI_ERR_ARG */, "grid covariance fields sampled on the device: not supported by this backend");
+  }
+  // Fields field0 .. field0 + nf - 1 of the plan (field0 even; fields 2 j and 2 j + 1 are Re and Im of one transform): rows
+  // [row0, row0 + nloc) of field c go to dst[(r - row0) + c ldd].  eps (HOST, or null): column c = the noise array of role
+  // c (Mtot values, even c: real part, odd c: imaginary part), 2 ceil(nf / 2) columns, leading dimension ldeps; null: role
+  // f draws randn(..., seed + f).
+  virtual void gridcov_sampler_fields(void* plan, double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf,
+                                      const double* eps, int64_t ldeps, uint64_t seed, int64_t field0) {
+    (void)plan; (void)dst; (void)ldd; (void)row0; (void)nloc; (void)nf; (void)eps; (void)ldeps; (void)seed; (void)field0;
+    throw Error(1 /* GSI_ERR_ARG */, "grid covariance fields sampled on the device: not supported by this backend");
+  }
   // column norms of Y (m x c) -> host array
   virtual void colnorms(const double* Y, int64_t m, int64_t c, int64_t ld, double* host_out) = 0;
   virtual void axpy(int64_t n, double a, const double* x, double* y) = 0;

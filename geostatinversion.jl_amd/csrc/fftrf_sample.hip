@@ -287,9 +287,12 @@ static void frf_chirp_k(hipStream_t st, int threads, size_t shmem, int P, int L,
   hipLaunchKernelGGL((fftrf_chirp_kernel<LR, SHORT>), dim3(1), dim3(threads), shmem, st, P, frf_ilog2(P), L, A, twg, chirp, bspec);
 }
 
+void fftrf_twiddles(hipStream_t st, double* twg) {
+  hipLaunchKernelGGL(fftrf_twiddle_kernel, dim3(FFT_TW_LEN / 2 / 256), dim3(256), 0, st, reinterpret_cast<double2*>(twg));
+}
 void fftrf_plan(hipStream_t st, const FftrfGeom& g, double* plan) {
   double2* twg = reinterpret_cast<double2*>(plan);
-  hipLaunchKernelGGL(fftrf_twiddle_kernel, dim3(FFT_TW_LEN / 2 / 256), dim3(256), 0, st, twg);
+  fftrf_twiddles(st, plan);
   for (int a = 0; a < g.d; ++a) {
     if (!g.blue[a]) continue;
     const int P = (int)g.P[a], L = (int)g.L[a], A = (int)g.A[a];
@@ -349,7 +352,7 @@ static void frf_launch_kb(const FrfLaunch& q, const FrfPass& ps) {
 
 // lines per tile.  Contiguous lines need no neighbours: up to 32 within 64 KB of LDS.  Strided lines want long segments: up
 // to 16 neighbours (256 bytes).  Both within 8192 points = 16 per thread x 512 threads (short lines: one thread per line).
-static int fftrf_tile_lines(int Ma, bool contiguous, int64_t nl0) {
+int fftrf_tile_lines(int Ma, bool contiguous, int64_t nl0) {
   const int tpl = Ma >= 16 ? Ma / 16 : 1;
   int T = 512 / tpl;
   if (contiguous) {

@@ -3,6 +3,7 @@
 // bodies are split by subsystem:
 //   hip_backend.hip           construction, the block cache and the workspaces, the host boundary, streams, errors, profiling
 //   hip_backend_products.hip  contractions, generated operators, the FFT covariance plans, FFTRF fields
+//   hip_backend_sampler.hip   fields with a grid covariance function by circulant embedding: plan and batches
 //   hip_backend_panels.hip    panel LU (one rank and row-sharded), the QR tiers, the fused tall SVD, the small factorizations
 //   hip_backend_lowrank.hip   the LowRankCovMatrix chains in sample space
 //   hip_backend_pcga.hip      BLAS-1/2, LSQR and the PCGA consumers
@@ -88,6 +89,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   struct GemmWs { double* p; size_t doubles; };      // the contractions' split-K workspace and how many doubles it holds
   struct Rec { Phase phase; hipEvent_t a, b; bool counted; };
   struct FftCov;                 // hip_backend_products.hip
+  struct GridCovSampler;         // hip_backend_sampler.hip
   struct LusWs;                  // hip_backend_panels.hip
   struct SplitWs;                // hip_backend_lowrank.hip
   enum FftFactor { FFT_F_COS = 0, FFT_F_COS_WEIGHTED = 1, FFT_F_SIN_WEIGHTED = 2 };
@@ -160,6 +162,14 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
                        const double* phi, int64_t ldphi, uint64_t seed, int64_t field0, const FftrfPointsPlan& plan) override;
   void fftrf_interpolate(double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg,
                          const FftrfPointsPlan& plan) override;
+
+  // ---- hip_backend_sampler.hip ----
+  void* gridcov_sampler_create(int ndims, const int64_t N[3], const int64_t M[3], int kind, const double ell[3], double theta,
+                               double sigma2, double nugget, double neg_tol, double info[4]) override;
+  void gridcov_sampler_destroy(void* plan) override;
+  void gridcov_sampler_spectrum(void* plan, double* lam_host) override;
+  void gridcov_sampler_fields(void* plan, double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf, const double* eps,
+                              int64_t ldeps, uint64_t seed, int64_t field0) override;
 
   // ---- hip_backend_panels.hip ----
   void lu_L(double* Y, int64_t m, int64_t l, int64_t ld, int32_t* ipiv_host) override;

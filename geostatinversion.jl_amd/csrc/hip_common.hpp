@@ -106,6 +106,25 @@ void fftrf_plan(hipStream_t st, const FftrfGeom& g, double* plan);
 // nb fields whose phi sits at ws + b fs (fs even, >= fftrf_field_doubles): dst[(r - row0) + b ldd] for r in [row0, row0 + nloc)
 void fftrf_sample(hipStream_t st, const FftrfGeom& g, const double* plan, double* ws, int64_t fs, int nb, double k0, double dk,
                   double beta, double* dst, int64_t ldd, int64_t row0, int64_t nloc);
+int fftrf_tile_lines(int Ma, bool contiguous, int64_t nl0);   // lines per tile of a pass (gridcov_sample.hip takes the same)
+void fftrf_twiddles(hipStream_t st, double* twg);             // exp(-2 pi i k / FFT_TW_LEN), k < FFT_TW_LEN / 2
+// ---- gridcov_sample.hip: Gaussian fields with a grid covariance function by circulant embedding ----
+// N (box) and M (torus, powers of two) squeezed to 3 axes (1 beyond d); torus order t0 + M0 (t1 + M1 t2)
+struct GcsGeom { int d; int64_t N[3], M[3]; int64_t Mtot, n; };
+constexpr int GCS_PARTS = 64;                       // partial results per reduction: fixed, so the plan's numbers are too
+size_t gcs_pair_doubles(const GcsGeom& g);          // workspace of one pair of fields: eps1 | eps2 | W (N0 x M1 x M2 complex)
+// amp <- the torus covariance sigma2 k(r), the even part taken where a lag is M_a / 2 (nugget not included)
+void gcs_lag_table(hipStream_t st, const GcsGeom& g, int kind, const double inv_ell[3], double cs, double sn, double sigma2,
+                   double* amp);
+// lam <- Re of the transform of the table in amp, by the sampler's own passes (W: Mtot complex)
+void gcs_plan_transform(hipStream_t st, const GcsGeom& g, const double* twg, const double* amp, double* W, double* lam);
+// lam += nugget; amp <- sqrt(max(lam, 0) / Mtot); part (4 GCS_PARTS) <- partial sums of |lam| over lam < 0, minima, maxima
+// and counts of lam < 0, each over a fixed chunk in a fixed order
+void gcs_plan_finish(hipStream_t st, const GcsGeom& g, double nugget, double* lam, double* amp, double* part);
+// nb pairs whose noise sits at ws + b fs (eps1 | eps2, Mtot each; fs even, >= gcs_pair_doubles): fields 2 b and 2 b + 1 (the
+// latter only if 2 b + 1 < ncols) into dst[(r - row0) + c ldd] for r in [row0, row0 + nloc)
+void gcs_sample(hipStream_t st, const GcsGeom& g, const double* twg, const double* amp, double* ws, int64_t fs, int nb,
+                double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t ncols);
 // ---- fftrf_interp.hip: FFTRF.interpolate (FFTRF.jl:107-129), nb structured fields at m scattered points ----
 // base (m), frac (d x m, axis-major): the plan of fftrf_points.hpp on the device; field b at V + b v_fs, vec() order, strides
 // 1, s1, s2 along its axes; dst[p + b ldd] = the nested two-term sums, each product and sum rounded on its own

@@ -240,6 +240,84 @@ function lowrank_fftrf_operator(points::Matrix{Float64}, Ns::Vector{Int}, k0::Fl
 	return op
 end
 
+# ---- Gaussian fields with a grid covariance function (circulant embedding, gsi_gridcov_sampler_*) --
+const GRIDCOV_KINDS = Dict("gaussian" => 0, "exponential" => 1, "matern32" => 2, "matern52" => 3)
+
+"The plan of one grid and covariance function (`gsi_sampler`): `M` the torus, `info` = (neg_mass, lambda_min, lambda_max,
+clamped count) as creation found them."
+mutable struct GridCovSampler
+	h::Ptr{Cvoid}
+	c::Context
+	Ns::Vector{Int}
+	M::Vector{Int}
+	info::Vector{Float64}
+end
+function finalize_sampler!(s::GridCovSampler)
+	s.h != C_NULL && ccall((:gsi_gridcov_sampler_destroy, libgsi), Cint, (Ptr{Cvoid},), s.h)
+	s.h = C_NULL
+end
+
+"The sampler of the covariance of `gsi_op_fft_gridcov(Ns, kind, ell, theta, sigma2, nugget)` on a 2-D or 3-D grid
+(`gsi_gridcov_sampler_create`).  `embed`: the torus per axis (powers of two, 2 N <= M <= 8192; `nothing`: the next power of
+two >= 2 N).  Refused (GSI_ERR_NOT_POSDEF) when the clamped negative part of the spectrum exceeds `neg_tol`."
+function gridcov_sampler(Ns::Vector{Int}; kind::String="exponential", ell::Vector{Float64}=ones(length(Ns)), theta::Float64=0.0,
+		sigma2::Float64=1.0, nugget::Float64=0.0, embed::Union{Nothing,Vector{Int}}=nothing, neg_tol::Float64=1e-12,
+		c::Context=ctx())
+	length(ell) == length(Ns) || error("ell must hold one length per axis")
+	embed === nothing || length(embed) == length(Ns) || error("embed must hold one torus length per axis")
+	N64 = Int64.(Ns)
+	M64 = embed === nothing ? Int64[] : Int64.(embed)
+	mp = embed === nothing ? Ptr{Int64}(C_NULL) : pointer(M64)
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	info = zeros(Float64, 4)
+	GC.@preserve M64 check(ccall((:gsi_gridcov_sampler_create, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Cint, Ptr{Int64}, Ptr{Int64}, Cint, Ptr{Float64}, Cdouble, Cdouble, Cdouble, Cdouble,
+		 Ptr{Float64}),
+		c.h, r, length(N64), N64, mp, GRIDCOV_KINDS[kind], ell, theta, sigma2, nugget, neg_tol, info))
+	M = zeros(Int64, 3)
+	check(ccall((:gsi_gridcov_sampler_info, libgsi), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}), r[], M, info))
+	s = GridCovSampler(r[], c, copy(Ns), Int.(M[1:length(Ns)]), info)
+	finalizer(finalize_sampler!, s)
+	return s
+end
+
+"lambda on the torus (size `M`, unclamped, nugget included): `gsi_gridcov_sampler_spectrum`."
+function spectrum(s::GridCovSampler)
+	lam = Vector{Float64}(undef, prod(s.M))
+	check(ccall((:gsi_gridcov_sampler_spectrum, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), s.c.h, s.h, lam))
+	return reshape(lam, s.M...)
+end
+
+"`numfields` fields of the sampler (`gsi_gridcov_fields`): an n x numfields `DeviceMatrix`, column c = `vec` of field
+`field0 + c` (`field0` even).  `eps` (Mtot x 2 ceil(numfields / 2), column c the noise of role c in torus order) fixes the
+random numbers; without it role f draws the device stream `seed + f`."
+function fields(s::GridCovSampler, numfields::Int; eps::Union{Nothing,Matrix{Float64}}=nothing, seed::Integer=0, field0::Int=0)
+	F = DeviceMatrix(prod(s.Ns), numfields; c=s.c)
+	if eps === nothing
+		check(ccall((:gsi_gridcov_fields, libgsi), Cint,
+			(Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, UInt64, Int64),
+			s.c.h, s.h, F.h, C_NULL, 0, UInt64(seed), field0))
+	else
+		size(eps) == (prod(s.M), 2 * cld(numfields, 2)) || error("eps must be Mtot x 2 ceil(numfields / 2)")
+		GC.@preserve eps check(ccall((:gsi_gridcov_fields, libgsi), Cint,
+			(Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, UInt64, Int64),
+			s.c.h, s.h, F.h, eps, stride(eps, 2), UInt64(0), 0))
+	end
+	return F
+end
+
+"`LowRankCovMatrix` over `numfields` device-sampled fields of the sampler (`gsi_op_lowrank_gridcov`), centred and kept in HBM."
+function lowrank_gridcov_operator(s::GridCovSampler, numfields::Int; seed::Integer=0)
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	n = prod(s.Ns)
+	check(ccall((:gsi_op_lowrank_gridcov, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Int64, UInt64, Int64, Int64),
+		s.c.h, r, s.h, numfields, UInt64(seed), 0, n))
+	op = DeviceOperator(r[], s.c, n, n)
+	finalizer(finalize_op!, op)
+	return op
+end
+
 "Gaussian covariance exp(-d^2/(2 ell^2)) of an nx x ny unit grid as a matrix-free operator: entries are regenerated
 inside the product kernel, nothing of size n^2 is stored (`gsi_op_gridcov_implicit`).  Usable wherever a Matrix is."
 function GridCovImplicit(nx::Int, ny::Int, ell::Float64; c::Context=ctx())
