@@ -19,7 +19,7 @@ from .randmatfact import rangefinder, randsvd, randsvd_rows, eig_nystrom, colnor
 from .lowrank import LowRankCovMatrix, PCGALowRankMatrix, device_samples
 from .getxis import getxis, getxis_iwantfields, getxis_device, getxis_fftrf, randsvdwithseed
 from . import fftrf as FFTRF
-from .fftrf import lowrank_fftrf_operator
+from .fftrf import lowrank_fftrf_operator, fft_operator_at, FFTOperatorAt
 from . import gridcov as GridCov
 from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, gridcov_structuredgrid
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
@@ -29,7 +29,7 @@ __all__ = [
     "GsiError", "load", "LIB_PATH", "Context", "Operator", "DeviceMatrix", "dense_operator",
     "gridcov_operator", "gridcov_implicit_operator", "pointcov_implicit_operator", "fft_powerlaw_operator", "fft_gridcov_operator", "lowrank_synthetic_operator", "default_context", "RandMatFact", "rangefinder", "randsvd", "randsvd_rows", "eig_nystrom",
     "colnorms", "lu_L", "lu_L_dev", "lu_L_sharded", "lu_L_sharded_virtual", "qr_thinQ", "svd_tall", "gemm", "gemm_view", "LowRankCovMatrix", "PCGALowRankMatrix", "device_samples",
-    "getxis", "getxis_iwantfields", "getxis_device", "getxis_fftrf", "randsvdwithseed", "FFTRF", "lowrank_fftrf_operator", "GridCov", "GridCovSampler",
+    "getxis", "getxis_iwantfields", "getxis_device", "getxis_fftrf", "randsvdwithseed", "FFTRF", "lowrank_fftrf_operator", "fft_operator_at", "FFTOperatorAt", "GridCov", "GridCovSampler",
     "gridcov_sampler", "lowrank_gridcov_operator", "gridcov_structuredgrid", "pcgadirect", "pcgalsqr", "rga", "pcga",
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",
 ]

@@ -44,6 +44,7 @@ SIGNATURES = {
     "gsi_op_lowrank_fftrf": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_double,
                                        c_i64, C.c_uint64, c_i64, c_i64]),
     "gsi_fftrf_interpolate": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.POINTER(c_i64), c_dp, c_i64, c_dp, c_i64]),
+    "gsi_fftrf_spread": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, C.POINTER(c_i64), c_dp, c_i64, c_dp, c_i64]),
     "gsi_fftrf_fields_at": (C.c_int, [c_vp, c_vp, C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_double, c_dp, c_i64,
                                       C.c_uint64, c_i64, c_dp, c_i64, c_dp, c_i64]),
     "gsi_op_lowrank_fftrf_at": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_double,
@@ -59,6 +60,7 @@ SIGNATURES = {
     "gsi_op_fft_gridcov": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.c_int, c_dp, C.c_double, C.c_double,
                                      C.c_double]),
     "gsi_op_fft_gridcov_table": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), c_dp, c_dp, C.c_double]),
+    "gsi_op_fft_at": (C.c_int, [c_vp, C.POINTER(c_vp), c_vp, c_dp, c_i64, c_dp]),
     "gsi_gridcov_sampler_create": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.POINTER(c_i64), C.c_int, c_dp,
                                              C.c_double, C.c_double, C.c_double, C.c_double, c_dp]),
     "gsi_gridcov_sampler_info": (C.c_int, [c_vp, C.POINTER(c_i64), c_dp]),

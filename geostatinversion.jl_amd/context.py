@@ -247,6 +247,13 @@ def pointcov_implicit_operator(ctx, points, kind="exponential", ell=1.0, sigma2=
     return Operator(ctx, h)
 
 
+def _fft_grid_operator(ctx, h, Ns):
+    """An FFT covariance operator that remembers its grid (`Ns`), for `fft_operator_at`."""
+    op = Operator(ctx, h)
+    op.Ns = tuple(Ns)
+    return op
+
+
 def fft_powerlaw_operator(ctx, Ns, beta, fftrf=False):
     """Matrix-free power-law covariance on a structured grid (circulant embedding, spectrum |k|^beta, unit diagonal).
     `Ns` = grid points per axis (1 to 3 axes); the operator acts on vec(field) in Julia's (column-major) order.
@@ -261,7 +268,7 @@ def fft_powerlaw_operator(ctx, Ns, beta, fftrf=False):
     h = C.c_void_p()
     fn = ctx.lib.gsi_op_fft_powerlaw_fftrf if fftrf else ctx.lib.gsi_op_fft_powerlaw
     L.check(fn(ctx.h, C.byref(h), len(Ns), arr, float(beta)), ctx.lib)
-    return Operator(ctx, h)
+    return _fft_grid_operator(ctx, h, Ns)
 
 
 def fft_gridcov_operator(ctx, Ns, kind="exponential", ell=1.0, theta=0.0, sigma2=1.0, nugget=0.0, table=None,
@@ -287,7 +294,7 @@ def fft_gridcov_operator(ctx, Ns, kind="exponential", ell=1.0, theta=0.0, sigma2
         tm = lags(table_mirror, "table_mirror") if table_mirror is not None else None
         L.check(ctx.lib.gsi_op_fft_gridcov_table(ctx.h, C.byref(h), len(Ns), arr, t.ctypes.data_as(L.c_dp),
                                                  tm.ctypes.data_as(L.c_dp) if tm is not None else None, float(nugget)), ctx.lib)
-        return Operator(ctx, h)
+        return _fft_grid_operator(ctx, h, Ns)
     if table_mirror is not None:
         raise ValueError("table_mirror needs table")
     k = POINTCOV_KINDS[kind] if isinstance(kind, str) else int(kind)
@@ -297,7 +304,7 @@ def fft_gridcov_operator(ctx, Ns, kind="exponential", ell=1.0, theta=0.0, sigma2
     earr = (C.c_double * len(ells))(*ells)
     L.check(ctx.lib.gsi_op_fft_gridcov(ctx.h, C.byref(h), len(Ns), arr, k, earr, float(theta), float(sigma2), float(nugget)),
             ctx.lib)
-    return Operator(ctx, h)
+    return _fft_grid_operator(ctx, h, Ns)
 
 
 class DeviceMatrix(_Handle):

@@ -550,7 +550,9 @@ static void make_fft_powerlaw(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_
   // several ranks: every rank holds the plan (spectrum + work array) and transforms ITS columns of a panel; panels are
   // row-sharded between the products (pipeline.cpp: rows_to_cols / cols_to_rows), so row0 / mloc = the block-row layout
   default_shard(n, ctx->c.nranks(), ctx->c.rank(), &A.row0, &A.mloc);
-  A.plan = ctx->c.be->fftcov_create(N3, beta, fftrf);
+  A.fft_ndims = ndims;
+  for (int a = 0; a < 3; ++a) A.fft_N[a] = N3[a];
+  own_fft_plan(A, ctx->c.be->fftcov_create(N3, beta, fftrf));
   *op = o.release();
 }
 
@@ -612,8 +614,60 @@ static void make_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t
   Operator& A = o->op;
   A.ctx = &ctx->c; A.kind = OP_FFT_COV; A.m = n; A.n = n; A.ld = 0;
   default_shard(n, ctx->c.nranks(), ctx->c.rank(), &A.row0, &A.mloc);     // as make_fft_powerlaw: the plan is replicated
-  A.plan = ctx->c.be->fftcov_create_lags(N3, kind, ell3, theta, sigma2, nugget, table, table_mirror);
+  A.fft_ndims = ndims;
+  for (int a = 0; a < 3; ++a) A.fft_N[a] = N3[a];
+  own_fft_plan(A, ctx->c.be->fftcov_create_lags(N3, kind, ell3, theta, sigma2, nugget, table, table_mirror));
   *op = o.release();
+}
+
+// A = W C W' (OP_FFT_COV_AT): C = grid_op's covariance, whose plan is shared, W = the interpolation of
+// gsi_fftrf_interpolate at the m points on grid_op's own grid.  The points plan and its inverted index go to the device here
+// and stay there.
+int gsi_op_fft_at(gsi_ctx* ctx, gsi_op** op, const gsi_op* grid_op, const double* points, int64_t m, const double* box) {
+  return guarded([&] {
+    REQUIRE(ctx && op && grid_op, "NULL argument");
+    *op = nullptr;
+    const Operator& C = grid_op->op;
+    REQUIRE(C.ctx == &ctx->c, "gsi_op_fft_at: the grid operator belongs to another context");
+    REQUIRE(C.kind == OP_FFT_COV && C.plan != nullptr,
+            "gsi_op_fft_at: the grid operator must be an FFT covariance operator (gsi_op_fft_powerlaw[_fftrf], gsi_op_fft_gridcov[_table])");
+    REQUIRE(!ctx->c.comm, "gsi_op_fft_at: one GPU only -- not available on a context with a communicator");
+    REQUIRE(C.fft_ndims == 2 || C.fft_ndims == 3, "gsi_op_fft_at: the grid operator must have 2 or 3 axes (a 1-D grid is not supported)");
+    FftrfPointsPlan plan;
+    make_points_plan(C.fft_ndims, C.fft_N, points, m, box, 0, m, &plan);     // refuses an axis of fewer than 2 points, bad points
+    std::unique_ptr<gsi_op> o(new gsi_op());
+    Operator& A = o->op;
+    A.ctx = &ctx->c; A.kind = OP_FFT_COV_AT; A.m = m; A.n = m; A.row0 = 0; A.mloc = m; A.ld = 0;
+    A.fft_ndims = C.fft_ndims;
+    for (int a = 0; a < 3; ++a) A.fft_N[a] = C.fft_N[a];
+    A.plan = C.plan;
+    A.plan_ref = C.plan_ref;
+    A.at = ctx->c.be->points_at_create(plan, A.at_info);
+    *op = o.release();
+  });
+}
+
+int gsi_fftrf_spread(gsi_ctx* ctx, gsi_mat* grid_out, const gsi_mat* in, int ndims, const int64_t* N, const double* points,
+                     int64_t m, const double* box, int64_t row0) {
+  return guarded([&] {
+    REQUIRE(ctx && grid_out && in && grid_out->ctx == ctx && in->ctx == ctx, "bad argument");
+    REQUIRE(grid_out != in, "FFTRF spread: grid_out and in must be different matrices");
+    FftrfPointsPlan plan;
+    make_points_plan(ndims, N, points, m, box, row0, in->rows, &plan);
+    int64_t n = 0, mtot = 0;
+    check_fftrf_grid(ndims, N, 0.0, 1.0, 0.0, &n, &mtot);
+    REQUIRE(grid_out->rows == n, "FFTRF spread: grid_out must have n = prod(N) rows");
+    REQUIRE(grid_out->cols == in->cols, "FFTRF spread: grid_out and in must have one column per field");
+    Backend* be = ctx->c.be.get();
+    void* at = be->points_at_create(plan, nullptr);
+    try {
+      be->points_at_spread(at, grid_out->buf.p, grid_out->rows, grid_out->cols, in->buf.p, in->rows);
+    } catch (...) {
+      be->points_at_destroy(at);
+      throw;
+    }
+    be->points_at_destroy(at);      // (release is ordered on the stream: the kernels above still see the plan)
+  });
 }
 
 int gsi_op_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, int kind, const double* ell, double theta,

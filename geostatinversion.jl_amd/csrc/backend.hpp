@@ -346,6 +346,26 @@ class Backend {
     (void)dst; (void)ldd; (void)nf; (void)grid; (void)ldg; (void)plan;
     throw Error(1 /* GSI_ERR_ARG */, "FFTRF interpolation on the device: not available on this backend");
   }
+  // A points plan RESIDENT in backend memory, for operators that apply the interpolation matrix W (m_local x n) of the plan
+  // and its adjoint many times (OP_FFT_COV_AT): base and frac of fftrf_points.hpp and the inverted index of
+  // interp_adjoint_plan.hpp are uploaded once.  Opaque handle; info[4] (may be null) = resident bytes, long nodes, chunks of
+  // the long nodes, contributions of the longest node list.
+  virtual void* points_at_create(const FftrfPointsPlan& plan, int64_t info[4]) {
+    (void)plan; (void)info;
+    throw Error(1 /* GSI_ERR_ARG */, "interpolation plans resident on the device: not available on this backend");
+  }
+  virtual void points_at_destroy(void* at) { (void)at; }
+  // dst (m_local x nf, ld ldd) = W grid (n x nf, ld ldg): fftrf_interpolate without the upload
+  virtual void points_at_gather(void* at, double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg) {
+    (void)at; (void)dst; (void)ldd; (void)nf; (void)grid; (void)ldg;
+    throw Error(1 /* GSI_ERR_ARG */, "interpolation plans resident on the device: not available on this backend");
+  }
+  // grid (n x nf, ld ldg) = W' src (m_local x nf, ld lds), interp_adjoint.hip: every entry of grid is written (a node no
+  // point reaches gets 0.0); no atomics, bit-identical from call to call and whatever nf is
+  virtual void points_at_spread(void* at, double* grid, int64_t ldg, int64_t nf, const double* src, int64_t lds) {
+    (void)at; (void)grid; (void)ldg; (void)nf; (void)src; (void)lds;
+    throw Error(1 /* GSI_ERR_ARG */, "interpolation plans resident on the device: not available on this backend");
+  }
   // FFTRF.powerlaw_unstructuredgrid (FFTRF.jl:102-105): fftrf_fields whose every field is interpolated at the plan's points
   // while it is still in the batch workspace; the n x nf structured matrix is never formed.
   virtual void fftrf_fields_at(double* dst, int64_t ldd, int64_t nf, int ndims, const int64_t* N, double k0, double dk,

@@ -89,6 +89,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   struct GemmWs { double* p; size_t doubles; };      // the contractions' split-K workspace and how many doubles it holds
   struct Rec { Phase phase; hipEvent_t a, b; bool counted; };
   struct FftCov;                 // hip_backend_products.hip
+  struct PointsAt;               // hip_backend_products.hip
   struct GridCovSampler;         // hip_backend_sampler.hip
   struct LusWs;                  // hip_backend_panels.hip
   struct SplitWs;                // hip_backend_lowrank.hip
@@ -162,6 +163,10 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
                        const double* phi, int64_t ldphi, uint64_t seed, int64_t field0, const FftrfPointsPlan& plan) override;
   void fftrf_interpolate(double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg,
                          const FftrfPointsPlan& plan) override;
+  void* points_at_create(const FftrfPointsPlan& plan, int64_t info[4]) override;
+  void points_at_destroy(void* at) override;
+  void points_at_gather(void* at, double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg) override;
+  void points_at_spread(void* at, double* grid, int64_t ldg, int64_t nf, const double* src, int64_t lds) override;
 
   // ---- hip_backend_sampler.hip ----
   void* gridcov_sampler_create(int ndims, const int64_t N[3], const int64_t M[3], int kind, const double ell[3], double theta,

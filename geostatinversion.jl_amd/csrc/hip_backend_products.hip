@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "hip_backend_impl.hpp"
+#include "interp_adjoint_plan.hpp"
 
 namespace gsi {
 
@@ -322,6 +323,91 @@ void HipBackend::interp_batch(const FftrfPointsPlan& plan, const double* dplan, 
   hipk::fftrf_interp(st_, plan.ndims, reinterpret_cast<const int32_t*>(dplan + m * plan.ndims), dplan, m, plan.N[0],
                      plan.N[0] * plan.N[1], V, v_fs, nb, dst, ldd);
   check_launch("fftrf_interp");
+}
+// ---- a points plan resident in HBM: the forward plan and its inverted index (interp_adjoint_plan.hpp), one allocation ----
+struct HipBackend::PointsAt {
+  Scratch mem;
+  int ndims = 0;
+  int64_t N[3] = {1, 1, 1}, m = 0, n = 0;
+  const double* frac = nullptr;
+  const int32_t* base = nullptr;
+  hipk::IadjDev dev{};
+  explicit PointsAt(HipBackend* be) : mem(be) {}
+};
+void* HipBackend::points_at_create(const FftrfPointsPlan& plan, int64_t info[4]) {
+  bind();
+  const InterpAdjointPlan ip = interp_adjoint_plan(plan);
+  const int64_t m = plan.m_local, nc = (int64_t)1 << plan.ndims;
+  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+  Carve cv;
+  const size_t o_frac = cv.take((size_t)m * plan.ndims), o_base = cv.take(words(4 * (size_t)m)),
+               o_ptr = cv.take((size_t)ip.n + 1), o_point = cv.take(words(4 * (size_t)(nc * m))),
+               o_corner = cv.take(words((size_t)(nc * m))), o_lnode = cv.take(words(4 * (size_t)ip.nlong())),
+               o_lchunk = cv.take((size_t)ip.nlong() + 1), o_coff = cv.take((size_t)ip.nchunk()),
+               o_clen = cv.packed(words(4 * (size_t)ip.nchunk()));
+  std::unique_ptr<PointsAt> at(new PointsAt(this));
+  double* d = at->mem.p = alloc(cv.total);
+  std::vector<double> packed;
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes == 0) return;
+    packed.assign(words(bytes), 0.0);
+    std::memcpy(packed.data(), src, bytes);
+    upload2d(d + off, (int64_t)packed.size(), packed.data(), (int64_t)packed.size(), (int64_t)packed.size(), 1);
+  };
+  put(o_frac, plan.frac.data(), 8 * (size_t)m * plan.ndims);
+  put(o_base, plan.base.data(), 4 * (size_t)m);
+  put(o_ptr, ip.nodeptr.data(), 8 * ((size_t)ip.n + 1));
+  put(o_point, ip.point.data(), 4 * (size_t)(nc * m));
+  put(o_corner, ip.corner.data(), (size_t)(nc * m));
+  put(o_lnode, ip.long_node.data(), 4 * (size_t)ip.nlong());
+  put(o_lchunk, ip.long_chunk0.data(), 8 * ((size_t)ip.nlong() + 1));
+  put(o_coff, ip.chunk_off.data(), 8 * (size_t)ip.nchunk());
+  put(o_clen, ip.chunk_len.data(), 4 * (size_t)ip.nchunk());
+  at->ndims = plan.ndims;
+  for (int a = 0; a < 3; ++a) at->N[a] = plan.N[a];
+  at->m = m; at->n = ip.n;
+  at->frac = d + o_frac;
+  at->base = reinterpret_cast<const int32_t*>(d + o_base);
+  hipk::IadjDev& v = at->dev;
+  v.d = plan.ndims; v.n = ip.n; v.m = m; v.chunk = ip.chunk; v.nlong = ip.nlong(); v.nchunk = ip.nchunk();
+  v.nodeptr = reinterpret_cast<const int64_t*>(d + o_ptr);
+  v.point = reinterpret_cast<const int32_t*>(d + o_point);
+  v.corner = reinterpret_cast<const uint8_t*>(d + o_corner);
+  v.frac = at->frac;
+  v.long_node = reinterpret_cast<const int32_t*>(d + o_lnode);
+  v.long_chunk0 = reinterpret_cast<const int64_t*>(d + o_lchunk);
+  v.chunk_off = reinterpret_cast<const int64_t*>(d + o_coff);
+  v.chunk_len = reinterpret_cast<const int32_t*>(d + o_clen);
+  if (info) { info[0] = (int64_t)(8 * cv.total); info[1] = ip.nlong(); info[2] = ip.nchunk(); info[3] = ip.maxlen; }
+  return at.release();
+}
+void HipBackend::points_at_destroy(void* at) {
+  delete static_cast<PointsAt*>(at);
+}
+void HipBackend::points_at_gather(void* at_, double* dst, int64_t ldd, int64_t nf, const double* grid, int64_t ldg) {
+  bind();
+  const PointsAt* at = static_cast<const PointsAt*>(at_);
+  if (nf <= 0 || at->m <= 0) return;
+  for (int64_t f0 = 0; f0 < nf; f0 += 4096) {
+    const int b = (int)((nf - f0 < 4096) ? (nf - f0) : 4096);
+    hipk::fftrf_interp(st_, at->ndims, at->base, at->frac, at->m, at->N[0], at->N[0] * at->N[1], grid + f0 * ldg, ldg, b,
+                       dst + f0 * ldd, ldd);
+  }
+  check_launch("fftrf_interp");
+}
+// The column groups of interp_adjoint.hip ride in blockIdx.y: 4096 columns per launch stay far below its limit.  The chunk
+// sums of the long nodes live in a pooled temporary of nchunk x (columns of the launch).
+void HipBackend::points_at_spread(void* at_, double* grid, int64_t ldg, int64_t nf, const double* src, int64_t lds) {
+  bind();
+  const PointsAt* at = static_cast<const PointsAt*>(at_);
+  if (nf <= 0) return;
+  const int64_t step = nf < 4096 ? nf : 4096;
+  Scratch partial(this, (size_t)at->dev.nchunk * (size_t)step);
+  for (int64_t f0 = 0; f0 < nf; f0 += step) {
+    const int64_t b = (nf - f0 < step) ? (nf - f0) : step;
+    hipk::interp_adjoint(st_, at->dev, src + f0 * lds, lds, b, grid + f0 * ldg, ldg, partial.p);
+  }
+  check_launch("interp_adjoint");
 }
 void HipBackend::fftrf_batches(double* dst, int64_t ldd, int64_t row0, int64_t nloc, int64_t nf, int ndims, const int64_t* N, double k0,
                                double dk, double beta, const double* phi, int64_t ldphi, uint64_t seed, int64_t field0,

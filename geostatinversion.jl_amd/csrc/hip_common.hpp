@@ -130,6 +130,23 @@ void gcs_sample(hipStream_t st, const GcsGeom& g, const double* twg, const doubl
 // 1, s1, s2 along its axes; dst[p + b ldd] = the nested two-term sums, each product and sum rounded on its own
 void fftrf_interp(hipStream_t st, int d, const int32_t* base, const double* frac, int64_t m, int64_t s1, int64_t s2,
                   const double* V, int64_t v_fs, int nb, double* dst, int64_t ldd);
+// ---- interp_adjoint.hip: the adjoint of that gather, G = W' X, through the inverted index of interp_adjoint_plan.hpp ----
+// The index and the points plan's frac on the device (arrays as documented there).  G (n x nf, ld ldg): every entry is
+// written, a node nobody reaches gets 0.0; X is m x nf (ld ldx); partial: nchunk x nf doubles (unused when nchunk == 0).
+struct IadjDev {
+  int d;
+  int64_t n, m, chunk, nlong, nchunk;
+  const int64_t* nodeptr;
+  const int32_t* point;
+  const uint8_t* corner;
+  const double* frac;
+  const int32_t* long_node;
+  const int64_t* long_chunk0;
+  const int64_t* chunk_off;
+  const int32_t* chunk_len;
+};
+void interp_adjoint(hipStream_t st, const IadjDev& p, const double* X, int64_t ldx, int64_t nf, double* G, int64_t ldg,
+                    double* partial);
 
 // ---- panel_lu_leaf.hip: register-resident leaves (panels of <= 4096 rows per CU, a little more with overflow rows); the
 //      updates between the blocks are panel_lu_blocks.hip's ----

@@ -35,7 +35,14 @@ void check_async_errors(Context& c) {
 }
 
 Operator::~Operator() {
-  if (plan && ctx && ctx->be) ctx->be->fftcov_destroy(plan);
+  if (at && ctx && ctx->be) ctx->be->points_at_destroy(at);
+  // (the FFT plan goes with the last holder of plan_ref)
+}
+void own_fft_plan(Operator& A, void* plan) {
+  Context* c = A.ctx;
+  // (if the control block cannot be allocated, shared_ptr's constructor calls the deleter itself before it throws)
+  A.plan_ref = std::shared_ptr<void>(plan, [c](void* p) { if (p && c && c->be) c->be->fftcov_destroy(p); });
+  A.plan = plan;
 }
 
 // C (m x l) = G[roff .. roff + m, koff .. koff + k) * B for the two generated (never stored) symmetric covariances: a table
@@ -86,9 +93,42 @@ static void lowrank_ScT(const Operator& A, const double* T, int64_t l, double* Y
   be->gemm_nn(A.mloc, l, A.N, 1.0 / (double)(A.N - 1), A.data.p, A.ld, T, A.N, 0.0, Yloc, ldy);
 }
 
+// OP_FFT_COV_AT: Y (m x l) = W C W' X, one rank.  The caller holds only m x l, so the two n x lb grid panels are the
+// operator's own: spread into G, the grid product into H, gather into the caller's rows, lb columns at a time.  lb is even
+// (two real columns ride in one complex transform, so the pairs are the same whatever lb is) and keeps both panels within
+// 2 GiB; GSI_FFT_AT_BATCH=<b> (read at every call) overrides it.  A is symmetric to rounding: A' X is the same product.
+// Profiling attributes the three stages to three phases (tools/fft_at_bench.py): W' as gemm_t, C as gemm_n, W as other.
+static int64_t fft_at_batch(int64_t n, int64_t l) {
+  int64_t lb = (((int64_t)2 << 30) / (int64_t)sizeof(double)) / (2 * std::max<int64_t>(n, 1));
+  if (const char* e = getenv("GSI_FFT_AT_BATCH")) { if (atoll(e) >= 1) lb = atoll(e); }
+  lb += lb & 1;
+  lb = std::min(lb, l + (l & 1));
+  return std::max<int64_t>(lb, 2);
+}
+static void fft_at_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Y, int64_t ldy) {
+  Backend* be = A.ctx->be.get();
+  if (A.ctx->comm) throw Error(GSI_ERR_INTERNAL, "an FFT covariance at scattered points runs on one rank only");
+  if (l <= 0) return;
+  const int64_t n = A.fft_N[0] * A.fft_N[1] * A.fft_N[2], lb = fft_at_batch(n, l);
+  Buf G(be, (size_t)n * lb), H(be, (size_t)n * lb);
+  for (int64_t c0 = 0; c0 < l; c0 += lb) {
+    const int64_t b = std::min(lb, l - c0);
+    const bool first = c0 == 0;
+    auto stage = [&](Phase ph, auto&& f) {      // one counted entry per product and phase, the later batches add their time
+      be->phase_begin(ph);
+      try { f(); } catch (...) { be->phase_end(ph); throw; }
+      if (first) be->phase_end(ph); else be->phase_end_more(ph);
+    };
+    stage(PH_GEMM_T, [&] { be->points_at_spread(A.at, G.p, n, b, X + c0 * ldx, ldx); });
+    stage(PH_GEMM_N, [&] { be->fftcov_apply(A.plan, b, G.p, n, H.p, n); });
+    stage(PH_OTHER, [&] { be->points_at_gather(A.at, Y + c0 * ldy, ldy, b, H.p, n); });
+  }
+}
+
 void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Yloc, int64_t ldy) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
+  if (A.kind == OP_FFT_COV_AT) { fft_at_mul(A, X, ldx, l, Yloc, ldy); return; }
   // a rank without rows (m < rank * ceil(m / G)) has nothing to compute, but it still takes part in every
   // collective below: only the collective-free operator kinds may leave early
   if (A.mloc == 0 && A.kind != OP_LOWRANK && !(A.kind == OP_FFT_COV && c.comm)) return;
@@ -135,6 +175,7 @@ void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* 
     implicit_mul(be, A, A.mloc, l, A.n, A.row0, 0, X, ldx, Yloc, ldy);
     return;
   }
+  if (A.kind != OP_LOWRANK) throw Error(GSI_ERR_INTERNAL, "op_mul: unknown operator kind");
   Buf T(be, (size_t)A.N * l);
   lowrank_StX(A, X + A.row0, ldx, l, T.p);
   lowrank_ScT(A, T.p, l, Yloc, ldy);
@@ -260,6 +301,7 @@ static void fft_mul_rows(const Operator& A, const double* Xloc, int64_t ldx, int
 void op_mul_t(const Operator& A, const double* Xloc, int64_t ldx, int64_t l, double* Z, int64_t ldz) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
+  if (A.kind == OP_FFT_COV_AT) { fft_at_mul(A, Xloc, ldx, l, Z, ldz); return; }   // symmetric to rounding, as OP_FFT_COV
   if (A.kind == OP_FFT_COV) {     // symmetric: A' X = A X
     if (!c.comm) {
       ScopedPhase ph(be, PH_GEMM_T);
@@ -322,6 +364,7 @@ void op_mul_t(const Operator& A, const double* Xloc, int64_t ldx, int64_t l, dou
     }
     return;
   }
+  if (A.kind != OP_LOWRANK) throw Error(GSI_ERR_INTERNAL, "op_mul_t: unknown operator kind");
   // adjoint(A::LowRankCovMatrix) === A  (lowrank.jl:38-40): A'*X = A*X, rows then gathered
   Buf T(be, (size_t)A.N * l);
   lowrank_StX(A, Xloc, ldx, l, T.p);
@@ -344,6 +387,7 @@ static Buf op_mul_t_sharded(const Operator& A, const double* Xloc, int64_t ldx, 
   Backend* be = c.be.get();
   const int G = c.nranks();
   const int64_t n = A.n, pad = (n + G - 1) / G;
+  if (A.kind == OP_FFT_COV_AT) throw Error(GSI_ERR_INTERNAL, "an FFT covariance at scattered points runs on one rank only");
   if (A.kind == OP_LOWRANK) {
     Buf T(be, (size_t)A.N * l);
     lowrank_StX(A, Xloc, ldx, l, T.p);

@@ -54,7 +54,7 @@ struct Context {
   int nranks() const { return comm ? comm->nranks : 1; }
 };
 
-enum OpKind { OP_DENSE = 0, OP_LOWRANK = 1, OP_GRIDCOV_IMPLICIT = 2, OP_FFT_COV = 3, OP_POINTCOV = 4 };
+enum OpKind { OP_DENSE = 0, OP_LOWRANK = 1, OP_GRIDCOV_IMPLICIT = 2, OP_FFT_COV = 3, OP_POINTCOV = 4, OP_FFT_COV_AT = 5 };
 
 // A linear operator m x n; this rank holds rows [row0, row0 + mloc).
 struct Operator {
@@ -68,7 +68,17 @@ struct Operator {
   // OP_POINTCOV (scattered points): data = the d x n coordinates; entries generated panel by panel, never stored whole
   int pc_d = 0, pc_kind = 0;
   double pc_ell = 1.0, pc_sigma2 = 1.0, pc_nugget = 0.0;
-  void* plan = nullptr;     // OP_FFT_COV: the backend's circulant-embedding plan (owned; single rank)
+  // OP_FFT_COV: the backend's circulant-embedding plan.  plan_ref owns it (own_fft_plan) and is shared with every
+  // OP_FFT_COV_AT built on this operator: the plan lives until the last of them is destroyed, in whatever order.
+  void* plan = nullptr;
+  std::shared_ptr<void> plan_ref;
+  int fft_ndims = 0;                    // OP_FFT_COV / OP_FFT_COV_AT: the grid as the caller gave it (axes of one point included)
+  int64_t fft_N[3] = {1, 1, 1};
+  // OP_FFT_COV_AT (m x m, one rank): A = W C W', C the grid operator whose plan is shared above, W the multilinear
+  // interpolation at m scattered points.  at = Backend::points_at_create's handle (owned): the points plan and its inverted
+  // index, resident for the operator's lifetime; at_info = what that call reported.
+  void* at = nullptr;
+  int64_t at_info[4] = {0, 0, 0, 0};
   // OP_DENSE whose rows are still crossing PCIe (gsi_randsvd_dense_host / gsi_rangefinder_dense_host): the handle of
   // Backend::upload2d_begin and its row-block height.  The FIRST product A*X consumes it -- block by block as the rows land,
   // bit-identical to the product of the resident matrix -- and clears it; the entry point's guard ends the upload on every
@@ -83,6 +93,9 @@ struct Operator {
   Operator& operator=(const Operator&) = delete;
   ~Operator();
 };
+
+// A.plan = plan, owned by A.plan_ref: destroyed through the context's backend when the last holder lets go
+void own_fft_plan(Operator& A, void* plan);
 
 // block-row layout used whenever a caller does not supply one
 void default_shard(int64_t m, int nranks, int rank, int64_t* row0, int64_t* mloc);

@@ -146,6 +146,124 @@ def interpolate(ctx, points, F, Ns, *, box=None, row0=0, rows=None):
             G.close()
 
 
+def spread(ctx, points, V, Ns, *, box=None):
+    """The adjoint of `interpolate` (`gsi_fftrf_spread`): `V` is a `DeviceMatrix` of m x nf (or a host array, uploaded) of
+    values at the m `points`; returns a `DeviceMatrix` of n x nf, n = prod(Ns), whose entry (g, c) is the sum over the points
+    that have node g as a corner of their cell of weight * V[p, c], with `interpolate`'s weights: W' V where
+    `interpolate` applies W.  Bins point data onto the grid; every entry is written, untouched nodes are exactly 0.0, and
+    the result is bit-identical from call to call (no atomics: fixed summation order per node)."""
+    Ns, arr = _grid(Ns)
+    P, B = _points_args(points, box, len(Ns))
+    m = P.shape[1]
+    own = not isinstance(V, DeviceMatrix)
+    if own:
+        Vh = np.asarray(V, dtype=np.float64)
+        X = DeviceMatrix.from_host(ctx, Vh.reshape(Vh.shape[0], -1))
+    else:
+        X = V
+    try:
+        if X.shape[0] < m:
+            raise ValueError(f"V must have one row per point: {m} rows, not {X.shape[0]}")
+        out = DeviceMatrix(ctx, int(np.prod(Ns)), X.shape[1])
+        try:
+            L.check(ctx.lib.gsi_fftrf_spread(ctx.h, out.h, X.h, len(Ns), arr, L.dptr(P), m, _box_ptr(B), 0), ctx.lib)
+        except Exception:
+            out.close()
+            raise
+        return out
+    finally:
+        if own:
+            X.close()
+
+
+def _host_plan(P, Ns, B):
+    """fftrf_points.hpp in numpy, operation for operation: (lo, hi, base index per axis, frac per axis) of the points."""
+    d, m = P.shape
+    lo = P.min(axis=1) if B is None else B[:d].copy()
+    hi = P.max(axis=1) if B is None else B[d:].copy()
+    cell = np.empty((d, m), dtype=np.int64)
+    frac = np.empty((d, m))
+    for a in range(d):
+        step = (hi[a] - lo[a]) / float(Ns[a] - 1)
+        top = float(Ns[a] - 1)
+        t = np.minimum(np.maximum((P[a] - lo[a]) / step, 0.0), top)
+        fl = np.minimum(np.floor(t), top - 1.0)
+        cell[a] = fl.astype(np.int64)
+        frac[a] = t - fl
+    return lo, hi, cell, frac
+
+
+class FFTOperatorAt(Operator):
+    """`fft_operator_at`'s result: the m x m operator W C W' (`gsi_op_fft_at`).  `grid_op` stays referenced; `steps` is the
+    physical size of a grid spacing per axis, (hi - lo) / (N - 1): the grid operator's `ell` is in GRID SPACINGS, so a
+    physical length L along axis a is L / steps[a] spacings (a grid whose steps differ per axis needs per-axis `ell`)."""
+
+    def __init__(self, ctx, h, grid_op, Ns, P, B):
+        super().__init__(ctx, h)
+        self.grid_op = grid_op
+        self.Ns = tuple(Ns)
+        self._P, self._B = P, B
+        d = len(self.Ns)
+        self.lo = P.min(axis=1) if B is None else B[:d].copy()
+        self.hi = P.max(axis=1) if B is None else B[d:].copy()
+        self.steps = (self.hi - self.lo) / (np.asarray(Ns, dtype=np.float64) - 1.0)
+
+    def diagonal(self):
+        """diag(W C W'), the prior variances at the points (what `posterior_variance(..., prior_variance=...)` wants), on
+        the host.  C is block Toeplitz, so a point's variance is the sum over pairs of corners of its cell of
+        w_a w_b c(a - b) and needs c at the lags {-1, 0, 1}^d only: they are read from 2^(d-1) unit-vector columns of the
+        grid operator (c(-t) = c(t) gives the rest).  Nothing m x m or n x n is formed.  A nugget of the grid operator is
+        part of c(0) and is interpolated like everything else."""
+        Ns, d = self.Ns, len(self.Ns)
+        n = int(np.prod(Ns))
+        strides = np.cumprod([1] + list(Ns[:-1]))
+        # unit vectors at the nodes (0, j1[, j2]), j in {0, 1}: column j holds c(i - j) for every node i
+        js = [(0,) + tuple((k >> a) & 1 for a in range(d - 1)) for k in range(1 << (d - 1))]
+        E = np.zeros((n, len(js)), order="F")
+        for k, j in enumerate(js):
+            E[int(np.dot(j, strides)), k] = 1.0
+        Ccols = self.grid_op.matmul(E)
+        lag = np.zeros((3,) * d)                       # lag[t + 1] = c(t), t in {-1, 0, 1}^d
+        for k, j in enumerate(js):
+            for i in np.ndindex(*((2,) * d)):
+                t = tuple(int(ia - ja) for ia, ja in zip(i, j))
+                v = Ccols[int(np.dot(i, strides)), k]
+                lag[tuple(ta + 1 for ta in t)] = v
+                lag[tuple(1 - ta for ta in t)] = v   # central symmetry
+        _, _, _, frac = _host_plan(self._P, Ns, self._B)
+        corners = list(np.ndindex(*((2,) * d)))
+        W = [np.prod([frac[a] if c[a] else 1.0 - frac[a] for a in range(d)], axis=0) for c in corners]
+        out = np.zeros(self._P.shape[1])
+        for ka, a in enumerate(corners):
+            for kb, b in enumerate(corners):
+                out += W[ka] * W[kb] * lag[tuple(a[x] - b[x] + 1 for x in range(d))]
+        return out
+
+
+def fft_operator_at(ctx, grid_op, points, *, box=None):
+    """An FFT covariance operator read at scattered points (`gsi_op_fft_at`): A = W C W', m x m, with C the covariance of
+    `grid_op` (from `fft_gridcov_operator` or `fft_powerlaw_operator`, 2 or 3 axes of at least 2 points) and W the
+    interpolation matrix of `interpolate` at `points` (ndims x m) on that grid, spanned by the points' extrema or `box`.
+    It is exactly the covariance of a field with covariance C read at the points: matrix-free, no rank cap, no sampling
+    noise; one product is a spread, a grid product and a gather, and the points plan stays in HBM.  One GPU only.
+    The grid operator's `ell` is in grid spacings (see `steps` of the result; steps that differ per axis need per-axis
+    `ell`).  A `nugget` on the grid operator is interpolated with everything else: noise at the points is the caller's R.
+    Usable wherever an `Operator` is: `randsvd`, `rangefinder`, `eig_nystrom`, `getxis_device`."""
+    Ns = getattr(grid_op, "Ns", None)
+    h = C.c_void_p()
+    if Ns is None or len(Ns) not in (2, 3):
+        # not an FFT grid operator of 2 or 3 axes: the library names the limit
+        P = np.asfortranarray(np.asarray(points, dtype=np.float64))
+        if P.ndim != 2:
+            raise ValueError("points must be ndims x m (one column per point)")
+        L.check(ctx.lib.gsi_op_fft_at(ctx.h, C.byref(h), grid_op.h, L.dptr(P), P.shape[1], None), ctx.lib)
+        ctx.lib.gsi_op_destroy(h)
+        raise ValueError("grid_op is not an FFT covariance operator made by this package")
+    P, B = _points_args(points, box, len(Ns))
+    L.check(ctx.lib.gsi_op_fft_at(ctx.h, C.byref(h), grid_op.h, L.dptr(P), P.shape[1], _box_ptr(B)), ctx.lib)
+    return FFTOperatorAt(ctx, h, grid_op, Ns, P, B)
+
+
 def powerlaw_unstructuredgrid(points, Ns, k0, dk, beta, *, phi=None, seed=None, box=None, ctx=None):
     """`FFTRF.powerlaw_unstructuredgrid(points, Ns, k0, dk, beta)` -> ndarray of m values, one per column of `points`.
     `phi`, `seed`: as in `powerlaw_structuredgrid`; `box`: the grid's extent instead of the points' extrema."""

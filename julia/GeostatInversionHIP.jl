@@ -240,6 +240,42 @@ function lowrank_fftrf_operator(points::Matrix{Float64}, Ns::Vector{Int}, k0::Fl
 	return op
 end
 
+"The adjoint of `FFTRF.interpolate` on the device (`gsi_fftrf_spread`): `V` (m x nf, values at the m `points`) spread onto
+the grid `Ns` with the interpolation weights; returns the n x nf `DeviceMatrix` W' V.  Every entry is written, untouched
+nodes are exactly 0.0, and the result is bit-identical from call to call."
+function fftrf_spread(points::Matrix{Float64}, V, Ns::Vector{Int};      # V: a DeviceMatrix (defined below)
+		box::Union{Nothing,Vector{Float64}}=nothing, c::Context=ctx())
+	N64 = Int64.(Ns)
+	size(points, 1) == length(Ns) || error("points must be ndims x m")
+	box === nothing || length(box) == 2 * length(Ns) || error("box must hold 2 ndims values")
+	m = size(points, 2)
+	V.rows == m || error("V must have one row per point")
+	G = DeviceMatrix(prod(Ns), V.cols; c=c)
+	bx = box === nothing ? Ptr{Float64}(C_NULL) : pointer(box)
+	GC.@preserve box check(ccall((:gsi_fftrf_spread, libgsi), Cint,
+		(Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+		c.h, G.h, V.h, length(N64), N64, points, m, bx, 0))
+	return G
+end
+
+"An FFT covariance operator read at scattered points (`gsi_op_fft_at`): W C W', m x m, with C the covariance of `grid_op`
+(an `FFTGridCovariance` or power-law FFT operator with 2 or 3 axes of at least 2 points) and W the interpolation at `points`
+(d x m) on its grid.  The grid operator's lengths are in grid spacings; its nugget is interpolated with everything else.
+The plan of `grid_op` is shared: the two operators may be finalized in either order.  One GPU only."
+function fft_operator_at(grid_op::DeviceOperator, points::Matrix{Float64};
+		box::Union{Nothing,Vector{Float64}}=nothing, c::Context=ctx())
+	r = Ref{Ptr{Cvoid}}(C_NULL)
+	box === nothing || length(box) == 2 * size(points, 1) || error("box must hold 2 ndims values")
+	m = size(points, 2)
+	bx = box === nothing ? Ptr{Float64}(C_NULL) : pointer(box)
+	GC.@preserve box check(ccall((:gsi_op_fft_at, libgsi), Cint,
+		(Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}),
+		c.h, r, grid_op.h, points, m, bx))
+	op = DeviceOperator(r[], c, m, m)
+	finalizer(finalize_op!, op)
+	return op
+end
+
 # ---- Gaussian fields with a grid covariance function (circulant embedding, gsi_gridcov_sampler_*) --
 const GRIDCOV_KINDS = Dict("gaussian" => 0, "exponential" => 1, "matern32" => 2, "matern52" => 3)
 
