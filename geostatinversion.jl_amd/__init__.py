@@ -22,6 +22,8 @@ from . import fftrf as FFTRF
 from .fftrf import lowrank_fftrf_operator, fft_operator_at, FFTOperatorAt
 from . import gridcov as GridCov
 from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, gridcov_structuredgrid
+from . import kriging as Kriging
+from .kriging import solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
                    posterior_realizations)
 
@@ -32,4 +34,5 @@ __all__ = [
     "getxis", "getxis_iwantfields", "getxis_device", "getxis_fftrf", "randsvdwithseed", "FFTRF", "lowrank_fftrf_operator", "fft_operator_at", "FFTOperatorAt", "GridCov", "GridCovSampler",
     "gridcov_sampler", "lowrank_gridcov_operator", "gridcov_structuredgrid", "pcgadirect", "pcgalsqr", "rga", "pcga",
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",
+    "Kriging", "solve", "kriging_weights", "krige_to_grid", "condition_fields", "mat_axpy",
 ]

@@ -101,6 +101,10 @@ SIGNATURES = {
     "gsi_pcga_update_dev": (C.c_int, [c_vp, c_vp, c_i64, c_dp, C.c_double, c_dp, c_i64, c_dp, c_dp]),
     "gsi_mat_download_col": (C.c_int, [c_vp, c_vp, c_i64, c_dp]),
     "gsi_op_lowrank_solve": (C.c_int, [c_vp, c_vp, c_dp, c_dp, C.POINTER(c_i64)]),
+    "gsi_op_solve_cg": (C.c_int, [c_vp, c_vp, c_dp, c_vp, c_vp, C.c_double, c_i64, C.POINTER(c_i64), c_dp, C.POINTER(c_i64)]),
+    "gsi_op_solve": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_i64, c_i64, c_dp, c_i64, C.c_double, c_i64, C.POINTER(c_i64), c_dp,
+                               C.POINTER(c_i64)]),
+    "gsi_mat_axpy": (C.c_int, [c_vp, C.c_double, c_vp, c_vp]),
     "gsi_pcgamat_create": (C.c_int, [c_vp, C.POINTER(c_vp), c_dp, c_i64, c_i64, c_dp, c_dp, C.c_int]),
     "gsi_pcgamat_destroy": (C.c_int, [c_vp]),
     "gsi_pcgamat_mul": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),

@@ -175,6 +175,11 @@ class Operator(_Handle):
 
     __matmul__ = matmul
 
+    def solve(self, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=False):
+        """`(A + diag) \\ B` by conjugate gradients on the device, all columns together: `kriging.solve`."""
+        from .kriging import solve
+        return solve(self, B, diag=diag, tol=tol, maxiter=maxiter, strict=strict, return_info=return_info)
+
 
 def dense_operator(ctx, A):
     """`Matrix{Float64}` operator.  With a communicator, `A` is the full matrix and only this rank's

@@ -1335,6 +1335,83 @@ int gsi_op_lowrank_solve(gsi_ctx* ctx, const gsi_op* op, const double* b, double
   });
 }
 
+// ---- kriging systems: block CG on any operator ------------------------------------------
+namespace {
+// the checks that need no memory, the upload of diag, the solve on resident panels, and the report: info, relres and iters
+// are filled before a breakdown is raised
+void solve_cg_resident(gsi_ctx* ctx, const Operator& A, const double* diag, const double* Bd, double* Xd, int64_t b, double tol,
+                       int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  Backend* be = ctx->c.be.get();
+  Buf dd;
+  if (diag) {
+    dd = Buf(be, (size_t)A.n);
+    be->upload2d(dd.p, A.n, diag, A.n, A.n, 1);
+  }
+  const BlockCgInfo r = block_cg(A, diag ? dd.p : nullptr, Bd, Xd, b, tol, maxiter, relres, iters);
+  if (info) { info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column; }
+  check_async_errors(ctx->c);
+  if (r.breakdown_column != 0)
+    throw Error(GSI_ERR_NOT_POSDEF, "conjugate gradients: A + diag is not positive definite along the search direction of column " +
+                                        std::to_string(r.breakdown_column));
+}
+void check_solve_args(gsi_ctx* ctx, const gsi_op* op, const double* diag, int64_t b, double tol, int64_t maxiter, int64_t* info) {
+  if (info) info[0] = info[1] = info[2] = info[3] = 0;
+  REQUIRE(ctx && op, "gsi_op_solve: ctx or op is NULL");
+  REQUIRE(op->op.ctx == &ctx->c, "gsi_op_solve: op belongs to another context");
+  block_cg_check(op->op, b, tol, maxiter);
+  if (diag)
+    for (int64_t i = 0; i < op->op.n; ++i)
+      if (!(diag[i] >= 0.0 && diag[i] <= 1.79769313486231570815e308))
+        throw Error(GSI_ERR_ARG, "gsi_op_solve: diag[" + std::to_string(i) + "] is negative or not finite");
+}
+}  // namespace
+
+int gsi_op_solve_cg(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_mat* B, gsi_mat* X, double tol,
+                    int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  return guarded([&] {
+    REQUIRE(B && X, "gsi_op_solve_cg: B or X is NULL");
+    check_solve_args(ctx, op, diag, B->cols, tol, maxiter, info);
+    const Operator& A = op->op;
+    REQUIRE(B->ctx == ctx && X->ctx == ctx, "gsi_op_solve_cg: B or X belongs to another context");
+    REQUIRE(B->rows == A.n, "gsi_op_solve_cg: B must have size(A, 1) rows");
+    REQUIRE(X->rows == A.n && X->cols == B->cols, "gsi_op_solve_cg: X must have the shape of B");
+    REQUIRE(X != B && X->buf.p != B->buf.p, "gsi_op_solve_cg: X must not be B");
+    solve_cg_resident(ctx, A, diag, B->buf.p, X->buf.p, B->cols, tol, maxiter, info, relres, iters);
+  });
+}
+
+int gsi_op_solve(gsi_ctx* ctx, const gsi_op* op, const double* diag, const double* B, int64_t ldb, int64_t b, double* X,
+                 int64_t ldx, double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  return guarded([&] {
+    REQUIRE(B && X, "gsi_op_solve: B or X is NULL");
+    check_solve_args(ctx, op, diag, b, tol, maxiter, info);
+    const Operator& A = op->op;
+    REQUIRE(ldb >= A.n, "gsi_op_solve: ldb is smaller than size(A, 1), the rows of B");
+    REQUIRE(ldx >= A.n, "gsi_op_solve: ldx is smaller than size(A, 1), the rows of X");
+    REQUIRE(X != B, "gsi_op_solve: X must not be B");
+    Backend* be = ctx->c.be.get();
+    Buf Bd(be, (size_t)A.n * b), Xd(be, (size_t)A.n * b);
+    be->upload2d(Bd.p, A.n, B, ldb, A.n, b);
+    // (the solution comes back also when the solve broke down: what the columns had reached)
+    try {
+      solve_cg_resident(ctx, A, diag, Bd.p, Xd.p, b, tol, maxiter, info, relres, iters);
+    } catch (const Error& e) {
+      if (e.code == GSI_ERR_NOT_POSDEF) be->download2d(X, ldx, Xd.p, A.n, A.n, b);
+      throw;
+    }
+    be->download2d(X, ldx, Xd.p, A.n, A.n, b);
+  });
+}
+
+int gsi_mat_axpy(gsi_ctx* ctx, double alpha, const gsi_mat* X, gsi_mat* Y) {
+  return guarded([&] {
+    REQUIRE(ctx && X && Y, "gsi_mat_axpy: NULL argument");
+    REQUIRE(X->ctx == ctx && Y->ctx == ctx, "gsi_mat_axpy: X or Y belongs to another context");
+    REQUIRE(X->rows == Y->rows && X->cols == Y->cols, "gsi_mat_axpy: X and Y must have the same shape");
+    ctx->c.be->axpy(X->rows * X->cols, alpha, X->buf.p, Y->buf.p);
+  });
+}
+
 int gsi_pcgamat_create(gsi_ctx* ctx, gsi_pcgamat** mat, const double* etas, int64_t nobs, int64_t K, const double* HX,
                        const double* R, int r_is_diag) {
   return guarded([&] {

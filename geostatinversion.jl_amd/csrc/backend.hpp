@@ -428,6 +428,25 @@ class Backend {
   virtual void lsqr_step_v(int64_t n, const double* t, double* v, double* w, double* x, double* work) = 0;
   //                                     v = t - beta v; alpha; the recurrences and stopping rules; v /= alpha; x += t1 w; w = v + t2 w
 
+  // ---- conjugate gradients on (A + diag(d)) X = B, all b columns together, with the per-column recurrences resident in
+  //      backend memory (cg_state.hpp): `work` holds block_cg_work_doubles(b) doubles = [state |
+  //      partial sums]; pipeline.cpp:block_cg sequences the operator product Q = A P around these and polls the state's
+  //      header every few iterations.  Panels n x b, ld n; d (n, may be null) >= 0.
+  //      block_cg_work_doubles: 0 = "not mine" (the default), and pipeline.cpp runs the same recurrences column by column
+  //      with op_mul, diag_mul_add, dot, axpy and scal.
+  virtual size_t block_cg_work_doubles(int64_t b) { (void)b; return 0; }
+  // R and P hold B, X is zero: the columns' norms and the state of a fresh solve
+  virtual void block_cg_begin(int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work) {
+    (void)n; (void)b; (void)B; (void)tol; (void)maxiter; (void)work;
+    throw Error(1 /* GSI_ERR_ARG */, "block_cg: not available on this backend");
+  }
+  // after Q = A P: alpha; x += alpha p, r -= alpha (q + d .* p); beta and the stopping rule; p = r + beta p
+  virtual void block_cg_step(int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
+                             double* work) {
+    (void)n; (void)b; (void)Q; (void)d; (void)X; (void)R; (void)P; (void)work;
+    throw Error(1 /* GSI_ERR_ARG */, "block_cg: not available on this backend");
+  }
+
   // ---- fp32-STORED xi-basis (BASELINE configs[4], "fp32 mixed precision"): the n x K basis is the one big HBM stream
   //      of the PCGA iteration's own algebra; stored in fp32 it is half the bytes, every sum stays in fp64 ----
   virtual void f64_to_f32(const double* src, void* dst32, size_t count) = 0;

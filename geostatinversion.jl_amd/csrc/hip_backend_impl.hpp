@@ -6,7 +6,7 @@
 //   hip_backend_sampler.hip   fields with a grid covariance function by circulant embedding: plan and batches
 //   hip_backend_panels.hip    panel LU (one rank and row-sharded), the QR tiers, the fused tall SVD, the small factorizations
 //   hip_backend_lowrank.hip   the LowRankCovMatrix chains in sample space
-//   hip_backend_pcga.hip      BLAS-1/2, LSQR and the PCGA consumers
+//   hip_backend_pcga.hip      BLAS-1/2, LSQR, block CG and the PCGA consumers
 #pragma once
 #include <map>
 #include <memory>
@@ -247,6 +247,10 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   void lsqr_begin(int64_t n, const double* w, double* work) override;
   void lsqr_step_u(int64_t m, const double* t, double* u, double* work) override;
   void lsqr_step_v(int64_t n, const double* t, double* v, double* w, double* x, double* work) override;
+  size_t block_cg_work_doubles(int64_t b) override { return hipk::block_cg_work_doubles(b); }
+  void block_cg_begin(int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work) override;
+  void block_cg_step(int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
+                     double* work) override;
   void f64_to_f32(const double* src, void* dst32, size_t count) override;
   void pcga_params(const double* Z, int64_t n, int64_t K, const double* s, const double* X, double delta,
                    double* out) override;

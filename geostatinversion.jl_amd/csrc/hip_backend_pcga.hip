@@ -74,6 +74,17 @@ void HipBackend::lsqr_step_v(int64_t n, const double* t, double* v, double* w, d
   hipk::lsqr_step_v(st_, n, t, v, w, x, work);
   check_launch("lsqr_step_v");
 }
+void HipBackend::block_cg_begin(int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work) {
+  bind();
+  hipk::block_cg_begin(st_, n, b, B, tol, maxiter, work);
+  check_launch("block_cg_begin");
+}
+void HipBackend::block_cg_step(int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
+                               double* work) {
+  bind();
+  hipk::block_cg_step(st_, n, b, Q, d, X, R, P, work);
+  check_launch("block_cg_step");
+}
 void HipBackend::f64_to_f32(const double* src, void* dst32, size_t count) {
   bind();
   hipk::f64_to_f32(st_, src, (float*)dst32, count);

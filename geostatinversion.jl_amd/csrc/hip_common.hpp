@@ -231,6 +231,12 @@ void lsqr_begin(hipStream_t st, int64_t n, const double* w, double* work);
 void lsqr_step_u(hipStream_t st, int64_t m, const double* t, double* u, double* work);
 void lsqr_step_v(hipStream_t st, int64_t n, const double* t, double* v, double* w, double* x, double* work);
 
+// ---- block_cg.hip: the multi-column conjugate-gradient solver's panel passes with device-resident scalars (cg_state.hpp) ----
+size_t block_cg_work_doubles(int64_t b);
+void block_cg_begin(hipStream_t st, int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work);
+void block_cg_step(hipStream_t st, int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
+                   double* work);
+
 // ---- panel_qr.hip ----
 constexpr int QR_NB = 16;
 struct QrWork {

@@ -12,6 +12,7 @@
 //                QR of the stack, local fix-up Q_g <- Q_g * Q2_g
 #include "pipeline.hpp"
 #include "lsqr_state.hpp"
+#include "block_cg_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1171,6 +1172,75 @@ int64_t lowrank_solve(const Operator& A, const double* b, double* x) {
   };
   L.mul_t = L.mul;
   return lsqr(c, L, b, x, A.N);                        // maxiter = length(A.samples)   lowrank.jl:142
+}
+
+// ---- conjugate gradients on (A + diag(d)) X = B, the b columns together (pipeline.hpp).  The
+//      operator product goes through op_mul on the whole panel in both paths; everything else of an iteration is either
+//      Backend::block_cg_step (state in backend memory, nothing waits for the host; iterations enqueued past the point
+//      where every column has stopped are no-ops on the device, so X, relres and iters do not depend on the poll interval)
+//      or block_cg_host.hpp.  GSI_CG_POLL: 4 by default.  A poll is one small copy and a drain of the stream: measured at
+//      0.04 ms each (10^6 points, 64 columns, 9.7 ms per iteration: polling every iteration adds 0.3 % to the call, every
+//      4th 0.04 %; profiles/op_solve.json, "poll_sweep"), while an interval of k can run k - 1 operator products after the last
+//      column has stopped.  4 keeps both below a percent of any solve long enough to matter.
+void block_cg_check(const Operator& A, int64_t b, double tol, int64_t maxiter) {
+  Context& c = *A.ctx;
+  if (c.comm) throw Error(GSI_ERR_ARG, "block_cg: ctx has a communicator; the solver runs on one rank");
+  if (A.m != A.n) throw Error(GSI_ERR_ARG, "block_cg: op is " + std::to_string(A.m) + " x " + std::to_string(A.n) + ", not square");
+  if (A.pending_upload != nullptr) throw Error(GSI_ERR_ARG, "block_cg: op has an upload pending");
+  if (b < 1) throw Error(GSI_ERR_ARG, "block_cg: B needs at least one column");
+  if (!(tol > 0.0 && tol < 1.0)) throw Error(GSI_ERR_ARG, "block_cg: tol must lie in (0, 1)");
+  if (maxiter < 1) throw Error(GSI_ERR_ARG, "block_cg: maxiter must be at least 1");
+}
+BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, double* X, int64_t b, double tol, int64_t maxiter,
+                     double* relres, int64_t* iters) {
+  using namespace cgst;
+  block_cg_check(A, b, tol, maxiter);
+  Backend* be = A.ctx->be.get();
+  const int64_t n = A.n;
+  const char* ec = getenv("GSI_CG_COMPOSED");
+  const size_t wd = (ec && atoi(ec) != 0) ? 0 : be->block_cg_work_doubles(b);
+  BlockCgInfo info;
+  info.path = wd ? 1 : 3;
+  Buf R(be, (size_t)n * b), P(be, (size_t)n * b), Q(be, (size_t)n * b);
+  be->copy2d(R.p, n, B, n, n, b);
+  be->copy2d(P.p, n, B, n, n, b);
+  be->fill_zero(X, (size_t)n * b);
+  std::vector<double> st(state_doubles(b), 0.0);
+  if (wd) {
+    int64_t poll = 4;
+    if (const char* e = getenv("GSI_CG_POLL")) poll = std::max<int64_t>(1, atoll(e));
+    Buf work(be, wd);
+    be->fill_zero(work.p, wd);
+    {
+      ScopedPhase ph(be, PH_OTHER);
+      be->block_cg_begin(n, b, B, tol, maxiter, work.p);
+    }
+    double hdr[H_COUNT];
+    be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
+    int64_t enq = 0;
+    while (hdr[H_ACTIVE] > 0.0 && enq < maxiter) {
+      const int64_t burst = std::min<int64_t>(poll, maxiter - enq);
+      for (int64_t k = 0; k < burst; ++k) {
+        op_mul(A, P.p, n, b, Q.p, n);
+        ScopedPhase ph(be, PH_OTHER);
+        be->block_cg_step(n, b, Q.p, diag, X, R.p, P.p, work.p);
+      }
+      enq += burst;
+      be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
+    }
+    info.products = enq;
+    be->download2d(st.data(), (int64_t)st.size(), work.p, (int64_t)st.size(), (int64_t)st.size(), 1);
+  } else {
+    info.products = block_cg_composed(be, [&](const double* p, double* q) { op_mul(A, p, n, b, q, n); }, n, b, diag, B, X, R.p,
+                                      P.p, Q.p, tol, maxiter, st);
+  }
+  info.converged = (int64_t)st[H_CONVERGED];
+  info.breakdown_column = (int64_t)st[H_BREAKDOWN];
+  for (int64_t j = 0; j < b; ++j) {
+    if (relres) relres[j] = cgst::relres(st.data(), j);
+    if (iters) iters[j] = (int64_t)colv(st.data(), ITERS, j);
+  }
+  return info;
 }
 
 int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double epsilon, int64_t r,

@@ -146,6 +146,21 @@ struct LsqrOperator {
 int64_t lsqr(Context& c, const LsqrOperator& A, const double* b, double* x, int64_t maxiter);
 // x = A \ b for a LowRankCovMatrix: lsqr with maxiter = number of samples  (lowrank.jl:141-144); b, x replicated (n)
 int64_t lowrank_solve(const Operator& A, const double* b, double* x);
+// (A + diag(d)) X = B by conjugate gradients, all b columns advanced together (cg_state.hpp): plain
+// CG per column from x0 = 0, the columns sharing only the operator product Q = A P on the whole n x b panel.  A: square,
+// symmetric positive semidefinite, one rank, nothing pending; diag (backend memory, n, may be null): entries >= 0 (checked
+// by the caller); B, X: n x b in backend memory (ld n), B untouched.  relres, iters (HOST, b each, may be null): the
+// recurred |r_j| / |b_j| at exit and the iterations applied to column j.  A column stops at |r_j| <= tol |b_j|; columns
+// still active after maxiter iterations are reported (converged < b), not an error; a breakdown (p'(A + D)p not positive
+// and finite) ends the call: breakdown_column is set, the outputs are filled, and the caller raises GSI_ERR_NOT_POSDEF.
+// Path 1: the backend's fused panel kernels with the state resident in backend memory, polled every GSI_CG_POLL
+// iterations (read per call).  Path 3: block_cg_host.hpp -- when the backend has no such kernels, or GSI_CG_COMPOSED=1
+// (read per call).  Workspace: three n x b panels, the state block and the partial sums.
+struct BlockCgInfo { int64_t products = 0, converged = 0, path = 0, breakdown_column = 0; };
+// what block_cg refuses (GSI_ERR_ARG naming the argument), for callers that allocate before they call it
+void block_cg_check(const Operator& A, int64_t b, double tol, int64_t maxiter);
+BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, double* X, int64_t b, double tol, int64_t maxiter,
+                     double* relres, int64_t* iters);
 // throws Error if a kernel raised an asynchronous flag
 void check_async_errors(Context& c);
 

@@ -1,0 +1,173 @@
+"""Kriging on any covariance operator: `(A + D) X = B` by conjugate gradients with all columns advanced together on the
+device (`gsi_op_solve_cg`, csrc/block_cg.hip), and what geostatistics builds on that solve -- kriging weights with a
+drift, the kriged field on the grid of an `FFTOperatorAt`, and conditional simulation, which turns the unconditional
+samplers of this package (`GridCovSampler.fields`, the FFTRF samplers) into fields that honour data.  Nothing here has a
+counterpart in the reference: its only solver is `lsqr` on a `LowRankCovMatrix`."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from . import randmatfact as RMF
+from . import fftrf as FFTRF
+from .context import DeviceMatrix
+
+PATHS = {1: "fused", 3: "composed"}
+
+
+def _diag_arg(diag, n):
+    if diag is None:
+        return None
+    d = np.asarray(diag, dtype=np.float64)
+    d = np.full(n, float(d)) if d.ndim == 0 else np.ascontiguousarray(d.reshape(-1))
+    if d.shape != (n,):
+        raise ValueError(f"diag must be a scalar or hold one entry per row of the operator, {n}")
+    return d
+
+
+def solve(op, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=False):
+    """`(A + diag) X = B` for a square, symmetric positive semidefinite operator `op` by conjugate gradients, every column
+    of `B` at once (`gsi_op_solve_cg` / `gsi_op_solve`).  `B`: a host vector or matrix, or a `DeviceMatrix`; the result
+    is of the same kind.  `diag`: None, a scalar, or n values >= 0.  A column stops when its recurred residual is below
+    `tol` times the column's norm; `maxiter` defaults to 10 n.  `strict`: a column that has not converged within
+    `maxiter` raises RuntimeError with the counts (otherwise it is only reported).  `return_info`: also a dict with
+    `products`, `converged`, `path` ("fused" / "composed"), `breakdown`, `relres` and `iters` per column.  An operator
+    that is not positive definite along a search direction raises `GsiError` (GSI_ERR_NOT_POSDEF) naming the column."""
+    op, _ = RMF._as_operator(op)
+    ctx, lib = op.ctx, op.ctx.lib
+    n = op.shape[0]
+    d = _diag_arg(diag, n)
+    dp = L.dptr(d) if d is not None else None
+    maxiter = 10 * n if maxiter is None else int(maxiter)
+    info = (C.c_int64 * 4)()
+    if isinstance(B, DeviceMatrix):
+        b = B.shape[1]
+        relres, iters = np.zeros(b), np.zeros(b, dtype=np.int64)
+        X = DeviceMatrix(ctx, B.shape[0], b)
+        status = lib.gsi_op_solve_cg(ctx.h, op.h, dp, B.h, X.h, float(tol), maxiter, info, L.dptr(relres),
+                                     iters.ctypes.data_as(C.POINTER(C.c_int64)))
+        if status != 0:
+            X.close()
+        out = X
+    else:
+        Bf = L.fmat(B, "B")
+        b = Bf.shape[1]
+        if Bf.shape[0] != n:
+            raise ValueError(f"dimension mismatch: operator is {op.shape[0]}x{op.shape[1]}, B has {Bf.shape[0]} rows")
+        relres, iters = np.zeros(b), np.zeros(b, dtype=np.int64)
+        Xh = np.zeros((n, b), order="F")
+        status = lib.gsi_op_solve(ctx.h, op.h, dp, L.dptr(Bf), n, b, L.dptr(Xh), n, float(tol), maxiter, info,
+                                  L.dptr(relres), iters.ctypes.data_as(C.POINTER(C.c_int64)))
+        out = Xh[:, 0] if np.ndim(B) == 1 else Xh
+    L.check(status, lib)
+    rep = {"products": int(info[0]), "converged": int(info[1]), "path": PATHS.get(int(info[2]), int(info[2])),
+           "breakdown": int(info[3]), "relres": relres, "iters": iters, "columns": b}
+    if strict and rep["converged"] < b:
+        if isinstance(out, DeviceMatrix):
+            out.close()
+        raise RuntimeError(f"conjugate gradients: {b - rep['converged']} of {b} columns did not reach tol = {tol:g} within "
+                           f"maxiter = {maxiter} iterations (largest relative residual {np.max(relres):.3e})")
+    return (out, rep) if return_info else out
+
+
+def mat_axpy(alpha, X, Y):
+    """`Y += alpha X` for two `DeviceMatrix` of one shape (`gsi_mat_axpy`); returns Y."""
+    L.check(Y.ctx.lib.gsi_mat_axpy(Y.ctx.h, float(alpha), X.h, Y.h), Y.ctx.lib)
+    return Y
+
+
+def kriging_weights(op, y, noise=None, drift=None, **cg):
+    """The weights of (universal) kriging: with M = A + diag(noise) and the drift matrix G (m x p, e.g. [1, x, y]),
+    `xi, beta` such that  M xi + G beta = y,  G' xi = 0  -- from ONE solve of the 1 + p columns [y, G]:
+    beta = (G' M^-1 G)^-1 G' M^-1 y on the host, xi = M^-1 y - M^-1 G beta.  Without `drift`, xi = M^-1 y and beta is
+    empty.  `cg`: `tol`, `maxiter`, `strict` of `solve`."""
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    m = yv.size
+    if drift is None:
+        return solve(op, yv, diag=noise, **cg), np.zeros(0)
+    G = np.asarray(drift, dtype=np.float64).reshape(m, -1)
+    S = solve(op, np.column_stack([yv, G]), diag=noise, **cg)
+    My, MG = S[:, 0], S[:, 1:]
+    beta = np.linalg.solve(G.T @ MG, G.T @ My)
+    return My - MG @ beta, beta
+
+
+def _grid_product(at_op, G):
+    """C G on the grid of `at_op` for a DeviceMatrix G (n_grid x b): a new DeviceMatrix."""
+    ctx = at_op.ctx
+    H = DeviceMatrix(ctx, *G.shape)
+    try:
+        L.check(ctx.lib.gsi_op_mul_dev(ctx.h, at_op.grid_op.h, 0, G.h, H.h), ctx.lib)
+    except Exception:
+        H.close()
+        raise
+    return H
+
+
+def krige_to_grid(at_op, xi, beta=None, drift_grid=None):
+    """The kriged field on the grid of an `FFTOperatorAt`: C W' xi (+ drift_grid beta), from `FFTRF.spread` and the grid
+    operator's device product.  `xi`: m weights (or m x k); `drift_grid`: n_grid x p, the drift functions at the nodes.
+    Returns a host array of n_grid values (or n_grid x k), vec() order."""
+    ctx = at_op.ctx
+    xv = np.asarray(xi, dtype=np.float64)
+    G = FFTRF.spread(ctx, at_op._P, xv.reshape(xv.shape[0], -1), at_op.Ns, box=at_op._B)
+    try:
+        H = _grid_product(at_op, G)
+        try:
+            out = H.to_host()
+        finally:
+            H.close()
+    finally:
+        G.close()
+    if beta is not None and np.size(beta) > 0:
+        if drift_grid is None:
+            raise ValueError("beta needs drift_grid, the drift functions at the grid nodes")
+        out = out + (np.asarray(drift_grid, dtype=np.float64).reshape(out.shape[0], -1) @ np.asarray(beta, dtype=np.float64)
+                     ).reshape(out.shape[0], -1)
+    return out[:, 0].copy() if xv.ndim == 1 else out
+
+
+def condition_fields(at_op, F, y, noise, eps=None, seed=None, **cg):
+    """Conditional simulation by residual kriging.  `F`: a `DeviceMatrix` of n_grid x b holding zero-mean unconditional
+    fields with the grid operator's covariance C (e.g. `GridCovSampler.fields` of the same kind, ell and sigma2);
+    `y`: the m data at the points of `at_op` = W C W'; `noise`: their error variances D (a scalar or m values).  Returns
+        F + C W' (A + D)^-1 (y 1' + sqrt(D) .* eps - W F)
+    as a new `DeviceMatrix`; `F` is not modified.  `eps`: m x b standard normals, given, or drawn by `RandMatFact.randn`
+    (after `RandMatFact.seed(seed)` if `seed` is given).  Interpolate, solve, spread, grid product, axpy -- all on the
+    device: only the m x b right-hand side crosses the host link, nothing of the grid's size."""
+    ctx = at_op.ctx
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    m, b = yv.size, F.shape[1]
+    if at_op.shape[0] != m:
+        raise ValueError(f"y must hold one value per point of at_op, {at_op.shape[0]}")
+    d = _diag_arg(noise, m)
+    if d is None:
+        d = np.zeros(m)
+    if eps is None:
+        if seed is not None:
+            RMF.seed(seed)
+        eps = RMF.randn(m, b)
+    E = np.asarray(eps, dtype=np.float64).reshape(m, -1)
+    if E.shape != (m, b):
+        raise ValueError(f"eps must be m x b = {m} x {b}")
+    handles = []
+    try:
+        rhs = DeviceMatrix.from_host(ctx, yv[:, None] + np.sqrt(d)[:, None] * E)
+        handles.append(rhs)
+        WF = FFTRF.interpolate(ctx, at_op._P, F, at_op.Ns, box=at_op._B)
+        handles.append(WF)
+        mat_axpy(-1.0, WF, rhs)
+        xi = solve(at_op, rhs, diag=d, **cg)
+        handles.append(xi)
+        G = FFTRF.spread(ctx, at_op._P, xi, at_op.Ns, box=at_op._B)
+        handles.append(G)
+        out = _grid_product(at_op, G)
+        try:
+            mat_axpy(1.0, F, out)
+        except Exception:
+            out.close()
+            raise
+        return out
+    finally:
+        for h in handles:
+            h.close()

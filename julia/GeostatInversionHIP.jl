@@ -575,6 +575,46 @@ function DeviceMatrix(A::Matrix{Float64}; c::Context=ctx())
 	return m
 end
 
+# ---- kriging systems: (A + diag) X = B by conjugate gradients, all columns together (gsi_op_solve_cg; no counterpart in
+#      the reference, whose only solver is lsqr on a LowRankCovMatrix) -----------------------------------------------------
+"`solve(A, B; diag, tol, maxiter)`: `(A + Diagonal(diag)) \\ B` for a square, symmetric positive semidefinite device operator
+by conjugate gradients on the device.  `B`: a `Vector`, a `Matrix` or a `DeviceMatrix`; the result is of the same kind.
+Returns `(X, info)` with `info = (products, converged, path, breakdown, relres, iters)`; an operator that is not positive
+definite along a search direction raises through `check`."
+function solve(A::DeviceOperator, B::Matrix{Float64}; diag::Union{Nothing, Vector{Float64}}=nothing, tol::Float64=1e-10,
+		maxiter::Int=10 * A.n)
+	size(B, 1) == A.n || throw(DimensionMismatch("solve: A is $(A.m)x$(A.n), B has $(size(B, 1)) rows"))
+	b = size(B, 2)
+	X = Matrix{Float64}(undef, A.n, b)
+	info = zeros(Int64, 4)
+	relres = zeros(Float64, b)
+	iters = zeros(Int64, b)
+	check(ccall((:gsi_op_solve, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64},
+			Int64, Float64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+		A.c.h, A.h, diag === nothing ? C_NULL : diag, B, stride(B, 2), b, X, A.n, tol, maxiter, info, relres, iters))
+	return X, (products=info[1], converged=info[2], path=info[3], breakdown=info[4], relres=relres, iters=iters)
+end
+function solve(A::DeviceOperator, b::Vector{Float64}; kw...)
+	X, info = solve(A, reshape(b, :, 1); kw...)
+	return vec(X), info
+end
+function solve(A::DeviceOperator, B::DeviceMatrix; diag::Union{Nothing, Vector{Float64}}=nothing, tol::Float64=1e-10,
+		maxiter::Int=10 * A.n)
+	X = DeviceMatrix(B.rows, B.cols; c=A.c)
+	info = zeros(Int64, 4)
+	relres = zeros(Float64, B.cols)
+	iters = zeros(Int64, B.cols)
+	check(ccall((:gsi_op_solve_cg, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64,
+			Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+		A.c.h, A.h, diag === nothing ? C_NULL : diag, B.h, X.h, tol, maxiter, info, relres, iters))
+	return X, (products=info[1], converged=info[2], path=info[3], breakdown=info[4], relres=relres, iters=iters)
+end
+"`axpy!(alpha, X, Y)` for device matrices of one shape: Y += alpha X."
+function LinearAlgebra.axpy!(alpha::Real, X::DeviceMatrix, Y::DeviceMatrix)
+	check(ccall((:gsi_mat_axpy, libgsi), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}), Y.c.h, Float64(alpha), X.h, Y.h))
+	return Y
+end
+
 "The xi-basis resident in HBM: what `getxis_device` returns and what `pcgadirect` / `pcgalsqr` / `rga` accept in place
 of `xis::Array{Array{Float64,1},1}`.  `precision = 32` stores the K columns in fp32 (all sums in fp64)."
 mutable struct DeviceBasis
