@@ -23,7 +23,8 @@ from .fftrf import lowrank_fftrf_operator, fft_operator_at, FFTOperatorAt
 from . import gridcov as GridCov
 from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, gridcov_structuredgrid
 from . import kriging as Kriging
-from .kriging import solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy
+from .kriging import (solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy, lowrank_preconditioner,
+                      Preconditioner)
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
                    posterior_realizations)
 
@@ -35,4 +36,5 @@ __all__ = [
     "gridcov_sampler", "lowrank_gridcov_operator", "gridcov_structuredgrid", "pcgadirect", "pcgalsqr", "rga", "pcga",
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",
     "Kriging", "solve", "kriging_weights", "krige_to_grid", "condition_fields", "mat_axpy",
+    "lowrank_preconditioner", "Preconditioner",
 ]

@@ -105,6 +105,14 @@ SIGNATURES = {
     "gsi_op_solve": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_i64, c_i64, c_dp, c_i64, C.c_double, c_i64, C.POINTER(c_i64), c_dp,
                                C.POINTER(c_i64)]),
     "gsi_mat_axpy": (C.c_int, [c_vp, C.c_double, c_vp, c_vp]),
+    "gsi_precond_lowrank_create": (C.c_int, [c_vp, C.POINTER(c_vp), c_vp, c_i64, c_dp, C.c_double, c_dp]),
+    "gsi_precond_destroy": (C.c_int, [c_vp]),
+    "gsi_precond_info": (C.c_int, [c_vp, c_dp]),
+    "gsi_precond_apply": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "gsi_op_solve_pcg": (C.c_int, [c_vp, c_vp, c_dp, c_vp, c_vp, c_vp, C.c_double, c_i64, C.POINTER(c_i64), c_dp,
+                                   C.POINTER(c_i64)]),
+    "gsi_op_solve_pcg_host": (C.c_int, [c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, c_i64, c_dp, c_i64, C.c_double, c_i64,
+                                        C.POINTER(c_i64), c_dp, C.POINTER(c_i64)]),
     "gsi_pcgamat_create": (C.c_int, [c_vp, C.POINTER(c_vp), c_dp, c_i64, c_i64, c_dp, c_dp, C.c_int]),
     "gsi_pcgamat_destroy": (C.c_int, [c_vp]),
     "gsi_pcgamat_mul": (C.c_int, [c_vp, c_vp, c_dp, c_dp]),

@@ -175,10 +175,10 @@ class Operator(_Handle):
 
     __matmul__ = matmul
 
-    def solve(self, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=False):
+    def solve(self, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=False, precond=None):
         """`(A + diag) \\ B` by conjugate gradients on the device, all columns together: `kriging.solve`."""
         from .kriging import solve
-        return solve(self, B, diag=diag, tol=tol, maxiter=maxiter, strict=strict, return_info=return_info)
+        return solve(self, B, diag=diag, tol=tol, maxiter=maxiter, strict=strict, return_info=return_info, precond=precond)
 
 
 def dense_operator(ctx, A):

@@ -33,6 +33,10 @@ struct gsi_pcgamat {
   gsi_ctx* ctx;
   PcgaLowRank A;
 };
+struct gsi_precond {
+  gsi_ctx* ctx;
+  LowRankPrecond pc;
+};
 struct gsi_basis {
   gsi_ctx* ctx;
   int64_t n, K;
@@ -1395,6 +1399,113 @@ int gsi_op_solve(gsi_ctx* ctx, const gsi_op* op, const double* diag, const doubl
     // (the solution comes back also when the solve broke down: what the columns had reached)
     try {
       solve_cg_resident(ctx, A, diag, Bd.p, Xd.p, b, tol, maxiter, info, relres, iters);
+    } catch (const Error& e) {
+      if (e.code == GSI_ERR_NOT_POSDEF) be->download2d(X, ldx, Xd.p, A.n, A.n, b);
+      throw;
+    }
+    be->download2d(X, ldx, Xd.p, A.n, A.n, b);
+  });
+}
+
+// ---- the low-rank-plus-diagonal preconditioner and the preconditioned solve ----
+int gsi_precond_lowrank_create(gsi_ctx* ctx, gsi_precond** pc, const gsi_mat* Z, int64_t K, const double* diag, double shift,
+                               double* info_out) {
+  return guarded([&] {
+    REQUIRE(ctx && pc && Z, "gsi_precond_lowrank_create: ctx, pc or Z is NULL");
+    *pc = nullptr;
+    if (info_out) info_out[0] = info_out[1] = info_out[2] = info_out[3] = 0.0;
+    REQUIRE(Z->ctx == ctx, "gsi_precond_lowrank_create: Z belongs to another context");
+    double lo = 0.0, hi = 0.0;
+    precond_lowrank_check(ctx->c, Z->rows, Z->cols, K, diag, shift, &lo, &hi);
+    std::unique_ptr<gsi_precond> h(new gsi_precond());
+    h->ctx = ctx;
+    precond_lowrank_build(h->pc, ctx->c, Z->buf.p, Z->rows, K, diag, shift);
+    if (info_out) { info_out[0] = (double)K; info_out[1] = (double)Z->rows; info_out[2] = lo; info_out[3] = hi; }
+    *pc = h.release();
+  });
+}
+int gsi_precond_destroy(gsi_precond* pc) {
+  return guarded([&] { delete pc; });
+}
+int gsi_precond_info(const gsi_precond* pc, double* info_out) {
+  return guarded([&] {
+    REQUIRE(pc && info_out, "gsi_precond_info: NULL argument");
+    info_out[0] = (double)pc->pc.K; info_out[1] = (double)pc->pc.n; info_out[2] = pc->pc.dmin; info_out[3] = pc->pc.dmax;
+  });
+}
+int gsi_precond_apply(gsi_ctx* ctx, const gsi_precond* pc, const gsi_mat* R, gsi_mat* Zout) {
+  return guarded([&] {
+    REQUIRE(ctx && pc && R && Zout, "gsi_precond_apply: NULL argument");
+    REQUIRE(pc->ctx == ctx, "gsi_precond_apply: pc belongs to another context");
+    REQUIRE(R->ctx == ctx && Zout->ctx == ctx, "gsi_precond_apply: R or Zout belongs to another context");
+    REQUIRE(R->rows == pc->pc.n && R->cols >= 1, "gsi_precond_apply: R must have the preconditioner's rows");
+    REQUIRE(Zout->rows == R->rows && Zout->cols == R->cols, "gsi_precond_apply: Zout must have the shape of R");
+    REQUIRE(Zout != R && Zout->buf.p != R->buf.p, "gsi_precond_apply: Zout must not be R");
+    precond_apply(pc->pc, R->buf.p, R->cols, Zout->buf.p);
+    check_async_errors(ctx->c);
+  });
+}
+
+namespace {
+void solve_pcg_resident(gsi_ctx* ctx, const Operator& A, const double* diag, const LowRankPrecond& pc, const double* Bd,
+                        double* Xd, int64_t b, double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  Backend* be = ctx->c.be.get();
+  Buf dd;
+  if (diag) {
+    dd = Buf(be, (size_t)A.n);
+    be->upload2d(dd.p, A.n, diag, A.n, A.n, 1);
+  }
+  const BlockPcgInfo r = block_pcg(A, diag ? dd.p : nullptr, pc, Bd, Xd, b, tol, maxiter, relres, iters);
+  if (info) {
+    info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column; info[4] = r.breakdown_kind;
+    info[5] = r.K;
+  }
+  check_async_errors(ctx->c);
+  if (r.breakdown_column != 0)
+    throw Error(GSI_ERR_NOT_POSDEF, std::string("preconditioned conjugate gradients: ") +
+                                        (r.breakdown_kind == 2 ? "r'z is not positive and finite (the preconditioner is not positive definite)"
+                                                               : "A + diag is not positive definite along the search direction") +
+                                        " of column " + std::to_string(r.breakdown_column));
+}
+void check_pcg_args(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, int64_t b, double tol,
+                    int64_t maxiter, int64_t* info) {
+  if (info) info[4] = info[5] = 0;
+  check_solve_args(ctx, op, diag, b, tol, maxiter, info);
+  REQUIRE(pc, "gsi_op_solve_pcg: pc is NULL");
+  REQUIRE(pc->ctx == ctx, "gsi_op_solve_pcg: pc belongs to another context");
+  block_pcg_check(op->op, pc->pc, b, tol, maxiter);
+}
+}  // namespace
+
+int gsi_op_solve_pcg(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, const gsi_mat* B, gsi_mat* X,
+                     double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  return guarded([&] {
+    REQUIRE(B && X, "gsi_op_solve_pcg: B or X is NULL");
+    check_pcg_args(ctx, op, diag, pc, B->cols, tol, maxiter, info);
+    const Operator& A = op->op;
+    REQUIRE(B->ctx == ctx && X->ctx == ctx, "gsi_op_solve_pcg: B or X belongs to another context");
+    REQUIRE(B->rows == A.n, "gsi_op_solve_pcg: B must have size(A, 1) rows");
+    REQUIRE(X->rows == A.n && X->cols == B->cols, "gsi_op_solve_pcg: X must have the shape of B");
+    REQUIRE(X != B && X->buf.p != B->buf.p, "gsi_op_solve_pcg: X must not be B");
+    solve_pcg_resident(ctx, A, diag, pc->pc, B->buf.p, X->buf.p, B->cols, tol, maxiter, info, relres, iters);
+  });
+}
+
+int gsi_op_solve_pcg_host(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, const double* B,
+                          int64_t ldb, int64_t b, double* X, int64_t ldx, double tol, int64_t maxiter, int64_t* info,
+                          double* relres, int64_t* iters) {
+  return guarded([&] {
+    REQUIRE(B && X, "gsi_op_solve_pcg_host: B or X is NULL");
+    check_pcg_args(ctx, op, diag, pc, b, tol, maxiter, info);
+    const Operator& A = op->op;
+    REQUIRE(ldb >= A.n, "gsi_op_solve_pcg_host: ldb is smaller than size(A, 1), the rows of B");
+    REQUIRE(ldx >= A.n, "gsi_op_solve_pcg_host: ldx is smaller than size(A, 1), the rows of X");
+    REQUIRE(X != B, "gsi_op_solve_pcg_host: X must not be B");
+    Backend* be = ctx->c.be.get();
+    Buf Bd(be, (size_t)A.n * b), Xd(be, (size_t)A.n * b);
+    be->upload2d(Bd.p, A.n, B, ldb, A.n, b);
+    try {                                                       // (as gsi_op_solve: the columns come back after a breakdown too)
+      solve_pcg_resident(ctx, A, diag, pc->pc, Bd.p, Xd.p, b, tol, maxiter, info, relres, iters);
     } catch (const Error& e) {
       if (e.code == GSI_ERR_NOT_POSDEF) be->download2d(X, ldx, Xd.p, A.n, A.n, b);
       throw;

@@ -447,6 +447,28 @@ class Backend {
     throw Error(1 /* GSI_ERR_ARG */, "block_cg: not available on this backend");
   }
 
+  // ---- the same solver preconditioned by P = Z Z' + diag(d + shift): P^-1 = diag(e) - W W' with
+  //      e (n) and W (n x K, ld n) in backend memory.  `work` holds block_pcg_work_doubles(b) doubles = [state | three sets
+  //      of partial sums]; S (K x b, ld K) and Y (n x b, ld n) are the caller's.  0 = "not mine" (the default):
+  //      pipeline.cpp runs block_pcg_host.hpp.
+  virtual size_t block_pcg_work_doubles(int64_t b) { (void)b; return 0; }
+  // R holds B, X is zero: P <- z0 = P^-1 B, the columns' b'b and b'z0, the state of a fresh solve
+  virtual void block_pcg_begin(int64_t n, int64_t b, int64_t K, const double* B, const double* e, const double* W, double* S,
+                               double* Y, double* P, double tol, int64_t maxiter, double* work) {
+    (void)n; (void)b; (void)K; (void)B; (void)e; (void)W; (void)S; (void)Y; (void)P; (void)tol; (void)maxiter; (void)work;
+    throw Error(1 /* GSI_ERR_ARG */, "block_pcg: not available on this backend");
+  }
+  // after Q = A P: alpha; x += alpha p, r -= alpha (q + d .* p); the stopping rule; z = e .* r - W (W'r); beta; p = z + beta p
+  virtual void block_pcg_step(int64_t n, int64_t b, int64_t K, const double* Q, const double* d, const double* e,
+                              const double* W, double* X, double* R, double* P, double* S, double* Y, double* work) {
+    (void)n; (void)b; (void)K; (void)Q; (void)d; (void)e; (void)W; (void)X; (void)R; (void)P; (void)S; (void)Y; (void)work;
+    throw Error(1 /* GSI_ERR_ARG */, "block_pcg: not available on this backend");
+  }
+  // the preconditioner's setup: e (n, holding d + shift) <- 1 / e and sqe (n) <- sqrt of that; C (K x K, ld K) += I.
+  // 1, or 0: "not mine" (the caller does both on the host).
+  virtual int precond_rows(int64_t n, double* e, double* sqe) { (void)n; (void)e; (void)sqe; return 0; }
+  virtual int add_identity(double* C, int64_t K) { (void)C; (void)K; return 0; }
+
   // ---- fp32-STORED xi-basis (BASELINE configs[4], "fp32 mixed precision"): the n x K basis is the one big HBM stream
   //      of the PCGA iteration's own algebra; stored in fp32 it is half the bytes, every sum stays in fp64 ----
   virtual void f64_to_f32(const double* src, void* dst32, size_t count) = 0;

@@ -26,7 +26,7 @@ namespace gsi { namespace hipk {
 
 namespace {
 using namespace gsi::cgst;
-constexpr int CG_PARTS = 128;       // row parts = partial sums per column and reduction
+constexpr int CG_PARTS = BLOCK_CG_PARTS;   // row parts = partial sums per column and reduction (128)
 constexpr int CG_BS = 256;
 constexpr int CG_COLS_Y = 16;       // gridDim.y: 128 x 16 = 2048 workgroups at most
 
@@ -230,6 +230,29 @@ void block_cg_begin(hipStream_t st, int64_t n, int64_t b, const double* B, doubl
   hipLaunchKernelGGL(cg_begin_kernel, dim3(1), dim3(CG_BS), 0, st, work, part, tol, maxiter, b);
 }
 
+// passes 1 and 2 on their own: block_pcg.hip runs them in front of its preconditioner passes
+bool block_cg_vec(int64_t n, const void* a, const void* b2, const void* c, const void* d, const void* e) {
+  return cg_vec(n, a, b2, c, d, e);
+}
+#define CG_LAUNCH2(K, ...)                                                                                     \
+  do {                                                                                                         \
+    if (vec && d) hipLaunchKernelGGL((K<true, true>), g, bs, 0, st, __VA_ARGS__);                              \
+    else if (vec) hipLaunchKernelGGL((K<true, false>), g, bs, 0, st, __VA_ARGS__);                             \
+    else if (d) hipLaunchKernelGGL((K<false, true>), g, bs, 0, st, __VA_ARGS__);                               \
+    else hipLaunchKernelGGL((K<false, false>), g, bs, 0, st, __VA_ARGS__);                                     \
+  } while (0)
+void block_cg_pass_pq(hipStream_t st, bool vec, int64_t n, int64_t b, const double* P, const double* Q, const double* d,
+                      const double* s, double* part) {
+  const dim3 g = cg_grid(b), bs(CG_BS);
+  CG_LAUNCH2(cg_pq_kernel, n, b, P, Q, d, s, part);
+}
+void block_cg_pass_xr(hipStream_t st, bool vec, int64_t n, int64_t b, const double* P, const double* Q, const double* d,
+                      double* X, double* R, const double* s, double* part) {
+  const dim3 g = cg_grid(b), bs(CG_BS);
+  CG_LAUNCH2(cg_xr_kernel, n, b, P, Q, d, X, R, s, part);
+}
+#undef CG_LAUNCH2
+
 // everything of one iteration behind the operator product Q = A P
 void block_cg_step(hipStream_t st, int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
                    double* work) {
@@ -238,18 +261,10 @@ void block_cg_step(hipStream_t st, int64_t n, int64_t b, const double* Q, const 
   double* prr = ppq + (size_t)b * CG_PARTS;
   const bool vec = cg_vec(n, Q, d, X, R, P);
   const dim3 g = cg_grid(b), bs(CG_BS);
-#define CG_LAUNCH2(K, ...)                                                                                     \
-  do {                                                                                                         \
-    if (vec && d) hipLaunchKernelGGL((K<true, true>), g, bs, 0, st, __VA_ARGS__);                              \
-    else if (vec) hipLaunchKernelGGL((K<true, false>), g, bs, 0, st, __VA_ARGS__);                             \
-    else if (d) hipLaunchKernelGGL((K<false, true>), g, bs, 0, st, __VA_ARGS__);                               \
-    else hipLaunchKernelGGL((K<false, false>), g, bs, 0, st, __VA_ARGS__);                                     \
-  } while (0)
-  CG_LAUNCH2(cg_pq_kernel, n, b, (const double*)P, Q, d, (const double*)s, ppq);
+  block_cg_pass_pq(st, vec, n, b, P, Q, d, s, ppq);
   hipLaunchKernelGGL(cg_after_pq_kernel, dim3(1), bs, 0, st, s, (const double*)ppq);
-  CG_LAUNCH2(cg_xr_kernel, n, b, (const double*)P, Q, d, X, R, (const double*)s, prr);
+  block_cg_pass_xr(st, vec, n, b, P, Q, d, X, R, s, prr);
   hipLaunchKernelGGL(cg_after_rr_kernel, dim3(1), bs, 0, st, s, (const double*)prr);
-#undef CG_LAUNCH2
   if (vec) hipLaunchKernelGGL(cg_p_kernel<true>, g, bs, 0, st, n, b, (const double*)R, P, (const double*)s);
   else hipLaunchKernelGGL(cg_p_kernel<false>, g, bs, 0, st, n, b, (const double*)R, P, (const double*)s);
 }

@@ -135,4 +135,69 @@ GSI_HD inline double relres(const double* s, int64_t j) {
   return bn > 0.0 ? std::sqrt(colv(s, RHO, j)) / bn : (bn == 0.0 ? 0.0 : bn);
 }
 
+// ---- the preconditioned recurrences: P = Z Z' + diag(d + shift), z = P^-1 r.  The same header and
+//      per-column fields, with RHO holding r'z (so that after_pq above gives alpha = r'z / p'w unchanged) and three fields
+//      more behind NFIELDS.  One iteration, per column j:
+//        q = A p;  w = q + d .* p;  pcg_after_pq(p'w);   x += alpha p;  r -= alpha w;   pcg_after_rr(r'r);
+//        z = P^-1 r;   pcg_after_rz(r'z);   p = z + beta p
+//      then after_iter once for the batch.  The stopping rule is the plain one, on the recurred |r|.
+enum {
+  RR = NFIELDS,   // r'r (RHO holds r'z)
+  BKIND,          // 0, or what broke down: 1 = p'(A + D)p, 2 = r'z was not positive and finite
+  PCG_NFIELDS
+};
+GSI_HD inline size_t pcg_state_doubles(int64_t b) { return (size_t)H_COUNT + (size_t)PCG_NFIELDS * (size_t)b; }
+
+// x = 0, r = b_j, z = p = P^-1 b_j:  bb = b_j'b_j, bz = b_j'z.  A zero column stops here, as in begin_col.
+GSI_HD inline void pcg_begin_col(double* s, int64_t j, double bb, double bz) {
+  begin_col(s, j, bb);
+  col(s, RR, j) = bb;
+  col(s, BKIND, j) = 0.0;
+  if (colv(s, STOPPED, j) != 0.0) return;
+  col(s, RHO, j) = bz;
+  if (!(bz > 0.0) || !(bz <= 1.79769313486231570815e308)) {      // P^-1 is not positive definite on b (a NaN in Z's factor)
+    col(s, BREAKDOWN, j) = 1.0;
+    col(s, BKIND, j) = 2.0;
+    col(s, STOPPED, j) = 1.0;
+  }
+}
+GSI_HD inline void pcg_after_pq(double* s, int64_t j, double pq) {
+  after_pq(s, j, pq);
+  if (colv(s, BREAKDOWN, j) != 0.0 && colv(s, BKIND, j) == 0.0) col(s, BKIND, j) = 1.0;
+}
+// after x += alpha p, r -= alpha w:  rr = r'r.  UPDP here means "z and r'z are wanted"; pcg_after_rz has the last word.
+GSI_HD inline void pcg_after_rr(double* s, int64_t j, double rr) {
+  if (colv(s, APPLY, j) == 0.0) return;
+  col(s, ITERS, j) += 1.0;
+  col(s, RR, j) = rr;
+  if (std::sqrt(rr) <= s[H_TOL] * colv(s, BNORM, j)) {           // converged: p stays as it is
+    col(s, STOPPED, j) = 1.0;
+    return;
+  }
+  if (!(rr <= 1.79769313486231570815e308)) {                     // the residual left the floating-point range
+    col(s, BREAKDOWN, j) = 1.0;
+    col(s, BKIND, j) = 1.0;
+    col(s, STOPPED, j) = 1.0;
+    return;
+  }
+  col(s, UPDP, j) = 1.0;
+}
+// after z = P^-1 r:  rz = r'z
+GSI_HD inline void pcg_after_rz(double* s, int64_t j, double rz) {
+  if (colv(s, UPDP, j) == 0.0) return;
+  if (!(rz > 0.0) || !(rz <= 1.79769313486231570815e308)) {
+    col(s, BREAKDOWN, j) = 1.0;
+    col(s, BKIND, j) = 2.0;
+    col(s, STOPPED, j) = 1.0;
+    col(s, UPDP, j) = 0.0;
+    return;
+  }
+  col(s, BETA, j) = rz / colv(s, RHO, j);                        // RHO > 0: the column was active
+  col(s, RHO, j) = rz;
+}
+GSI_HD inline double pcg_relres(const double* s, int64_t j) {
+  const double bn = colv(s, BNORM, j);
+  return bn > 0.0 ? std::sqrt(colv(s, RR, j)) / bn : (bn == 0.0 ? 0.0 : bn);
+}
+
 }}  // namespace gsi::cgst

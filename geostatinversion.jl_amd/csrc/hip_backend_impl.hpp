@@ -248,6 +248,13 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   void lsqr_step_u(int64_t m, const double* t, double* u, double* work) override;
   void lsqr_step_v(int64_t n, const double* t, double* v, double* w, double* x, double* work) override;
   size_t block_cg_work_doubles(int64_t b) override { return hipk::block_cg_work_doubles(b); }
+  size_t block_pcg_work_doubles(int64_t b) override { return hipk::block_pcg_work_doubles(b); }
+  void block_pcg_begin(int64_t n, int64_t b, int64_t K, const double* B, const double* e, const double* W, double* S, double* Y,
+                       double* P, double tol, int64_t maxiter, double* work) override;
+  void block_pcg_step(int64_t n, int64_t b, int64_t K, const double* Q, const double* d, const double* e, const double* W,
+                      double* X, double* R, double* P, double* S, double* Y, double* work) override;
+  int precond_rows(int64_t n, double* e, double* sqe) override;
+  int add_identity(double* C, int64_t K) override;
   void block_cg_begin(int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work) override;
   void block_cg_step(int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
                      double* work) override;

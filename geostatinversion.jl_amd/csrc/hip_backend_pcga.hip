@@ -85,6 +85,38 @@ void HipBackend::block_cg_step(int64_t n, int64_t b, const double* Q, const doub
   hipk::block_cg_step(st_, n, b, Q, d, X, R, P, work);
   check_launch("block_cg_step");
 }
+// The preconditioned solver (block_pcg.hip): z = e .* r - W (W'r) is the two contraction launchers
+// on all b columns between the panel passes.
+void HipBackend::block_pcg_begin(int64_t n, int64_t b, int64_t K, const double* B, const double* e, const double* W, double* S,
+                                 double* Y, double* P, double tol, int64_t maxiter, double* work) {
+  bind();
+  gemm_tn(K, b, n, 1.0, W, n, B, n, 0.0, S, K);
+  gemm_nn(n, b, K, 1.0, W, n, S, K, 0.0, Y, n);
+  hipk::block_pcg_begin(st_, n, b, B, e, Y, P, tol, maxiter, work);
+  check_launch("block_pcg_begin");
+}
+void HipBackend::block_pcg_step(int64_t n, int64_t b, int64_t K, const double* Q, const double* d, const double* e,
+                                const double* W, double* X, double* R, double* P, double* S, double* Y, double* work) {
+  bind();
+  hipk::block_pcg_step_xr(st_, n, b, Q, d, X, R, P, work);
+  check_launch("block_pcg_step: passes 1 and 2");
+  gemm_tn(K, b, n, 1.0, W, n, R, n, 0.0, S, K);
+  gemm_nn(n, b, K, 1.0, W, n, S, K, 0.0, Y, n);
+  hipk::block_pcg_step_p(st_, n, b, e, R, Y, P, work);
+  check_launch("block_pcg_step: pass 3");
+}
+int HipBackend::precond_rows(int64_t n, double* e, double* sqe) {
+  bind();
+  hipk::pcg_precond_rows(st_, n, e, sqe);
+  check_launch("precond_rows");
+  return 1;
+}
+int HipBackend::add_identity(double* C, int64_t K) {
+  bind();
+  hipk::pcg_add_identity(st_, C, K);
+  check_launch("add_identity");
+  return 1;
+}
 void HipBackend::f64_to_f32(const double* src, void* dst32, size_t count) {
   bind();
   hipk::f64_to_f32(st_, src, (float*)dst32, count);

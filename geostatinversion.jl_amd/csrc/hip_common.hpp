@@ -232,10 +232,31 @@ void lsqr_step_u(hipStream_t st, int64_t m, const double* t, double* u, double* 
 void lsqr_step_v(hipStream_t st, int64_t n, const double* t, double* v, double* w, double* x, double* work);
 
 // ---- block_cg.hip: the multi-column conjugate-gradient solver's panel passes with device-resident scalars (cg_state.hpp) ----
+constexpr int BLOCK_CG_PARTS = 128;    // row parts of the fixed grid = partial sums per column and reduction
 size_t block_cg_work_doubles(int64_t b);
 void block_cg_begin(hipStream_t st, int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work);
 void block_cg_step(hipStream_t st, int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
                    double* work);
+// passes 1 and 2 of block_cg_step alone (s: the state block, part: b x BLOCK_CG_PARTS sums), for block_pcg.hip; vec: the
+// 16-byte form, allowed where block_cg_vec says so of every panel the pass touches
+bool block_cg_vec(int64_t n, const void* a, const void* b2, const void* c, const void* d, const void* e);
+void block_cg_pass_pq(hipStream_t st, bool vec, int64_t n, int64_t b, const double* P, const double* Q, const double* d,
+                      const double* s, double* part);
+void block_cg_pass_xr(hipStream_t st, bool vec, int64_t n, int64_t b, const double* P, const double* Q, const double* d,
+                      double* X, double* R, const double* s, double* part);
+
+// ---- block_pcg.hip: the same solver preconditioned by a low-rank-plus-diagonal P ----
+size_t block_pcg_work_doubles(int64_t b);
+// Y = W (W'B) has been formed by the caller: P <- z0 = e .* B - Y, the sums b'b and b'z0, the state of a fresh solve
+void block_pcg_begin(hipStream_t st, int64_t n, int64_t b, const double* B, const double* e, const double* Y, double* P,
+                     double tol, int64_t maxiter, double* work);
+// passes 1 and 2 and their scalar kernels; then, once the caller has formed Y = W (W'R): passes 3a and 3b and theirs
+void block_pcg_step_xr(hipStream_t st, int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R,
+                       const double* P, double* work);
+void block_pcg_step_p(hipStream_t st, int64_t n, int64_t b, const double* e, const double* R, const double* Y, double* P,
+                      double* work);
+void pcg_precond_rows(hipStream_t st, int64_t n, double* e, double* sqe);
+void pcg_add_identity(hipStream_t st, double* C, int64_t K);
 
 // ---- panel_qr.hip ----
 constexpr int QR_NB = 16;

@@ -13,6 +13,7 @@
 #include "pipeline.hpp"
 #include "lsqr_state.hpp"
 #include "block_cg_host.hpp"
+#include "block_pcg_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1238,6 +1239,147 @@ BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, dou
   info.breakdown_column = (int64_t)st[H_BREAKDOWN];
   for (int64_t j = 0; j < b; ++j) {
     if (relres) relres[j] = cgst::relres(st.data(), j);
+    if (iters) iters[j] = (int64_t)colv(st.data(), ITERS, j);
+  }
+  return info;
+}
+
+// ---- the preconditioner P = Z Z' + diag(d + shift) and the preconditioned solve (pipeline.hpp).
+//      The setup is composed from what exists -- scale_rows, gemm_tn, chol_upper, trsm_right_upper -- around the backend's
+//      precond_rows / add_identity; a backend that declines those (the CPU reference backend) gets the row scalings and the
+//      identity from the host.
+void precond_lowrank_check(Context& c, int64_t n, int64_t zcols, int64_t K, const double* diag, double shift, double* dmin,
+                           double* dmax) {
+  if (c.comm) throw Error(GSI_ERR_ARG, "precond_lowrank: ctx has a communicator; the preconditioner lives on one rank");
+  if (n < 1) throw Error(GSI_ERR_ARG, "precond_lowrank: Z has no rows");
+  if (K < 1) throw Error(GSI_ERR_ARG, "precond_lowrank: K must be at least 1");
+  if (K > zcols) throw Error(GSI_ERR_ARG, "precond_lowrank: K exceeds the columns of Z, " + std::to_string(zcols));
+  if (K > n) throw Error(GSI_ERR_ARG, "precond_lowrank: K exceeds the rows of Z, " + std::to_string(n));
+  if (K > 2048) throw Error(GSI_ERR_ARG, "precond_lowrank: K exceeds 2048, the limit of the small Cholesky");
+  if (!(shift >= 0.0 && shift <= 1.79769313486231570815e308))
+    throw Error(GSI_ERR_ARG, "precond_lowrank: shift is negative or not finite");
+  double lo = 1.79769313486231570815e308, hi = 0.0;
+  for (int64_t i = 0; i < n; ++i) {
+    const double v = (diag ? diag[i] : 0.0) + shift;
+    if (!(v > 0.0 && v <= 1.79769313486231570815e308))
+      throw Error(GSI_ERR_ARG, diag ? "precond_lowrank: diag[" + std::to_string(i) + "] + shift is not positive and finite"
+                                    : std::string("precond_lowrank: without diag, shift must be positive (diag + shift is not positive)"));
+    lo = std::min(lo, v);
+    hi = std::max(hi, v);
+  }
+  if (dmin) *dmin = lo;
+  if (dmax) *dmax = hi;
+}
+
+void precond_lowrank_build(LowRankPrecond& pc, Context& c, const double* Z, int64_t n, int64_t K, const double* diag,
+                           double shift) {
+  precond_lowrank_check(c, n, K, K, diag, shift, &pc.dmin, &pc.dmax);
+  Backend* be = c.be.get();
+  pc.ctx = &c; pc.n = n; pc.K = K;
+  std::vector<double> eh((size_t)n), sh((size_t)n);
+  for (int64_t i = 0; i < n; ++i) eh[(size_t)i] = (diag ? diag[i] : 0.0) + shift;
+  pc.e = Buf(be, (size_t)n);
+  Buf sqe(be, (size_t)n), C(be, (size_t)K * K);
+  be->upload2d(pc.e.p, n, eh.data(), n, n, 1);
+  if (!be->precond_rows(n, pc.e.p, sqe.p)) {
+    for (int64_t i = 0; i < n; ++i) { eh[(size_t)i] = 1.0 / eh[(size_t)i]; sh[(size_t)i] = std::sqrt(eh[(size_t)i]); }
+    be->upload2d(pc.e.p, n, eh.data(), n, n, 1);
+    be->upload2d(sqe.p, n, sh.data(), n, n, 1);
+  }
+  std::vector<double> zh;                                       // Z on the host, where the backend does not scale rows
+  {
+    Buf T(be, (size_t)n * K);                                   // T = diag(sqrt(e)) Z;  C = I + T'T
+    if (!be->scale_rows(n, K, sqe.p, Z, n, T.p, n)) {
+      be->download2d(sh.data(), n, sqe.p, n, n, 1);
+      be->download2d(eh.data(), n, pc.e.p, n, n, 1);
+      zh.resize((size_t)n * K);
+      be->download2d(zh.data(), n, Z, n, n, K);
+      std::vector<double> th((size_t)n * K);
+      for (int64_t k = 0; k < K; ++k)
+        for (int64_t i = 0; i < n; ++i) th[(size_t)(i + k * n)] = sh[(size_t)i] * zh[(size_t)(i + k * n)];
+      be->upload2d(T.p, n, th.data(), n, n, K);
+    }
+    be->gemm_tn(K, K, n, 1.0, T.p, n, T.p, n, 0.0, C.p, K);
+  }
+  if (!be->add_identity(C.p, K)) {
+    std::vector<double> ch((size_t)K * K);
+    be->download2d(ch.data(), K, C.p, K, K, K);
+    for (int64_t k = 0; k < K; ++k) ch[(size_t)(k + k * K)] += 1.0;
+    be->upload2d(C.p, K, ch.data(), K, K, K);
+  }
+  be->chol_upper(C.p, K);
+  pc.W = Buf(be, (size_t)n * K);                                // W = diag(e) Z R^-1
+  if (zh.empty()) {
+    be->scale_rows(n, K, pc.e.p, Z, n, pc.W.p, n);
+  } else {
+    for (int64_t k = 0; k < K; ++k)
+      for (int64_t i = 0; i < n; ++i) zh[(size_t)(i + k * n)] *= eh[(size_t)i];
+    be->upload2d(pc.W.p, n, zh.data(), n, n, K);
+  }
+  be->trsm_right_upper(pc.W.p, n, K, n, C.p);
+  check_async_errors(c);                                        // the Cholesky's flag: GSI_ERR_NOT_POSDEF
+}
+
+void precond_apply(const LowRankPrecond& pc, const double* R, int64_t b, double* Zout) {
+  Backend* be = pc.ctx->be.get();
+  Buf S(be, (size_t)pc.K * b);
+  precond_apply_composed(be, pc.n, pc.K, pc.e.p, pc.W.p, R, b, S.p, Zout);
+}
+
+void block_pcg_check(const Operator& A, const LowRankPrecond& pc, int64_t b, double tol, int64_t maxiter) {
+  block_cg_check(A, b, tol, maxiter);
+  if (pc.ctx != A.ctx) throw Error(GSI_ERR_ARG, "block_pcg: pc belongs to another context");
+  if (pc.n != A.n) throw Error(GSI_ERR_ARG, "block_pcg: pc was built for " + std::to_string(pc.n) + " rows, op has " +
+                                                std::to_string(A.n));
+}
+BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPrecond& pc, const double* B, double* X, int64_t b,
+                       double tol, int64_t maxiter, double* relres, int64_t* iters) {
+  using namespace cgst;
+  block_pcg_check(A, pc, b, tol, maxiter);
+  Backend* be = A.ctx->be.get();
+  const int64_t n = A.n, K = pc.K;
+  const char* ec = getenv("GSI_CG_COMPOSED");
+  const size_t wd = (ec && atoi(ec) != 0) ? 0 : be->block_pcg_work_doubles(b);
+  BlockPcgInfo info;
+  info.path = wd ? 1 : 3;
+  info.K = K;
+  Buf R(be, (size_t)n * b), P(be, (size_t)n * b), Q(be, (size_t)n * b), Y(be, (size_t)n * b), S(be, (size_t)K * b);
+  be->copy2d(R.p, n, B, n, n, b);
+  be->fill_zero(X, (size_t)n * b);
+  std::vector<double> st(pcg_state_doubles(b), 0.0);
+  if (wd) {
+    int64_t poll = 4;
+    if (const char* e = getenv("GSI_CG_POLL")) poll = std::max<int64_t>(1, atoll(e));
+    Buf work(be, wd);
+    be->fill_zero(work.p, wd);
+    {
+      ScopedPhase ph(be, PH_OTHER);
+      be->block_pcg_begin(n, b, K, B, pc.e.p, pc.W.p, S.p, Y.p, P.p, tol, maxiter, work.p);
+    }
+    double hdr[H_COUNT];
+    be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
+    int64_t enq = 0;
+    while (hdr[H_ACTIVE] > 0.0 && enq < maxiter) {
+      const int64_t burst = std::min<int64_t>(poll, maxiter - enq);
+      for (int64_t k = 0; k < burst; ++k) {
+        op_mul(A, P.p, n, b, Q.p, n);
+        ScopedPhase ph(be, PH_OTHER);
+        be->block_pcg_step(n, b, K, Q.p, diag, pc.e.p, pc.W.p, X, R.p, P.p, S.p, Y.p, work.p);
+      }
+      enq += burst;
+      be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
+    }
+    info.products = enq;
+    be->download2d(st.data(), (int64_t)st.size(), work.p, (int64_t)st.size(), (int64_t)st.size(), 1);
+  } else {
+    info.products = block_pcg_composed(be, [&](const double* p, double* q) { op_mul(A, p, n, b, q, n); }, n, b, K, diag,
+                                       pc.e.p, pc.W.p, B, X, R.p, P.p, Q.p, Y.p, S.p, tol, maxiter, st);
+  }
+  info.converged = (int64_t)st[H_CONVERGED];
+  info.breakdown_column = (int64_t)st[H_BREAKDOWN];
+  if (info.breakdown_column != 0) info.breakdown_kind = (int64_t)colv(st.data(), BKIND, info.breakdown_column - 1);
+  for (int64_t j = 0; j < b; ++j) {
+    if (relres) relres[j] = pcg_relres(st.data(), j);
     if (iters) iters[j] = (int64_t)colv(st.data(), ITERS, j);
   }
   return info;

@@ -161,6 +161,28 @@ struct BlockCgInfo { int64_t products = 0, converged = 0, path = 0, breakdown_co
 void block_cg_check(const Operator& A, int64_t b, double tol, int64_t maxiter);
 BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, double* X, int64_t b, double tol, int64_t maxiter,
                      double* relres, int64_t* iters);
+// ---- the same solve preconditioned by P = Z Z' + diag(d + shift).  P^-1 = diag(e) - W W' exactly,
+//      with e = 1 / (d + shift), R'R = I + Z' diag(e) Z and W = diag(e) Z R^-1: the handle keeps e (n) and W (n x K) only.
+struct LowRankPrecond {
+  Context* ctx = nullptr;
+  int64_t n = 0, K = 0;
+  double dmin = 0.0, dmax = 0.0;       // min and max of d + shift
+  Buf e, W;
+};
+// what precond_lowrank_build refuses (GSI_ERR_ARG naming the argument), before anything is allocated; dmin / dmax filled
+void precond_lowrank_check(Context& c, int64_t n, int64_t zcols, int64_t K, const double* diag, double shift, double* dmin,
+                           double* dmax);
+// Z: n x (>= K) in backend memory, ld n, not modified; diag: n HOST values or null.  A Cholesky that fails (a NaN in Z):
+// GSI_ERR_NOT_POSDEF.
+void precond_lowrank_build(LowRankPrecond& pc, Context& c, const double* Z, int64_t n, int64_t K, const double* diag,
+                           double shift);
+// Zout (n x b) = P^-1 R (n x b), both in backend memory, ld n
+void precond_apply(const LowRankPrecond& pc, const double* R, int64_t b, double* Zout);
+// breakdown_kind: 1 = p'(A + D)p, 2 = r'z was not positive and finite.  Paths and GSI_CG_POLL / GSI_CG_COMPOSED as block_cg.
+struct BlockPcgInfo { int64_t products = 0, converged = 0, path = 0, breakdown_column = 0, breakdown_kind = 0, K = 0; };
+void block_pcg_check(const Operator& A, const LowRankPrecond& pc, int64_t b, double tol, int64_t maxiter);
+BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPrecond& pc, const double* B, double* X, int64_t b,
+                       double tol, int64_t maxiter, double* relres, int64_t* iters);
 // throws Error if a kernel raised an asynchronous flag
 void check_async_errors(Context& c);
 

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib as L
 from . import randmatfact as RMF
 from . import fftrf as FFTRF
-from .context import DeviceMatrix
+from .context import DeviceMatrix, _Handle
 
 PATHS = {1: "fused", 3: "composed"}
 
@@ -25,27 +25,115 @@ def _diag_arg(diag, n):
     return d
 
 
-def solve(op, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=False):
+class Preconditioner(_Handle):
+    """P = Z Z' + diag(d + shift) for the solves of this module (`gsi_precond`): e = 1 / (d + shift)
+    and W with P^-1 = diag(e) - W W' resident on the device.  Made by `lowrank_preconditioner`; pass it as `precond=` to
+    `solve`, `Operator.solve`, `kriging_weights`, `condition_fields`.  `close()` (or a `with` block) frees it."""
+
+    _destroy = "gsi_precond_destroy"
+
+    def __init__(self, ctx, h, info):
+        super().__init__(ctx, h)
+        self.rank, self.n = int(info[0]), int(info[1])
+        self.info = {"rank": self.rank, "n": self.n, "diag_min": float(info[2]), "diag_max": float(info[3])}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def apply(self, R):
+        """`P^-1 R` (`gsi_precond_apply`): a host vector or matrix, or a `DeviceMatrix`; the result is of the same kind."""
+        ctx, lib = self.ctx, self.ctx.lib
+        if isinstance(R, DeviceMatrix):
+            Z = DeviceMatrix(ctx, *R.shape)
+            try:
+                L.check(lib.gsi_precond_apply(ctx.h, self.h, R.h, Z.h), lib)
+            except Exception:
+                Z.close()
+                raise
+            return Z
+        Rf = L.fmat(R, "R")
+        if Rf.shape[0] != self.n:
+            raise ValueError(f"dimension mismatch: the preconditioner has {self.n} rows, R has {Rf.shape[0]}")
+        Rd = DeviceMatrix.from_host(ctx, Rf)
+        try:
+            Z = self.apply(Rd)
+            try:
+                out = Z.to_host()
+            finally:
+                Z.close()
+        finally:
+            Rd.close()
+        return out[:, 0].copy() if np.ndim(R) == 1 else out
+
+
+def lowrank_preconditioner(op, rank=None, basis=None, diag=None, shift=0.0, p=None, q=2, seed=None):
+    """A `Preconditioner` P = Z Z' + diag(diag + shift) for solves with `op` (`gsi_precond_lowrank_create`).  `basis`: a
+    `DeviceMatrix` or a host n x K array whose first `rank` columns (all of them by default) are Z; otherwise `rank` runs the
+    device randsvd of `op` (`gsi_randsvd_dev`: Z Z' ~ A, oversampling `p` -- min(rank, 64) by default, at most n - rank --
+    and `q` power steps, Omega from `gsi_mat_randn` with `seed`) and the basis is dropped once the preconditioner is built.
+    `diag`: None, a scalar or n values, normally the solve's; every diag + shift must be positive."""
+    op, _ = RMF._as_operator(op)
+    ctx, lib = op.ctx, op.ctx.lib
+    n = op.shape[0]
+    d = _diag_arg(diag, n)
+    owned = []
+    try:
+        if basis is not None:
+            Z = basis
+            if not isinstance(Z, DeviceMatrix):
+                Z = DeviceMatrix.from_host(ctx, basis)
+                owned.append(Z)
+            K = Z.shape[1] if rank is None else int(rank)
+        else:
+            if rank is None:
+                raise ValueError("lowrank_preconditioner needs rank or basis")
+            K = int(rank)
+            pp = max(0, min(min(K, 64) if p is None else int(p), n - K))
+            Om = DeviceMatrix(ctx, n, K + pp)
+            owned.append(Om)
+            Om.randn(0 if seed is None else int(seed))
+            Z = DeviceMatrix(ctx, n, K + pp)
+            owned.append(Z)
+            L.check(lib.gsi_randsvd_dev(ctx.h, op.h, Om.h, K, pp, int(q), Z.h, None), lib)
+        h = C.c_void_p()
+        info = (C.c_double * 4)()
+        L.check(lib.gsi_precond_lowrank_create(ctx.h, C.byref(h), Z.h, K, L.dptr(d) if d is not None else None, float(shift),
+                                               info), lib)
+        return Preconditioner(ctx, h, info)
+    finally:
+        for m in owned:
+            m.close()
+
+
+def solve(op, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=False, precond=None):
     """`(A + diag) X = B` for a square, symmetric positive semidefinite operator `op` by conjugate gradients, every column
     of `B` at once (`gsi_op_solve_cg` / `gsi_op_solve`).  `B`: a host vector or matrix, or a `DeviceMatrix`; the result
     is of the same kind.  `diag`: None, a scalar, or n values >= 0.  A column stops when its recurred residual is below
     `tol` times the column's norm; `maxiter` defaults to 10 n.  `strict`: a column that has not converged within
     `maxiter` raises RuntimeError with the counts (otherwise it is only reported).  `return_info`: also a dict with
     `products`, `converged`, `path` ("fused" / "composed"), `breakdown`, `relres` and `iters` per column.  An operator
-    that is not positive definite along a search direction raises `GsiError` (GSI_ERR_NOT_POSDEF) naming the column."""
+    that is not positive definite along a search direction raises `GsiError` (GSI_ERR_NOT_POSDEF) naming the column.
+    `precond`: a `Preconditioner` -- the preconditioned solver (`gsi_op_solve_pcg` / `gsi_op_solve_pcg_host`) with the
+    same stopping rule; the report then also has `breakdown_kind` (1: p'(A + D)p, 2: r'z) and `rank`."""
     op, _ = RMF._as_operator(op)
     ctx, lib = op.ctx, op.ctx.lib
     n = op.shape[0]
     d = _diag_arg(diag, n)
     dp = L.dptr(d) if d is not None else None
     maxiter = 10 * n if maxiter is None else int(maxiter)
-    info = (C.c_int64 * 4)()
+    info = (C.c_int64 * (4 if precond is None else 6))()
     if isinstance(B, DeviceMatrix):
         b = B.shape[1]
         relres, iters = np.zeros(b), np.zeros(b, dtype=np.int64)
         X = DeviceMatrix(ctx, B.shape[0], b)
-        status = lib.gsi_op_solve_cg(ctx.h, op.h, dp, B.h, X.h, float(tol), maxiter, info, L.dptr(relres),
-                                     iters.ctypes.data_as(C.POINTER(C.c_int64)))
+        ip = iters.ctypes.data_as(C.POINTER(C.c_int64))
+        if precond is None:
+            status = lib.gsi_op_solve_cg(ctx.h, op.h, dp, B.h, X.h, float(tol), maxiter, info, L.dptr(relres), ip)
+        else:
+            status = lib.gsi_op_solve_pcg(ctx.h, op.h, dp, precond.h, B.h, X.h, float(tol), maxiter, info, L.dptr(relres), ip)
         if status != 0:
             X.close()
         out = X
@@ -56,12 +144,19 @@ def solve(op, B, diag=None, tol=1e-10, maxiter=None, strict=True, return_info=Fa
             raise ValueError(f"dimension mismatch: operator is {op.shape[0]}x{op.shape[1]}, B has {Bf.shape[0]} rows")
         relres, iters = np.zeros(b), np.zeros(b, dtype=np.int64)
         Xh = np.zeros((n, b), order="F")
-        status = lib.gsi_op_solve(ctx.h, op.h, dp, L.dptr(Bf), n, b, L.dptr(Xh), n, float(tol), maxiter, info,
-                                  L.dptr(relres), iters.ctypes.data_as(C.POINTER(C.c_int64)))
+        ip = iters.ctypes.data_as(C.POINTER(C.c_int64))
+        if precond is None:
+            status = lib.gsi_op_solve(ctx.h, op.h, dp, L.dptr(Bf), n, b, L.dptr(Xh), n, float(tol), maxiter, info,
+                                      L.dptr(relres), ip)
+        else:
+            status = lib.gsi_op_solve_pcg_host(ctx.h, op.h, dp, precond.h, L.dptr(Bf), n, b, L.dptr(Xh), n, float(tol), maxiter,
+                                               info, L.dptr(relres), ip)
         out = Xh[:, 0] if np.ndim(B) == 1 else Xh
     L.check(status, lib)
     rep = {"products": int(info[0]), "converged": int(info[1]), "path": PATHS.get(int(info[2]), int(info[2])),
            "breakdown": int(info[3]), "relres": relres, "iters": iters, "columns": b}
+    if precond is not None:
+        rep["breakdown_kind"], rep["rank"] = int(info[4]), int(info[5])
     if strict and rep["converged"] < b:
         if isinstance(out, DeviceMatrix):
             out.close()
@@ -80,7 +175,7 @@ def kriging_weights(op, y, noise=None, drift=None, **cg):
     """The weights of (universal) kriging: with M = A + diag(noise) and the drift matrix G (m x p, e.g. [1, x, y]),
     `xi, beta` such that  M xi + G beta = y,  G' xi = 0  -- from ONE solve of the 1 + p columns [y, G]:
     beta = (G' M^-1 G)^-1 G' M^-1 y on the host, xi = M^-1 y - M^-1 G beta.  Without `drift`, xi = M^-1 y and beta is
-    empty.  `cg`: `tol`, `maxiter`, `strict` of `solve`."""
+    empty.  `cg`: `tol`, `maxiter`, `strict`, `precond` of `solve`."""
     yv = np.asarray(y, dtype=np.float64).reshape(-1)
     m = yv.size
     if drift is None:
