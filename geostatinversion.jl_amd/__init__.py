@@ -15,9 +15,9 @@ from .context import (Context, Operator, DeviceMatrix, dense_operator, gridcov_o
                       gridcov_implicit_operator, pointcov_implicit_operator, fft_powerlaw_operator, fft_gridcov_operator, lowrank_synthetic_operator,
                       default_context)
 from . import randmatfact as RandMatFact
-from .randmatfact import rangefinder, randsvd, randsvd_rows, eig_nystrom, colnorms, lu_L, lu_L_dev, lu_L_sharded, lu_L_sharded_virtual, qr_thinQ, svd_tall, gemm, gemm_view
+from .randmatfact import rangefinder, randsvd, randsvd_rows, eig_nystrom, colnorms, lu_L, lu_L_dev, lu_L_sharded, lu_L_sharded_virtual, qr_thinQ, svd_tall, gemm, gemm_view, pivoted_cholesky, principal_factor
 from .lowrank import LowRankCovMatrix, PCGALowRankMatrix, device_samples
-from .getxis import getxis, getxis_iwantfields, getxis_device, getxis_fftrf, randsvdwithseed
+from .getxis import getxis, getxis_iwantfields, getxis_device, getxis_fftrf, getxis_pivchol, randsvdwithseed
 from . import fftrf as FFTRF
 from .fftrf import lowrank_fftrf_operator, fft_operator_at, FFTOperatorAt
 from . import gridcov as GridCov
@@ -36,5 +36,5 @@ __all__ = [
     "gridcov_sampler", "lowrank_gridcov_operator", "gridcov_structuredgrid", "pcgadirect", "pcgalsqr", "rga", "pcga",
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",
     "Kriging", "solve", "kriging_weights", "krige_to_grid", "condition_fields", "mat_axpy",
-    "lowrank_preconditioner", "Preconditioner",
+    "lowrank_preconditioner", "Preconditioner", "pivoted_cholesky", "principal_factor", "getxis_pivchol",
 ]

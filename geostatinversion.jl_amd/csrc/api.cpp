@@ -1523,6 +1523,45 @@ int gsi_mat_axpy(gsi_ctx* ctx, double alpha, const gsi_mat* X, gsi_mat* Y) {
   });
 }
 
+// ---- diagonal-pivoted Cholesky of a covariance read by entries, and the principal form of a factor ----
+int gsi_op_pivoted_cholesky(gsi_ctx* ctx, const gsi_op* op, int64_t K, double tol, gsi_mat* L, int64_t* piv_out, int64_t* info,
+                            double* err_out) {
+  return guarded([&] {
+    if (info) for (int i = 0; i < 6; ++i) info[i] = 0;
+    if (err_out) err_out[0] = err_out[1] = err_out[2] = 0.0;
+    REQUIRE(ctx && op && L, "gsi_op_pivoted_cholesky: ctx, op or L is NULL");
+    REQUIRE(op->op.ctx == &ctx->c, "gsi_op_pivoted_cholesky: op belongs to another context");
+    REQUIRE(L->ctx == ctx, "gsi_op_pivoted_cholesky: L belongs to another context");
+    pivoted_cholesky_check(op->op, K, tol, L->rows, L->cols);
+    const PcholInfo r = pivoted_cholesky(op->op, K, tol, L->buf.p, piv_out);
+    if (info) { info[0] = r.rank; info[1] = r.reason; info[2] = r.path; info[3] = r.form; info[4] = r.polls; info[5] = 0; }
+    if (err_out) { err_out[0] = r.trace0; err_out[1] = r.trace; err_out[2] = r.dmax; }
+    check_async_errors(ctx->c);
+    if (r.reason == 4)
+      throw Error(GSI_ERR_NOT_POSDEF, r.rank == 0
+                      ? std::string("pivoted Cholesky: the diagonal of op holds a non-finite value (step 0)")
+                      : "pivoted Cholesky: a non-finite value was met in step " + std::to_string(r.rank - 1) +
+                            " (0-based; in its column, in d or in the trace)");
+  });
+}
+
+int gsi_mat_principal_factor(gsi_ctx* ctx, const gsi_mat* L, int64_t K, gsi_mat* Z_out, double* s_out) {
+  return guarded([&] {
+    REQUIRE(ctx && L && Z_out, "gsi_mat_principal_factor: ctx, L or Z_out is NULL");
+    REQUIRE(L->ctx == ctx && Z_out->ctx == ctx, "gsi_mat_principal_factor: L or Z_out belongs to another context");
+    REQUIRE(!ctx->c.comm, "gsi_mat_principal_factor: ctx has a communicator; the factor lives on one rank");
+    REQUIRE(K >= 1 && K <= L->cols, "gsi_mat_principal_factor: K must lie in 1 .. the columns of L");
+    REQUIRE(K <= L->rows, "gsi_mat_principal_factor: K exceeds the rows of L");
+    REQUIRE(Z_out->rows == L->rows && Z_out->cols >= K, "gsi_mat_principal_factor: Z_out must have the rows of L and at least K columns");
+    REQUIRE(Z_out != L && Z_out->buf.p != L->buf.p, "gsi_mat_principal_factor: Z_out must not be L");
+    Backend* be = ctx->c.be.get();
+    Buf S(be, (size_t)K);
+    principal_factor(ctx->c, L->buf.p, L->rows, K, Z_out->buf.p, S.p);
+    if (s_out) be->download2d(s_out, K, S.p, K, K, 1);
+    check_async_errors(ctx->c);
+  });
+}
+
 int gsi_pcgamat_create(gsi_ctx* ctx, gsi_pcgamat** mat, const double* etas, int64_t nobs, int64_t K, const double* HX,
                        const double* R, int r_is_diag) {
   return guarded([&] {

@@ -469,6 +469,36 @@ class Backend {
   virtual int precond_rows(int64_t n, double* e, double* sqe) { (void)n; (void)e; (void)sqe; return 0; }
   virtual int add_identity(double* C, int64_t K) { (void)C; (void)K; return 0; }
 
+  // ---- diagonal-pivoted Cholesky of a covariance read by entries (pchol_state.hpp).  Where
+  //      A(i, p) comes from: form 1 -- data = the stored n x n matrix (ld); 2 -- data = the gx * gy table over grid offsets;
+  //      3 -- data = the d x n coordinates of a scattered-point covariance with the parameters below.
+  struct PcholSource {
+    int form = 0;
+    const double* data = nullptr;
+    int64_t ld = 0, gx = 0, gy = 0;
+    int pc_d = 0, pc_kind = 0;
+    double pc_ell = 1.0, pc_sigma2 = 1.0, pc_nugget = 0.0;
+  };
+  // `work` holds pchol_work_doubles doubles and starts with the state block (pchol::state_doubles(K)); d: n doubles;
+  // L: n x >= K, ld ldl, its first K columns cleared by the caller.  0 = "not mine" (the default): pipeline.cpp runs
+  // pivoted_chol_host.hpp.
+  virtual size_t pchol_work_doubles(const PcholSource& a, int64_t n, int64_t K) { (void)a; (void)n; (void)K; return 0; }
+  // d <- diag(A), the state of a fresh factorization, the first decision
+  virtual void pchol_begin(const PcholSource& a, int64_t n, int64_t K, double tol, const double* L, int64_t ldl, double* d,
+                           double* work) {
+    (void)a; (void)n; (void)K; (void)tol; (void)L; (void)ldl; (void)d; (void)work;
+    throw Error(1 /* GSI_ERR_ARG */, "pivoted_cholesky: not available on this backend");
+  }
+  // one step and the decision behind it, enqueued; a no-op once the state block says stop
+  virtual void pchol_step(const PcholSource& a, int64_t n, int64_t K, double* L, int64_t ldl, double* d, double* work) {
+    (void)a; (void)n; (void)K; (void)L; (void)ldl; (void)d; (void)work;
+    throw Error(1 /* GSI_ERR_ARG */, "pivoted_cholesky: not available on this backend");
+  }
+  // U (n x K, ld ldu): column k *= S[k], S in backend memory.  1, or 0: "not mine" (the caller scales on the host).
+  virtual int scale_cols(int64_t n, int64_t K, double* U, int64_t ldu, const double* S) {
+    (void)n; (void)K; (void)U; (void)ldu; (void)S; return 0;
+  }
+
   // ---- fp32-STORED xi-basis (BASELINE configs[4], "fp32 mixed precision"): the n x K basis is the one big HBM stream
   //      of the PCGA iteration's own algebra; stored in fp32 it is half the bytes, every sum stays in fp64 ----
   virtual void f64_to_f32(const double* src, void* dst32, size_t count) = 0;

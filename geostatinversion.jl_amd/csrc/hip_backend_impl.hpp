@@ -255,6 +255,11 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
                       double* X, double* R, double* P, double* S, double* Y, double* work) override;
   int precond_rows(int64_t n, double* e, double* sqe) override;
   int add_identity(double* C, int64_t K) override;
+  size_t pchol_work_doubles(const PcholSource& a, int64_t n, int64_t K) override { return hipk::pchol_work_doubles(a.form, n, K); }
+  void pchol_begin(const PcholSource& a, int64_t n, int64_t K, double tol, const double* L, int64_t ldl, double* d,
+                   double* work) override;
+  void pchol_step(const PcholSource& a, int64_t n, int64_t K, double* L, int64_t ldl, double* d, double* work) override;
+  int scale_cols(int64_t n, int64_t K, double* U, int64_t ldu, const double* S) override;
   void block_cg_begin(int64_t n, int64_t b, const double* B, double tol, int64_t maxiter, double* work) override;
   void block_cg_step(int64_t n, int64_t b, const double* Q, const double* d, double* X, double* R, double* P,
                      double* work) override;

@@ -117,6 +117,35 @@ int HipBackend::add_identity(double* C, int64_t K) {
   check_launch("add_identity");
   return 1;
 }
+// Diagonal-pivoted Cholesky (pivoted_chol.hip).  The scattered-point form keeps the points as the
+// generator's pre-scaled 32-byte records inside `work`, made once by pchol_begin.
+static hipk::PcholCol pchol_col(const Backend::PcholSource& a, double* work, int64_t n, int64_t K) {
+  hipk::PcholCol c;
+  c.form = a.form; c.a = a.data; c.ld = a.ld; c.ny = (int32_t)a.gy;
+  c.dim = a.pc_d; c.kind = a.pc_kind; c.sigma2 = a.pc_sigma2; c.nugget = a.pc_nugget;
+  if (a.form == 3) c.a = hipk::pchol_points(work, n, K);
+  return c;
+}
+void HipBackend::pchol_begin(const PcholSource& a, int64_t n, int64_t K, double tol, const double* L, int64_t ldl, double* d,
+                             double* work) {
+  bind();
+  if (a.form == 3)
+    hipk::pointcov_pad_points(st_, a.data, a.pc_d, n, hipk::pointcov_point_scale(a.pc_kind, 1.0 / a.pc_ell),
+                              hipk::pchol_points(work, n, K));
+  hipk::pchol_begin(st_, pchol_col(a, work, n, K), n, K, tol, L, ldl, d, work);
+  check_launch("pchol_begin");
+}
+void HipBackend::pchol_step(const PcholSource& a, int64_t n, int64_t K, double* L, int64_t ldl, double* d, double* work) {
+  bind();
+  hipk::pchol_step(st_, pchol_col(a, work, n, K), n, K, L, ldl, d, work);
+  check_launch("pchol_step");
+}
+int HipBackend::scale_cols(int64_t n, int64_t K, double* U, int64_t ldu, const double* S) {
+  bind();
+  hipk::scale_cols(st_, n, K, U, ldu, S);
+  check_launch("scale_cols");
+  return 1;
+}
 void HipBackend::f64_to_f32(const double* src, void* dst32, size_t count) {
   bind();
   hipk::f64_to_f32(st_, src, (float*)dst32, count);

@@ -258,6 +258,24 @@ void block_pcg_step_p(hipStream_t st, int64_t n, int64_t b, const double* e, con
 void pcg_precond_rows(hipStream_t st, int64_t n, double* e, double* sqe);
 void pcg_add_identity(hipStream_t st, double* C, int64_t K);
 
+// ---- pivoted_chol.hip: diagonal-pivoted Cholesky of a covariance read by entries (pchol_state.hpp) ----
+// where A(i, p) comes from.  form 1: a = the stored matrix (ld); 2: a = the nx * ny table over grid offsets; 3: a = the points
+// as the 32-byte records of pointcov_pad_points, entries by the generator of pointcov_gen.hpp
+struct PcholCol {
+  int form;
+  const double* a;
+  int64_t ld;
+  int32_t ny;
+  int dim, kind;
+  double sigma2, nugget;
+};
+size_t pchol_work_doubles(int form, int64_t n, int64_t K);
+double* pchol_points(double* work, int64_t n, int64_t K);     // form 3: where the 4 n doubles of the records lie in `work`
+void pchol_begin(hipStream_t st, const PcholCol& a, int64_t n, int64_t K, double tol, const double* L, int64_t ldl, double* d,
+                 double* work);
+void pchol_step(hipStream_t st, const PcholCol& a, int64_t n, int64_t K, double* L, int64_t ldl, double* d, double* work);
+void scale_cols(hipStream_t st, int64_t n, int64_t K, double* U, int64_t ldu, const double* S);
+
 // ---- panel_qr.hip ----
 constexpr int QR_NB = 16;
 struct QrWork {

@@ -14,6 +14,8 @@
 #include "lsqr_state.hpp"
 #include "block_cg_host.hpp"
 #include "block_pcg_host.hpp"
+#include "pivoted_chol_host.hpp"
+#include "pointcov.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1383,6 +1385,109 @@ BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPreco
     if (iters) iters[j] = (int64_t)colv(st.data(), ITERS, j);
   }
   return info;
+}
+
+// ---- diagonal-pivoted Cholesky of a covariance read by entries (pipeline.hpp) ----
+static int pchol_form(const Operator& A) {
+  switch (A.kind) {
+    case OP_DENSE: return 1;
+    case OP_GRIDCOV_IMPLICIT: return 2;
+    case OP_POINTCOV: return 3;
+    default: return 0;
+  }
+}
+void pivoted_cholesky_check(const Operator& A, int64_t K, double tol, int64_t Lrows, int64_t Lcols) {
+  Context& c = *A.ctx;
+  if (c.comm) throw Error(GSI_ERR_ARG, "pivoted_cholesky: ctx has a communicator; the factorization runs on one rank");
+  if (pchol_form(A) == 0)
+    throw Error(GSI_ERR_ARG, "pivoted_cholesky: op must be a dense, an implicit grid-covariance or an implicit point-covariance "
+                             "operator (the kinds whose entries can be read); use randsvd for the others");
+  if (A.m != A.n) throw Error(GSI_ERR_ARG, "pivoted_cholesky: op is " + std::to_string(A.m) + " x " + std::to_string(A.n) + ", not square");
+  if (A.kind == OP_DENSE && (A.row0 != 0 || A.mloc != A.m))
+    throw Error(GSI_ERR_ARG, "pivoted_cholesky: op does not hold all its rows on this rank");
+  if (A.pending_upload != nullptr) throw Error(GSI_ERR_ARG, "pivoted_cholesky: op has an upload pending");
+  if (K < 1) throw Error(GSI_ERR_ARG, "pivoted_cholesky: K must be at least 1");
+  if (K > A.n) throw Error(GSI_ERR_ARG, "pivoted_cholesky: K exceeds the size of op, " + std::to_string(A.n));
+  if (K > 2048) throw Error(GSI_ERR_ARG, "pivoted_cholesky: K exceeds 2048");
+  if (Lrows != A.n) throw Error(GSI_ERR_ARG, "pivoted_cholesky: L must have size(op, 1) = " + std::to_string(A.n) + " rows");
+  if (K > Lcols) throw Error(GSI_ERR_ARG, "pivoted_cholesky: K exceeds the columns of L, " + std::to_string(Lcols));
+  if (!(tol >= 0.0 && tol < 1.0)) throw Error(GSI_ERR_ARG, "pivoted_cholesky: tol must lie in [0, 1)");
+}
+
+PcholInfo pivoted_cholesky(const Operator& A, int64_t K, double tol, double* L, int64_t* piv) {
+  using namespace pchol;
+  Backend* be = A.ctx->be.get();
+  const int64_t n = A.n;
+  Backend::PcholSource src;
+  src.form = pchol_form(A);
+  src.data = A.data.p; src.ld = A.ld; src.gx = A.gx; src.gy = A.gy;
+  src.pc_d = A.pc_d; src.pc_kind = A.pc_kind; src.pc_ell = A.pc_ell; src.pc_sigma2 = A.pc_sigma2; src.pc_nugget = A.pc_nugget;
+  const char* ec = getenv("GSI_PCHOL_COMPOSED");
+  const size_t wd = (ec && atoi(ec) != 0) ? 0 : be->pchol_work_doubles(src, n, K);
+  PcholInfo info;
+  info.path = wd ? 1 : 3;
+  info.form = src.form;
+  std::vector<double> st(state_doubles(K), 0.0);
+  if (wd) {
+    int64_t poll = 8;
+    if (const char* e = getenv("GSI_PCHOL_POLL")) poll = std::max<int64_t>(1, atoll(e));
+    Buf work(be, wd), d(be, (size_t)n);
+    be->fill_zero(L, (size_t)n * K);
+    ScopedPhase ph(be, PH_OTHER);
+    be->pchol_begin(src, n, K, tol, L, n, d.p, work.p);
+    double hdr[S_COUNT];
+    be->download2d(hdr, S_COUNT, work.p, S_COUNT, S_COUNT, 1);
+    info.polls = 1;
+    int64_t enq = 0;
+    while (hdr[S_REASON] == 0.0 && enq < K) {
+      const int64_t burst = std::min<int64_t>(poll, K - enq);
+      for (int64_t k = 0; k < burst; ++k) be->pchol_step(src, n, K, L, n, d.p, work.p);
+      enq += burst;
+      be->download2d(hdr, S_COUNT, work.p, S_COUNT, S_COUNT, 1);
+      ++info.polls;
+    }
+    be->download2d(st.data(), (int64_t)st.size(), work.p, (int64_t)st.size(), (int64_t)st.size(), 1);
+  } else {
+    // the diagonal by entries, as the kernels read it; the columns by the operator product with a unit vector
+    std::vector<double> dh((size_t)n), Lh((size_t)n * K);
+    if (src.form == 1) be->download2d(dh.data(), 1, A.data.p, A.ld + 1, 1, n);
+    else if (src.form == 2) { double t0 = 0.0; be->download2d(&t0, 1, A.data.p, 1, 1, 1); std::fill(dh.begin(), dh.end(), t0); }
+    else {
+      const pointcov::Params pp = {A.pc_d, A.pc_kind, 1.0 / A.pc_ell, A.pc_sigma2, A.pc_nugget};
+      std::fill(dh.begin(), dh.end(), pointcov::kernel(pp, 0.0, true));
+    }
+    Buf e(be, (size_t)n), y(be, (size_t)n);
+    be->fill_zero(e.p, (size_t)n);
+    const double one = 1.0, zero = 0.0;
+    host_factor(n, K, tol, dh.data(), [&](int64_t p, double* out) {
+      be->upload2d(e.p + p, 1, &one, 1, 1, 1);
+      op_mul(A, e.p, n, 1, y.p, n);
+      be->upload2d(e.p + p, 1, &zero, 1, 1, 1);
+      be->download2d(out, n, y.p, n, n, 1);
+    }, Lh.data(), n, st);
+    be->upload2d(L, n, Lh.data(), n, n, K);
+  }
+  info.rank = (int64_t)st[S_STEP];
+  info.reason = (int64_t)st[S_REASON];
+  info.trace0 = st[S_TRACE0]; info.trace = st[S_TRACE]; info.dmax = st[S_DMAX];
+  if (piv)
+    for (int64_t j = 0; j < K; ++j) piv[j] = (j < info.rank) ? (int64_t)st[(size_t)S_COUNT + (size_t)j] : -1;
+  return info;
+}
+
+void principal_factor(Context& c, const double* L, int64_t n, int64_t K, double* Z, double* S) {
+  Backend* be = c.be.get();
+  Buf W(be, (size_t)n * K);
+  be->copy2d(W.p, n, L, n, n, K);
+  svd_tall(c, W.p, n, K, -1, Z, S);                             // Z = U (plain), S = the singular values
+  if (!be->scale_cols(n, K, Z, n, S)) {
+    std::vector<double> zh((size_t)n * K), sh((size_t)K);
+    be->download2d(zh.data(), n, Z, n, n, K);
+    be->download2d(sh.data(), K, S, K, K, 1);
+    for (int64_t k = 0; k < K; ++k)
+      for (int64_t i = 0; i < n; ++i) zh[(size_t)(i + k * n)] *= sh[(size_t)k];
+    be->upload2d(Z, n, zh.data(), n, n, K);
+  }
 }
 
 int64_t rangefinder_adaptive(const Operator& A, randn_fn rn, void* user, double epsilon, int64_t r,

@@ -183,6 +183,24 @@ struct BlockPcgInfo { int64_t products = 0, converged = 0, path = 0, breakdown_c
 void block_pcg_check(const Operator& A, const LowRankPrecond& pc, int64_t b, double tol, int64_t maxiter);
 BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPrecond& pc, const double* B, double* X, int64_t b,
                        double tol, int64_t maxiter, double* relres, int64_t* iters);
+// ---- diagonal-pivoted Cholesky of a covariance read by entries (pchol_state.hpp): L L' ~ A from K
+//      columns of A, without an operator product.  A: OP_DENSE (one rank, all rows resident, nothing pending),
+//      OP_GRIDCOV_IMPLICIT or OP_POINTCOV, square.  L: n x >= K in backend memory, ld n; columns rank .. K - 1 are zeros.
+//      piv (HOST, K, may be null): the pivots, -1 beyond the rank.  reason: pchol::STOP_*; a non-finite value (reason 4) is
+//      reported, the caller raises GSI_ERR_NOT_POSDEF.  Path 1: the backend's kernels with the state resident in backend
+//      memory, polled every GSI_PCHOL_POLL steps (8; read per call).  Path 3: pivoted_chol_host.hpp with columns from
+//      op_mul on a unit vector -- when the backend has no such kernels, or GSI_PCHOL_COMPOSED=1 (read per call); it holds
+//      L on the host.  form: 1 stored, 2 table, 3 points.
+struct PcholInfo {
+  int64_t rank = 0, reason = 0, path = 0, form = 0, polls = 0;
+  double trace0 = 0.0, trace = 0.0, dmax = 0.0;
+};
+// what pivoted_cholesky refuses (GSI_ERR_ARG naming the argument), before anything is allocated
+void pivoted_cholesky_check(const Operator& A, int64_t K, double tol, int64_t Lrows, int64_t Lcols);
+PcholInfo pivoted_cholesky(const Operator& A, int64_t K, double tol, double* L, int64_t* piv);
+// Z (n x K, ld n) = U diag(s) for the thin SVD L[:, :K] = U diag(s) V' of a resident n x >= K matrix (ld n): Z Z' = L L'
+// with orthogonal columns, the form randsvd returns.  S (backend memory, K): the singular values.  L is not modified.
+void principal_factor(Context& c, const double* L, int64_t n, int64_t K, double* Z, double* S);
 // throws Error if a kernel raised an asynchronous flag
 void check_async_errors(Context& c);
 

@@ -75,6 +75,36 @@ def getxis_device(Q, numxis, p, q=3, seed=None, *, Omega=None, ctx=None, precisi
             op.close()
 
 
+def getxis_pivchol(Q, numxis, tol=0.0, *, principal=True, precision=64, ctx=None):
+    """A xi-basis from the diagonal-pivoted Cholesky factor of Q (`RandMatFact.pivoted_cholesky`; no operator product): a
+    `DeviceBasis`, as `getxis_device` returns, of the columns that were reached -- `numxis`, or fewer by `tol` or where Q is
+    exhausted.  Q: a host matrix, or a dense / implicit grid-covariance / implicit point-covariance `Operator`.
+    `principal=True` turns the factor into its principal form (`RandMatFact.principal_factor`: orthogonal columns in
+    descending order of norm, as `randsvd` returns them); with `False` the columns are those of L, in pivot order.  The PCGA
+    consumers only use sum xi xi' = L L', which both forms share."""
+    from .context import Operator, dense_operator, default_context
+    from .pcga import DeviceBasis
+    owned = not isinstance(Q, Operator)
+    op = dense_operator(ctx or default_context(), Q) if owned else Q
+    try:
+        Ld, piv, _ = RMF._pivoted_cholesky_dev(op, numxis, tol)
+    finally:
+        if owned:
+            op.close()
+    K = len(piv)
+    if K == 0:
+        Ld.close()
+        raise ValueError("pivoted_cholesky found rank 0: Q has no positive diagonal entry")
+    if principal:
+        try:
+            Z, _ = RMF.principal_factor(Ld, K)
+        finally:
+            Ld.close()
+    else:
+        Z = Ld
+    return DeviceBasis(Z, K, precision=precision)
+
+
 def getxis_fftrf(Ns, k0, dk, beta, numfields, numxis, p, q=3, seed=None, *, field_seed=0, Omega=None, ctx=None, device=False,
                  points=None, box=None):
     """`getxis(() -> FFTRF.powerlaw_structuredgrid(Ns, k0, dk, beta), numfields, numxis, p, q, seed)` with the fields sampled

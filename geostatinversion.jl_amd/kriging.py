@@ -69,19 +69,33 @@ class Preconditioner(_Handle):
         return out[:, 0].copy() if np.ndim(R) == 1 else out
 
 
-def lowrank_preconditioner(op, rank=None, basis=None, diag=None, shift=0.0, p=None, q=2, seed=None):
+def lowrank_preconditioner(op, rank=None, basis=None, diag=None, shift=0.0, p=None, q=2, seed=None, *, method="randsvd",
+                           tol=0.0):
     """A `Preconditioner` P = Z Z' + diag(diag + shift) for solves with `op` (`gsi_precond_lowrank_create`).  `basis`: a
     `DeviceMatrix` or a host n x K array whose first `rank` columns (all of them by default) are Z; otherwise `rank` runs the
     device randsvd of `op` (`gsi_randsvd_dev`: Z Z' ~ A, oversampling `p` -- min(rank, 64) by default, at most n - rank --
     and `q` power steps, Omega from `gsi_mat_randn` with `seed`) and the basis is dropped once the preconditioner is built.
+    `method="pivoted_cholesky"` factors `op` by `RandMatFact.pivoted_cholesky` instead -- no operator product; for dense,
+    implicit grid-covariance and implicit point-covariance operators -- to `rank`, or to fewer columns where the trace of
+    the remainder has fallen to `tol` times the trace of `op`; `Preconditioner.rank` is the rank that was reached.
     `diag`: None, a scalar or n values, normally the solve's; every diag + shift must be positive."""
+    if method not in ("randsvd", "pivoted_cholesky"):
+        raise ValueError("method must be 'randsvd' or 'pivoted_cholesky'")
     op, _ = RMF._as_operator(op)
     ctx, lib = op.ctx, op.ctx.lib
     n = op.shape[0]
     d = _diag_arg(diag, n)
     owned = []
     try:
-        if basis is not None:
+        if basis is None and method == "pivoted_cholesky":
+            if rank is None:
+                raise ValueError("lowrank_preconditioner needs rank or basis")
+            Z, piv, _ = RMF._pivoted_cholesky_dev(op, min(int(rank), n), tol)
+            owned.append(Z)
+            K = len(piv)
+            if K == 0:
+                raise ValueError("pivoted_cholesky found rank 0: op has no positive diagonal entry")
+        elif basis is not None:
             Z = basis
             if not isinstance(Z, DeviceMatrix):
                 Z = DeviceMatrix.from_host(ctx, basis)

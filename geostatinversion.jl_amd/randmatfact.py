@@ -168,6 +168,90 @@ def randsvd_rows(op, K, p, q, Omega_rows, *, return_S=False):
     return (Z, Sh) if return_S else Z
 
 
+PCHOL_REASONS = {1: "rank", 2: "trace", 3: "exhausted", 4: "non-finite"}
+PCHOL_FORMS = {1: "stored", 2: "table", 3: "points"}
+
+
+def _pivoted_cholesky_dev(op, K, tol):
+    """`gsi_op_pivoted_cholesky` on an `Operator`: (L as a DeviceMatrix of n x K, piv, info)."""
+    from .context import DeviceMatrix
+    cx, lib = op.ctx, op.ctx.lib
+    n = op.shape[0]
+    K = int(K)
+    # (the library refuses these before it allocates; L is allocated here, so the shape is checked first)
+    if not 1 <= K <= min(n, 2048):
+        raise ValueError(f"K must lie in 1 .. min(n, 2048) = {min(n, 2048)}")
+    Ld = DeviceMatrix(cx, n, K)
+    piv = np.full(K, -1, dtype=np.int64)
+    info = (C.c_int64 * 6)()
+    err = (C.c_double * 3)()
+    try:
+        L.check(lib.gsi_op_pivoted_cholesky(cx.h, op.h, K, float(tol), Ld.h, piv.ctypes.data_as(C.POINTER(C.c_int64)), info,
+                                            err), lib)
+    except Exception:
+        Ld.close()
+        raise
+    rank = int(info[0])
+    rep = {"rank": rank, "reason": int(info[1]), "stopped_by": PCHOL_REASONS.get(int(info[1]), int(info[1])),
+           "path": {1: "fused", 3: "composed"}.get(int(info[2]), int(info[2])),
+           "form": PCHOL_FORMS.get(int(info[3]), int(info[3])), "polls": int(info[4]),
+           "trace0": float(err[0]), "trace": float(err[1]), "dmax": float(err[2])}
+    return Ld, piv[:rank].copy(), rep
+
+
+def pivoted_cholesky(A, K, tol=0.0, *, return_info=False, ctx=None):
+    """Diagonal-pivoted Cholesky `L L' ~ A` of a symmetric positive semidefinite `A` that is read by entries
+    (`gsi_op_pivoted_cholesky`): K columns of A and no operator product.  `A`: a host matrix, or an
+    `Operator` made by `dense_operator`, `gridcov_implicit_operator` or `pointcov_implicit_operator`.  It stops at rank K,
+    or earlier when the trace of `A - L L'` has fallen to `tol` times that of A, or when A is exhausted.
+    Returns `(L, piv)`: L is n x K with zeros from column `len(piv)` on -- a host array for a host matrix, a `DeviceMatrix`
+    for an `Operator`, as `randsvd` has it --, `piv` the pivot rows in order (the rank entries).  `return_info`: also a dict
+    with `rank`, `reason` (1 rank, 2 trace, 3 exhausted) and `stopped_by`, `path` ("fused" / "composed"), `form`
+    ("stored" / "table" / "points"), `polls`, `trace0`, `trace`, `dmax`."""
+    op, owned = _as_operator(A, ctx)
+    try:
+        Ld, piv, rep = _pivoted_cholesky_dev(op, K, tol)
+        if owned:
+            try:
+                out = Ld.to_host()
+            finally:
+                Ld.close()
+        else:
+            out = Ld
+        return (out, piv, rep) if return_info else (out, piv)
+    finally:
+        if owned:
+            op.close()
+
+
+def principal_factor(Lmat, K=None, *, ctx=None):
+    """With the thin SVD `L[:, :K] = U diag(s) V'`: `(Z, s)` with `Z = U diag(s)`, so that `Z Z' = L L'` with orthogonal
+    columns -- the form `randsvd` returns; `s**2` are the eigenvalues of `L L'` (`gsi_mat_principal_factor`).  `Lmat`: a
+    `DeviceMatrix` (Z is one too) or a host matrix (Z is a host array).  K: all columns by default."""
+    from .context import DeviceMatrix
+    host = not isinstance(Lmat, DeviceMatrix)
+    Ld = DeviceMatrix.from_host(ctx or default_context(), Lmat) if host else Lmat
+    cx = Ld.ctx
+    try:
+        K = Ld.shape[1] if K is None else int(K)
+        Z = DeviceMatrix(cx, Ld.shape[0], max(K, 1))
+        s = np.zeros(max(K, 1))
+        try:
+            L.check(cx.lib.gsi_mat_principal_factor(cx.h, Ld.h, K, Z.h, L.dptr(s)), cx.lib)
+            if host:
+                return Z.to_host(), s
+        except Exception:
+            Z.close()
+            raise
+        finally:
+            if host:
+                Z.close()
+        return Z, s
+    finally:
+        if host:
+            Ld.close()
+
+
 def eig_nystrom(A, Q, *, ctx=None):
     """`eig_nystrom(A, Q)`  (RandMatFact.jl:92-102) -> (U, Sigmavec); eigenvalues are Sigmavec**2."""
     op, owned = _as_operator(A, ctx)

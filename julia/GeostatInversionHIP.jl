@@ -609,6 +609,24 @@ function solve(A::DeviceOperator, B::DeviceMatrix; diag::Union{Nothing, Vector{F
 		A.c.h, A.h, diag === nothing ? C_NULL : diag, B.h, X.h, tol, maxiter, info, relres, iters))
 	return X, (products=info[1], converged=info[2], path=info[3], breakdown=info[4], relres=relres, iters=iters)
 end
+"`pivoted_cholesky(A, K; tol)`: the diagonal-pivoted Cholesky factor `L L' ~ A` of a dense, implicit grid-covariance or implicit
+point-covariance device operator from K columns of A and no operator product (gsi_op_pivoted_cholesky).  Returns
+`(L, piv, info)`: `L` a `DeviceMatrix` of n x K with zeros from column `rank + 1` on, `piv` the 1-based pivot rows (the rank
+entries), `info = (rank, reason, path, form, polls, trace0, trace, dmax)` with reason 1 (rank K reached), 2 (the trace of the
+remainder fell to `tol` times the trace of A) or 3 (A is exhausted)."
+function pivoted_cholesky(A::DeviceOperator, K::Int; tol::Float64=0.0)
+	1 <= K <= min(A.n, 2048) || throw(ArgumentError("pivoted_cholesky: K must lie in 1:min(n, 2048)"))
+	L = DeviceMatrix(A.n, K; c=A.c)
+	piv = fill(Int64(-1), K)
+	info = zeros(Int64, 6)
+	err = zeros(Float64, 3)
+	check(ccall((:gsi_op_pivoted_cholesky, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Ptr{Cvoid}, Ptr{Int64},
+			Ptr{Int64}, Ptr{Float64}),
+		A.c.h, A.h, K, tol, L.h, piv, info, err))
+	rank = Int(info[1])
+	return L, piv[1:rank] .+ 1, (rank=rank, reason=info[2], path=info[3], form=info[4], polls=info[5], trace0=err[1],
+		trace=err[2], dmax=err[3])
+end
 "`axpy!(alpha, X, Y)` for device matrices of one shape: Y += alpha X."
 function LinearAlgebra.axpy!(alpha::Real, X::DeviceMatrix, Y::DeviceMatrix)
 	check(ccall((:gsi_mat_axpy, libgsi), Cint, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}), Y.c.h, Float64(alpha), X.h, Y.h))
