@@ -24,7 +24,7 @@ from . import gridcov as GridCov
 from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, gridcov_structuredgrid
 from . import kriging as Kriging
 from .kriging import (solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy, lowrank_preconditioner,
-                      Preconditioner)
+                      Preconditioner, logdet, log_likelihood, solve_trace)
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
                    posterior_realizations)
 
@@ -36,5 +36,5 @@ __all__ = [
     "gridcov_sampler", "lowrank_gridcov_operator", "gridcov_structuredgrid", "pcgadirect", "pcgalsqr", "rga", "pcga",
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",
     "Kriging", "solve", "kriging_weights", "krige_to_grid", "condition_fields", "mat_axpy",
-    "lowrank_preconditioner", "Preconditioner", "pivoted_cholesky", "principal_factor", "getxis_pivchol",
+    "lowrank_preconditioner", "Preconditioner", "logdet", "log_likelihood", "solve_trace", "pivoted_cholesky", "principal_factor", "getxis_pivchol",
 ]

@@ -113,6 +113,11 @@ SIGNATURES = {
                                    C.POINTER(c_i64)]),
     "gsi_op_solve_pcg_host": (C.c_int, [c_vp, c_vp, c_dp, c_vp, c_dp, c_i64, c_i64, c_dp, c_i64, C.c_double, c_i64,
                                         C.POINTER(c_i64), c_dp, C.POINTER(c_i64)]),
+    "gsi_op_solve_trace": (C.c_int, [c_vp, c_vp, c_dp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_double, c_i64, C.POINTER(c_i64), c_dp,
+                                     C.POINTER(c_i64), c_dp]),
+    "gsi_slq_quadrature": (C.c_int, [c_vp, c_dp, c_dp, C.POINTER(c_i64), c_dp, c_i64, c_i64, c_dp]),
+    "gsi_precond_sample": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gsi_precond_logdet": (C.c_int, [c_vp, c_dp]),
     "gsi_op_pivoted_cholesky": (C.c_int, [c_vp, c_vp, c_i64, C.c_double, c_vp, C.POINTER(c_i64), C.POINTER(c_i64), c_dp]),
     "gsi_mat_principal_factor": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_dp]),
     "gsi_pcgamat_create": (C.c_int, [c_vp, C.POINTER(c_vp), c_dp, c_i64, c_i64, c_dp, c_dp, C.c_int]),

@@ -180,6 +180,16 @@ class Operator(_Handle):
         from .kriging import solve
         return solve(self, B, diag=diag, tol=tol, maxiter=maxiter, strict=strict, return_info=return_info, precond=precond)
 
+    def logdet(self, diag=None, **kw):
+        """log det(A + diag) by stochastic Lanczos quadrature: `kriging.logdet`."""
+        from .kriging import logdet
+        return logdet(self, diag=diag, **kw)
+
+    def log_likelihood(self, y, noise=None, drift=None, restricted=True, **kw):
+        """The Gaussian (restricted) log-likelihood of `y` under A + diag(noise): `kriging.log_likelihood`."""
+        from .kriging import log_likelihood
+        return log_likelihood(self, y, noise=noise, drift=drift, restricted=restricted, **kw)
+
 
 def dense_operator(ctx, A):
     """`Matrix{Float64}` operator.  With a communicator, `A` is the full matrix and only this rank's

@@ -11,6 +11,7 @@
 #include "pcga.hpp"
 #include "pointcov.hpp"
 #include "fftrf_points.hpp"
+#include "cg_state.hpp"
 
 using namespace gsi;
 
@@ -1511,6 +1512,112 @@ int gsi_op_solve_pcg_host(gsi_ctx* ctx, const gsi_op* op, const double* diag, co
       throw;
     }
     be->download2d(X, ldx, Xd.p, A.n, A.n, b);
+  });
+}
+
+// ---- log-determinants by stochastic Lanczos quadrature: the traced solve, the quadrature alone, draws of N(0, P) and
+//      log det P ----
+int gsi_op_solve_trace(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, const gsi_mat* B, gsi_mat* X,
+                       int64_t nquad, int64_t qmax, double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters,
+                       double* quad_out) {
+  return guarded([&] {
+    if (info) for (int i = 0; i < 7; ++i) info[i] = 0;
+    REQUIRE(B && X, "gsi_op_solve_trace: B or X is NULL");
+    const int64_t b = B->cols;
+    if (quad_out) for (int64_t j = 0; j < 2 * b; ++j) quad_out[j] = 0.0;
+    if (pc) check_pcg_args(ctx, op, diag, pc, b, tol, maxiter, info);
+    else check_solve_args(ctx, op, diag, b, tol, maxiter, info);
+    const Operator& A = op->op;
+    REQUIRE(B->ctx == ctx && X->ctx == ctx, "gsi_op_solve_trace: B or X belongs to another context");
+    REQUIRE(B->rows == A.n, "gsi_op_solve_trace: B must have size(A, 1) rows");
+    REQUIRE(X->rows == A.n && X->cols == b, "gsi_op_solve_trace: X must have the shape of B");
+    REQUIRE(X != B && X->buf.p != B->buf.p, "gsi_op_solve_trace: X must not be B");
+    REQUIRE(qmax >= 1, "gsi_op_solve_trace: qmax must be at least 1");
+    REQUIRE(qmax <= 4096, "gsi_op_solve_trace: qmax exceeds 4096");
+    REQUIRE(nquad >= 0 && nquad <= b, "gsi_op_solve_trace: nquad must lie in 0 .. the columns of B");
+    Backend* be = ctx->c.be.get();
+    CgTrace trace;
+    trace.qmax = qmax;
+    trace.tr = Buf(be, cgst::trace_doubles(b, qmax));
+    std::vector<int64_t> its((size_t)b, 0);
+    Buf dd;
+    if (diag) {
+      dd = Buf(be, (size_t)A.n);
+      be->upload2d(dd.p, A.n, diag, A.n, A.n, 1);
+    }
+    int64_t bcol = 0, bkind = 0;
+    if (pc) {
+      const BlockPcgInfo r = block_pcg(A, diag ? dd.p : nullptr, pc->pc, B->buf.p, X->buf.p, b, tol, maxiter, relres, its.data(),
+                                       &trace);
+      if (info) { info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column;
+                  info[4] = r.breakdown_kind; info[5] = r.K; }
+      bcol = r.breakdown_column; bkind = r.breakdown_kind;
+    } else {
+      const BlockCgInfo r = block_cg(A, diag ? dd.p : nullptr, B->buf.p, X->buf.p, b, tol, maxiter, relres, its.data(), &trace);
+      if (info) { info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column;
+                  info[4] = r.breakdown_column ? 1 : 0; }
+      bcol = r.breakdown_column; bkind = 1;
+    }
+    if (info) info[6] = trace.truncated;
+    if (iters) for (int64_t j = 0; j < b; ++j) iters[j] = its[(size_t)j];
+    check_async_errors(ctx->c);
+    if (bcol != 0)
+      throw Error(GSI_ERR_NOT_POSDEF, std::string("traced conjugate gradients: ") +
+                                          (bkind == 2 ? "r'z is not positive and finite (the preconditioner is not positive definite)"
+                                                      : "A + diag is not positive definite along the search direction") +
+                                          " of column " + std::to_string(bcol));
+    if (quad_out) {
+      double* tr = trace.tr.p;
+      for (int64_t j = 0; j < b - nquad; ++j) its[(size_t)j] = 0;          // the data columns: no quadrature, 0
+      if (nquad > 0)
+        slq_quadrature(ctx->c, cgst::trace_alpha(tr, b, qmax), cgst::trace_beta(tr, b, qmax), its.data(),
+                       cgst::trace_rho0(tr, b, qmax), qmax, b, quad_out);
+      be->download2d(quad_out + b, b, cgst::trace_rho0(tr, b, qmax), b, b, 1);
+      check_async_errors(ctx->c);
+    }
+  });
+}
+
+int gsi_slq_quadrature(gsi_ctx* ctx, const double* alpha, const double* beta, const int64_t* steps, const double* rho0,
+                       int64_t qmax, int64_t b, double* out) {
+  return guarded([&] {
+    REQUIRE(ctx && alpha && beta && steps && rho0 && out, "gsi_slq_quadrature: NULL argument");
+    try {
+      slq_quadrature_check(qmax, b);
+    } catch (const Error& e) {
+      throw Error(e.code, std::string("gsi_slq_quadrature: ") + e.what());
+    }
+    for (int64_t j = 0; j < b; ++j)
+      REQUIRE(steps[j] >= 0 && steps[j] <= qmax, "gsi_slq_quadrature: steps must lie in 0 .. qmax");
+    Backend* be = ctx->c.be.get();
+    const int64_t nb = qmax * b;
+    Buf ad(be, (size_t)nb), bd(be, (size_t)nb), rd(be, (size_t)b);
+    be->upload2d(ad.p, nb, alpha, nb, nb, 1);
+    be->upload2d(bd.p, nb, beta, nb, nb, 1);
+    be->upload2d(rd.p, b, rho0, b, b, 1);
+    slq_quadrature(ctx->c, ad.p, bd.p, steps, rd.p, qmax, b, out);
+    check_async_errors(ctx->c);
+  });
+}
+
+int gsi_precond_sample(gsi_ctx* ctx, const gsi_precond* pc, const gsi_mat* G1, const gsi_mat* G2, gsi_mat* Zout) {
+  return guarded([&] {
+    REQUIRE(ctx && pc && G1 && G2 && Zout, "gsi_precond_sample: NULL argument");
+    REQUIRE(pc->ctx == ctx, "gsi_precond_sample: pc belongs to another context");
+    REQUIRE(G1->ctx == ctx && G2->ctx == ctx && Zout->ctx == ctx, "gsi_precond_sample: G1, G2 or Zout belongs to another context");
+    REQUIRE(G2->rows == pc->pc.n && G2->cols >= 1, "gsi_precond_sample: G2 must have the preconditioner's rows");
+    REQUIRE(G1->rows == pc->pc.K && G1->cols == G2->cols, "gsi_precond_sample: G1 must be K x the columns of G2");
+    REQUIRE(Zout->rows == G2->rows && Zout->cols == G2->cols, "gsi_precond_sample: Zout must have the shape of G2");
+    REQUIRE(Zout != G2 && Zout->buf.p != G2->buf.p && Zout != G1 && Zout->buf.p != G1->buf.p,
+            "gsi_precond_sample: Zout must not be G1 or G2");
+    precond_sample(pc->pc, G1->buf.p, G2->buf.p, G2->cols, Zout->buf.p);
+    check_async_errors(ctx->c);
+  });
+}
+int gsi_precond_logdet(const gsi_precond* pc, double* logdet_out) {
+  return guarded([&] {
+    REQUIRE(pc && logdet_out, "gsi_precond_logdet: NULL argument");
+    *logdet_out = pc->pc.logdet;
   });
 }
 

@@ -469,6 +469,32 @@ class Backend {
   virtual int precond_rows(int64_t n, double* e, double* sqe) { (void)n; (void)e; (void)sqe; return 0; }
   virtual int add_identity(double* C, int64_t K) { (void)C; (void)K; return 0; }
 
+  // ---- the coefficient trace of the two solvers above and its Gauss quadrature (cg_state.hpp's trace_col, slq_state.hpp;
+  //      DESIGN.md section 4.6k).  work: the solver's `work` (its state block in front); tr: cgst::trace_doubles(b, qmax)
+  //      doubles in backend memory.  Called behind block_cg_begin / block_pcg_begin and behind every block_cg_step /
+  //      block_pcg_step of a traced solve.  A backend with the fused solvers has these; the default is never reached.
+  virtual void cg_trace_begin(const double* work, double* tr, int64_t qmax) {
+    (void)work; (void)tr; (void)qmax;
+    throw Error(1 /* GSI_ERR_ARG */, "cg_trace: not available on this backend");
+  }
+  virtual void cg_trace_step(const double* work, double* tr, int64_t qmax) {
+    (void)work; (void)tr; (void)qmax;
+    throw Error(1 /* GSI_ERR_ARG */, "cg_trace: not available on this backend");
+  }
+  // out[j] = rho0[j] * e1' log(T_j) e1 from steps[j] (a whole number in a double) coefficients of column j; alpha, beta
+  // (qmax x b, step k of column j at k * b + j), steps, rho0, out (b) and work (3 * qmax * b) in backend memory.
+  // 1, or 0: "not mine" (the caller runs slq_state.hpp on the host).
+  virtual int slq_quadrature(const double* alpha, const double* beta, const double* steps, const double* rho0, int64_t qmax,
+                             int64_t b, double* work, double* out) {
+    (void)alpha; (void)beta; (void)steps; (void)rho0; (void)qmax; (void)b; (void)work; (void)out;
+    return 0;
+  }
+  // Zout = Y ./ e + G2 ./ sqrt(e) on n x b panels (ld n).  1, or 0: "not mine" (the caller forms it on the host).
+  virtual int precond_sample_rows(int64_t n, int64_t b, const double* e, const double* Y, const double* G2, double* Zout) {
+    (void)n; (void)b; (void)e; (void)Y; (void)G2; (void)Zout;
+    return 0;
+  }
+
   // ---- diagonal-pivoted Cholesky of a covariance read by entries (pchol_state.hpp).  Where
   //      A(i, p) comes from: form 1 -- data = the stored n x n matrix (ld); 2 -- data = the gx * gy table over grid offsets;
   //      3 -- data = the d x n coordinates of a scattered-point covariance with the parameters below.

@@ -11,15 +11,20 @@
 namespace gsi {
 
 // R and P hold B, X is zero (n x b, ld n); mul(P, Q): Q = A P on the whole panel.  st: cgst::state_doubles(b) doubles,
-// left as the device path's state block would be.  Returns the operator products performed.
+// left as the device path's state block would be.  Returns the operator products performed.  trace (HOST,
+// cgst::trace_doubles(b, qmax) doubles, or null): the coefficient trace of cg_state.hpp's trace_col.
 template <class Mul>
 int64_t block_cg_composed(Backend* be, Mul&& mul, int64_t n, int64_t b, const double* diag, const double* B, double* X,
-                          double* R, double* P, double* Q, double tol, int64_t maxiter, std::vector<double>& st) {
+                          double* R, double* P, double* Q, double tol, int64_t maxiter, std::vector<double>& st,
+                          double* trace = nullptr, int64_t qmax = 0) {
   using namespace cgst;
   st.assign(state_doubles(b), 0.0);
   double* s = st.data();
   begin(s, b, tol, maxiter);
-  for (int64_t j = 0; j < b; ++j) begin_col(s, j, be->dot(n, B + j * n, B + j * n));
+  for (int64_t j = 0; j < b; ++j) {
+    begin_col(s, j, be->dot(n, B + j * n, B + j * n));
+    if (trace) trace_begin_col(s, j, trace, qmax);
+  }
   after_iter(s);
   int64_t products = 0;
   while (s[H_ACTIVE] > 0.0) {
@@ -42,6 +47,7 @@ int64_t block_cg_composed(Backend* be, Mul&& mul, int64_t n, int64_t b, const do
         rr = be->dot(n, r, r);
       }
       after_rr(s, j, rr);
+      if (trace) trace_col(s, j, trace, qmax);
       if (colv(s, UPDP, j) != 0.0) {                            // p = r + beta p
         be->scal(n, colv(s, BETA, j), p);
         be->axpy(n, 1.0, r, p);

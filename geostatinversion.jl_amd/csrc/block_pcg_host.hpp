@@ -20,17 +20,21 @@ inline void precond_apply_composed(Backend* be, int64_t n, int64_t K, const doub
 
 // R holds B, X is zero (n x b, ld n); mul(P, Q): Q = A P on the whole panel; Zp (n x b) and S (K x b): scratch.
 // st: cgst::pcg_state_doubles(b) doubles, left as the device path's state block would be.  Returns the operator products.
+// trace (HOST, cgst::trace_doubles(b, qmax) doubles, or null): the coefficient trace of cg_state.hpp's trace_col.
 template <class Mul>
 int64_t block_pcg_composed(Backend* be, Mul&& mul, int64_t n, int64_t b, int64_t K, const double* diag, const double* e,
                            const double* W, const double* B, double* X, double* R, double* P, double* Q, double* Zp, double* S,
-                           double tol, int64_t maxiter, std::vector<double>& st) {
+                           double tol, int64_t maxiter, std::vector<double>& st, double* trace = nullptr, int64_t qmax = 0) {
   using namespace cgst;
   st.assign(pcg_state_doubles(b), 0.0);
   double* s = st.data();
   begin(s, b, tol, maxiter);
   precond_apply_composed(be, n, K, e, W, B, b, S, Zp);
   be->copy2d(P, n, Zp, n, n, b);
-  for (int64_t j = 0; j < b; ++j) pcg_begin_col(s, j, be->dot(n, B + j * n, B + j * n), be->dot(n, B + j * n, Zp + j * n));
+  for (int64_t j = 0; j < b; ++j) {
+    pcg_begin_col(s, j, be->dot(n, B + j * n, B + j * n), be->dot(n, B + j * n, Zp + j * n));
+    if (trace) trace_begin_col(s, j, trace, qmax);
+  }
   after_iter(s);
   int64_t products = 0;
   while (s[H_ACTIVE] > 0.0) {
@@ -61,6 +65,7 @@ int64_t block_pcg_composed(Backend* be, Mul&& mul, int64_t n, int64_t b, int64_t
       double* p = P + j * n;
       const double* z = Zp + j * n;
       pcg_after_rz(s, j, colv(s, UPDP, j) != 0.0 ? be->dot(n, R + j * n, z) : 0.0);
+      if (trace) trace_col(s, j, trace, qmax);
       if (colv(s, UPDP, j) != 0.0) {                            // p = z + beta p
         be->scal(n, colv(s, BETA, j), p);
         be->axpy(n, 1.0, z, p);

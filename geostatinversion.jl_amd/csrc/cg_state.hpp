@@ -200,4 +200,28 @@ GSI_HD inline double pcg_relres(const double* s, int64_t j) {
   return bn > 0.0 ? std::sqrt(colv(s, RR, j)) / bn : (bn == 0.0 ? 0.0 : bn);
 }
 
+// ---- the coefficient trace: alpha_k and beta_k of every column, kept for slq_state.hpp's
+//      quadrature.  They are the Lanczos tridiagonal of P^-1/2 (A + D) P^-1/2 started at P^-1/2 b_j (P = I for plain CG).
+//      tr = [alpha (qmax x b) | beta (qmax x b) | rho0 (b)], step k of column j at k * b + j: column-interleaved, so that
+//      one thread per column reads and writes neighbouring words.  The trace only reads the state: a traced solve returns
+//      the bits of an untraced one.
+GSI_HD inline size_t trace_doubles(int64_t b, int64_t qmax) { return (size_t)(2 * qmax + 1) * (size_t)b; }
+GSI_HD inline double* trace_alpha(double* tr, int64_t b, int64_t qmax) { (void)b; (void)qmax; return tr; }
+GSI_HD inline double* trace_beta(double* tr, int64_t b, int64_t qmax) { return tr + qmax * b; }
+GSI_HD inline double* trace_rho0(double* tr, int64_t b, int64_t qmax) { return tr + 2 * qmax * b; }
+// once per column, after begin_col (rho0 = b'b) or pcg_begin_col (rho0 = r0'z0); 0 for a zero column
+GSI_HD inline void trace_begin_col(const double* s, int64_t j, double* tr, int64_t qmax) {
+  const int64_t b = (int64_t)s[H_NCOLS];
+  trace_rho0(tr, b, qmax)[j] = colv(s, RHO, j);
+}
+// once per column and iteration, after after_rr (CG) or pcg_after_rz (PCG): ITERS has been advanced where APPLY is set
+GSI_HD inline void trace_col(const double* s, int64_t j, double* tr, int64_t qmax) {
+  if (colv(s, APPLY, j) == 0.0) return;
+  const int64_t b = (int64_t)s[H_NCOLS];
+  const int64_t k = (int64_t)colv(s, ITERS, j) - 1;
+  if (k < 0 || k >= qmax) return;
+  trace_alpha(tr, b, qmax)[k * b + j] = colv(s, ALPHA, j);
+  if (colv(s, UPDP, j) != 0.0) trace_beta(tr, b, qmax)[k * b + j] = colv(s, BETA, j);
+}
+
 }}  // namespace gsi::cgst

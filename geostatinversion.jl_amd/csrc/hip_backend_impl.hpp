@@ -255,6 +255,11 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
                       double* X, double* R, double* P, double* S, double* Y, double* work) override;
   int precond_rows(int64_t n, double* e, double* sqe) override;
   int add_identity(double* C, int64_t K) override;
+  void cg_trace_begin(const double* work, double* tr, int64_t qmax) override;
+  void cg_trace_step(const double* work, double* tr, int64_t qmax) override;
+  int slq_quadrature(const double* alpha, const double* beta, const double* steps, const double* rho0, int64_t qmax, int64_t b,
+                     double* work, double* out) override;
+  int precond_sample_rows(int64_t n, int64_t b, const double* e, const double* Y, const double* G2, double* Zout) override;
   size_t pchol_work_doubles(const PcholSource& a, int64_t n, int64_t K) override { return hipk::pchol_work_doubles(a.form, n, K); }
   void pchol_begin(const PcholSource& a, int64_t n, int64_t K, double tol, const double* L, int64_t ldl, double* d,
                    double* work) override;

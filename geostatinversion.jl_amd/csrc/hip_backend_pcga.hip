@@ -117,6 +117,30 @@ int HipBackend::add_identity(double* C, int64_t K) {
   check_launch("add_identity");
   return 1;
 }
+// The coefficient trace and its quadrature (block_slq.hip)
+void HipBackend::cg_trace_begin(const double* work, double* tr, int64_t qmax) {
+  bind();
+  hipk::slq_trace_begin(st_, work, tr, qmax);
+  check_launch("cg_trace_begin");
+}
+void HipBackend::cg_trace_step(const double* work, double* tr, int64_t qmax) {
+  bind();
+  hipk::slq_trace_step(st_, work, tr, qmax);
+  check_launch("cg_trace_step");
+}
+int HipBackend::slq_quadrature(const double* alpha, const double* beta, const double* steps, const double* rho0, int64_t qmax,
+                               int64_t b, double* work, double* out) {
+  bind();
+  hipk::slq_quadrature(st_, alpha, beta, steps, rho0, qmax, b, work, out);
+  check_launch("slq_quadrature");
+  return 1;
+}
+int HipBackend::precond_sample_rows(int64_t n, int64_t b, const double* e, const double* Y, const double* G2, double* Zout) {
+  bind();
+  hipk::slq_sample_rows(st_, n, b, e, Y, G2, Zout);
+  check_launch("precond_sample_rows");
+  return 1;
+}
 // Diagonal-pivoted Cholesky (pivoted_chol.hip).  The scattered-point form keeps the points as the
 // generator's pre-scaled 32-byte records inside `work`, made once by pchol_begin.
 static hipk::PcholCol pchol_col(const Backend::PcholSource& a, double* work, int64_t n, int64_t K) {

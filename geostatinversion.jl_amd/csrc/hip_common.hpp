@@ -258,6 +258,16 @@ void block_pcg_step_p(hipStream_t st, int64_t n, int64_t b, const double* e, con
 void pcg_precond_rows(hipStream_t st, int64_t n, double* e, double* sqe);
 void pcg_add_identity(hipStream_t st, double* C, int64_t K);
 
+// ---- block_slq.hip: the coefficient trace of the two solvers above and its Gauss quadrature (cg_state.hpp's trace_col,
+//      slq_state.hpp).  state: the solver's state block (the front of its `work`); tr:
+//      cgst::trace_doubles(b, qmax) doubles; alpha, beta, work: column-interleaved, work 3 * qmax * b doubles ----
+void slq_trace_begin(hipStream_t st, const double* state, double* tr, int64_t qmax);
+void slq_trace_step(hipStream_t st, const double* state, double* tr, int64_t qmax);
+void slq_quadrature(hipStream_t st, const double* alpha, const double* beta, const double* steps, const double* rho0,
+                    int64_t qmax, int64_t b, double* work, double* out);
+// Zout = Y ./ e + G2 ./ sqrt(e), n x b panels (ld n)
+void slq_sample_rows(hipStream_t st, int64_t n, int64_t b, const double* e, const double* Y, const double* G2, double* Zout);
+
 // ---- pivoted_chol.hip: diagonal-pivoted Cholesky of a covariance read by entries (pchol_state.hpp) ----
 // where A(i, p) comes from.  form 1: a = the stored matrix (ld); 2: a = the nx * ny table over grid offsets; 3: a = the points
 // as the 32-byte records of pointcov_pad_points, entries by the generator of pointcov_gen.hpp

@@ -15,6 +15,7 @@
 #include "block_cg_host.hpp"
 #include "block_pcg_host.hpp"
 #include "pivoted_chol_host.hpp"
+#include "slq_state.hpp"
 #include "pointcov.hpp"
 #include <algorithm>
 #include <cmath>
@@ -1194,8 +1195,17 @@ void block_cg_check(const Operator& A, int64_t b, double tol, int64_t maxiter) {
   if (!(tol > 0.0 && tol < 1.0)) throw Error(GSI_ERR_ARG, "block_cg: tol must lie in (0, 1)");
   if (maxiter < 1) throw Error(GSI_ERR_ARG, "block_cg: maxiter must be at least 1");
 }
+// the composed paths keep the trace on the host: it goes to the caller's buffer at the end; the columns beyond qmax
+static void trace_finish(Backend* be, CgTrace* trace, const std::vector<double>& host_trace, const double* st, int64_t b) {
+  if (!host_trace.empty()) be->upload2d(trace->tr.p, (int64_t)host_trace.size(), host_trace.data(), (int64_t)host_trace.size(),
+                                        (int64_t)host_trace.size(), 1);
+  trace->truncated = 0;
+  for (int64_t j = 0; j < b; ++j)
+    if ((int64_t)cgst::colv(st, cgst::ITERS, j) > trace->qmax) ++trace->truncated;
+}
+
 BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, double* X, int64_t b, double tol, int64_t maxiter,
-                     double* relres, int64_t* iters) {
+                     double* relres, int64_t* iters, CgTrace* trace) {
   using namespace cgst;
   block_cg_check(A, b, tol, maxiter);
   Backend* be = A.ctx->be.get();
@@ -1208,7 +1218,8 @@ BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, dou
   be->copy2d(R.p, n, B, n, n, b);
   be->copy2d(P.p, n, B, n, n, b);
   be->fill_zero(X, (size_t)n * b);
-  std::vector<double> st(state_doubles(b), 0.0);
+  std::vector<double> st(state_doubles(b), 0.0), host_trace;
+  if (trace) be->fill_zero(trace->tr.p, trace_doubles(b, trace->qmax));
   if (wd) {
     int64_t poll = 4;
     if (const char* e = getenv("GSI_CG_POLL")) poll = std::max<int64_t>(1, atoll(e));
@@ -1217,6 +1228,7 @@ BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, dou
     {
       ScopedPhase ph(be, PH_OTHER);
       be->block_cg_begin(n, b, B, tol, maxiter, work.p);
+      if (trace) be->cg_trace_begin(work.p, trace->tr.p, trace->qmax);
     }
     double hdr[H_COUNT];
     be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
@@ -1227,6 +1239,7 @@ BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, dou
         op_mul(A, P.p, n, b, Q.p, n);
         ScopedPhase ph(be, PH_OTHER);
         be->block_cg_step(n, b, Q.p, diag, X, R.p, P.p, work.p);
+        if (trace) be->cg_trace_step(work.p, trace->tr.p, trace->qmax);
       }
       enq += burst;
       be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
@@ -1234,9 +1247,11 @@ BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, dou
     info.products = enq;
     be->download2d(st.data(), (int64_t)st.size(), work.p, (int64_t)st.size(), (int64_t)st.size(), 1);
   } else {
+    if (trace) host_trace.assign(trace_doubles(b, trace->qmax), 0.0);
     info.products = block_cg_composed(be, [&](const double* p, double* q) { op_mul(A, p, n, b, q, n); }, n, b, diag, B, X, R.p,
-                                      P.p, Q.p, tol, maxiter, st);
+                                      P.p, Q.p, tol, maxiter, st, trace ? host_trace.data() : nullptr, trace ? trace->qmax : 0);
   }
+  if (trace) trace_finish(be, trace, host_trace, st.data(), b);
   info.converged = (int64_t)st[H_CONVERGED];
   info.breakdown_column = (int64_t)st[H_BREAKDOWN];
   for (int64_t j = 0; j < b; ++j) {
@@ -1310,6 +1325,18 @@ void precond_lowrank_build(LowRankPrecond& pc, Context& c, const double* Z, int6
     be->upload2d(C.p, K, ch.data(), K, K, K);
   }
   be->chol_upper(C.p, K);
+  // R and log det P = sum log(d + shift) + 2 sum log R_kk stay on the host (K^2 numbers, read by precond_sample)
+  pc.R.assign((size_t)K * K, 0.0);
+  be->download2d(pc.R.data(), K, C.p, K, K, K);
+  {
+    long double acc = 0.0L;
+    for (int64_t i = 0; i < n; ++i) acc += std::log((long double)((diag ? diag[i] : 0.0) + shift));
+    for (int64_t k = 0; k < K; ++k) {
+      acc += 2.0L * std::log((long double)pc.R[(size_t)(k + k * K)]);
+      for (int64_t i = k + 1; i < K; ++i) pc.R[(size_t)(i + k * K)] = 0.0;
+    }
+    pc.logdet = (double)acc;
+  }
   pc.W = Buf(be, (size_t)n * K);                                // W = diag(e) Z R^-1
   if (zh.empty()) {
     be->scale_rows(n, K, pc.e.p, Z, n, pc.W.p, n);
@@ -1328,6 +1355,55 @@ void precond_apply(const LowRankPrecond& pc, const double* R, int64_t b, double*
   precond_apply_composed(be, pc.n, pc.K, pc.e.p, pc.W.p, R, b, S.p, Zout);
 }
 
+void precond_sample(const LowRankPrecond& pc, const double* G1, const double* G2, int64_t b, double* Zout) {
+  Backend* be = pc.ctx->be.get();
+  const int64_t n = pc.n, K = pc.K;
+  Buf Rd(be, (size_t)K * K), T(be, (size_t)K * b), Y(be, (size_t)n * b);
+  be->upload2d(Rd.p, K, pc.R.data(), K, K, K);
+  be->gemm_nn(K, b, K, 1.0, Rd.p, K, G1, K, 0.0, T.p, K);        // T = R G1
+  be->gemm_nn(n, b, K, 1.0, pc.W.p, n, T.p, K, 0.0, Y.p, n);     // Y = W T = diag(e) Z G1
+  if (!be->precond_sample_rows(n, b, pc.e.p, Y.p, G2, Zout)) {
+    std::vector<double> eh((size_t)n), yh((size_t)n * b), gh((size_t)n * b);
+    be->download2d(eh.data(), n, pc.e.p, n, n, 1);
+    be->download2d(yh.data(), n, Y.p, n, n, b);
+    be->download2d(gh.data(), n, G2, n, n, b);
+    for (int64_t j = 0; j < b; ++j)
+      for (int64_t i = 0; i < n; ++i)
+        yh[(size_t)(i + j * n)] = yh[(size_t)(i + j * n)] / eh[(size_t)i] + gh[(size_t)(i + j * n)] / std::sqrt(eh[(size_t)i]);
+    be->upload2d(Zout, n, yh.data(), n, n, b);
+  }
+}
+
+// ---- the Gauss quadrature of a coefficient trace (pipeline.hpp; slq_state.hpp) ----
+void slq_quadrature_check(int64_t qmax, int64_t b) {
+  if (qmax < 1) throw Error(GSI_ERR_ARG, "slq: qmax must be at least 1");
+  if (qmax > slq::QMAX_LIMIT) throw Error(GSI_ERR_ARG, "slq: qmax exceeds " + std::to_string(slq::QMAX_LIMIT));
+  if (b < 1) throw Error(GSI_ERR_ARG, "slq: b must be at least 1");
+}
+void slq_quadrature(Context& c, const double* alpha, const double* beta, const int64_t* steps, const double* rho0, int64_t qmax,
+                    int64_t b, double* out) {
+  slq_quadrature_check(qmax, b);
+  Backend* be = c.be.get();
+  std::vector<double> sh((size_t)b);
+  for (int64_t j = 0; j < b; ++j) sh[(size_t)j] = (double)std::min<int64_t>(std::max<int64_t>(steps[j], 0), qmax);
+  {
+    Buf sd(be, (size_t)b), od(be, (size_t)b), work(be, slq::work_doubles(b, qmax));
+    be->upload2d(sd.p, b, sh.data(), b, b, 1);
+    ScopedPhase ph(be, PH_OTHER);
+    if (be->slq_quadrature(alpha, beta, sd.p, rho0, qmax, b, work.p, od.p)) {
+      be->download2d(out, b, od.p, b, b, 1);
+      return;
+    }
+  }
+  std::vector<double> ah((size_t)qmax * b), bh((size_t)qmax * b), rh((size_t)b), work(slq::work_doubles(b, qmax));
+  be->download2d(ah.data(), qmax * b, alpha, qmax * b, qmax * b, 1);
+  be->download2d(bh.data(), qmax * b, beta, qmax * b, qmax * b, 1);
+  be->download2d(rh.data(), b, rho0, b, b, 1);
+  for (int64_t j = 0; j < b; ++j)
+    out[j] = slq::quadrature_log(ah.data() + j, bh.data() + j, (int64_t)sh[(size_t)j], rh[(size_t)j], b, work.data() + j,
+                                 work.data() + qmax * b + j, work.data() + 2 * qmax * b + j);
+}
+
 void block_pcg_check(const Operator& A, const LowRankPrecond& pc, int64_t b, double tol, int64_t maxiter) {
   block_cg_check(A, b, tol, maxiter);
   if (pc.ctx != A.ctx) throw Error(GSI_ERR_ARG, "block_pcg: pc belongs to another context");
@@ -1335,7 +1411,7 @@ void block_pcg_check(const Operator& A, const LowRankPrecond& pc, int64_t b, dou
                                                 std::to_string(A.n));
 }
 BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPrecond& pc, const double* B, double* X, int64_t b,
-                       double tol, int64_t maxiter, double* relres, int64_t* iters) {
+                       double tol, int64_t maxiter, double* relres, int64_t* iters, CgTrace* trace) {
   using namespace cgst;
   block_pcg_check(A, pc, b, tol, maxiter);
   Backend* be = A.ctx->be.get();
@@ -1348,7 +1424,8 @@ BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPreco
   Buf R(be, (size_t)n * b), P(be, (size_t)n * b), Q(be, (size_t)n * b), Y(be, (size_t)n * b), S(be, (size_t)K * b);
   be->copy2d(R.p, n, B, n, n, b);
   be->fill_zero(X, (size_t)n * b);
-  std::vector<double> st(pcg_state_doubles(b), 0.0);
+  std::vector<double> st(pcg_state_doubles(b), 0.0), host_trace;
+  if (trace) be->fill_zero(trace->tr.p, trace_doubles(b, trace->qmax));
   if (wd) {
     int64_t poll = 4;
     if (const char* e = getenv("GSI_CG_POLL")) poll = std::max<int64_t>(1, atoll(e));
@@ -1357,6 +1434,7 @@ BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPreco
     {
       ScopedPhase ph(be, PH_OTHER);
       be->block_pcg_begin(n, b, K, B, pc.e.p, pc.W.p, S.p, Y.p, P.p, tol, maxiter, work.p);
+      if (trace) be->cg_trace_begin(work.p, trace->tr.p, trace->qmax);
     }
     double hdr[H_COUNT];
     be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
@@ -1367,6 +1445,7 @@ BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPreco
         op_mul(A, P.p, n, b, Q.p, n);
         ScopedPhase ph(be, PH_OTHER);
         be->block_pcg_step(n, b, K, Q.p, diag, pc.e.p, pc.W.p, X, R.p, P.p, S.p, Y.p, work.p);
+        if (trace) be->cg_trace_step(work.p, trace->tr.p, trace->qmax);
       }
       enq += burst;
       be->download2d(hdr, H_COUNT, work.p, H_COUNT, H_COUNT, 1);
@@ -1374,9 +1453,12 @@ BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPreco
     info.products = enq;
     be->download2d(st.data(), (int64_t)st.size(), work.p, (int64_t)st.size(), (int64_t)st.size(), 1);
   } else {
+    if (trace) host_trace.assign(trace_doubles(b, trace->qmax), 0.0);
     info.products = block_pcg_composed(be, [&](const double* p, double* q) { op_mul(A, p, n, b, q, n); }, n, b, K, diag,
-                                       pc.e.p, pc.W.p, B, X, R.p, P.p, Q.p, Y.p, S.p, tol, maxiter, st);
+                                       pc.e.p, pc.W.p, B, X, R.p, P.p, Q.p, Y.p, S.p, tol, maxiter, st,
+                                       trace ? host_trace.data() : nullptr, trace ? trace->qmax : 0);
   }
+  if (trace) trace_finish(be, trace, host_trace, st.data(), b);
   info.converged = (int64_t)st[H_CONVERGED];
   info.breakdown_column = (int64_t)st[H_BREAKDOWN];
   if (info.breakdown_column != 0) info.breakdown_kind = (int64_t)colv(st.data(), BKIND, info.breakdown_column - 1);

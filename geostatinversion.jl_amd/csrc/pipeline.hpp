@@ -157,17 +157,31 @@ int64_t lowrank_solve(const Operator& A, const double* b, double* x);
 // iterations (read per call).  Path 3: block_cg_host.hpp -- when the backend has no such kernels, or GSI_CG_COMPOSED=1
 // (read per call).  Workspace: three n x b panels, the state block and the partial sums.
 struct BlockCgInfo { int64_t products = 0, converged = 0, path = 0, breakdown_column = 0; };
+// The traced form of block_cg / block_pcg: tr, cgst::trace_doubles(b, qmax) doubles in backend
+// memory made by the caller, receives alpha_k and beta_k of the first qmax iterations of every column and the columns'
+// rho0 (cg_state.hpp's trace_col).  On the fused path it costs one single-block launch per iteration, which only reads the
+// solver's state; on the composed path the trace is kept on the host and uploaded at the end.  X, relres and iters are the
+// bits of the untraced solve.  truncated: the columns that went beyond qmax iterations.
+struct CgTrace {
+  int64_t qmax = 0;
+  Buf tr;
+  int64_t truncated = 0;
+};
 // what block_cg refuses (GSI_ERR_ARG naming the argument), for callers that allocate before they call it
 void block_cg_check(const Operator& A, int64_t b, double tol, int64_t maxiter);
 BlockCgInfo block_cg(const Operator& A, const double* diag, const double* B, double* X, int64_t b, double tol, int64_t maxiter,
-                     double* relres, int64_t* iters);
+                     double* relres, int64_t* iters, CgTrace* trace = nullptr);
 // ---- the same solve preconditioned by P = Z Z' + diag(d + shift).  P^-1 = diag(e) - W W' exactly,
-//      with e = 1 / (d + shift), R'R = I + Z' diag(e) Z and W = diag(e) Z R^-1: the handle keeps e (n) and W (n x K) only.
+//      with e = 1 / (d + shift), R'R = I + Z' diag(e) Z and W = diag(e) Z R^-1: the handle keeps e (n) and W (n x K) in
+//      backend memory, and on the host R (K x K, ld K, zeros below the diagonal) and log det P = sum log(d + shift) +
+//      2 sum log R_kk.
 struct LowRankPrecond {
   Context* ctx = nullptr;
   int64_t n = 0, K = 0;
   double dmin = 0.0, dmax = 0.0;       // min and max of d + shift
+  double logdet = 0.0;
   Buf e, W;
+  std::vector<double> R;
 };
 // what precond_lowrank_build refuses (GSI_ERR_ARG naming the argument), before anything is allocated; dmin / dmax filled
 void precond_lowrank_check(Context& c, int64_t n, int64_t zcols, int64_t K, const double* diag, double shift, double* dmin,
@@ -178,11 +192,21 @@ void precond_lowrank_build(LowRankPrecond& pc, Context& c, const double* Z, int6
                            double shift);
 // Zout (n x b) = P^-1 R (n x b), both in backend memory, ld n
 void precond_apply(const LowRankPrecond& pc, const double* R, int64_t b, double* Zout);
+// Zout (n x b) = (W (R G1)) ./ e + G2 ./ sqrt(e) = Z G1 + sqrt(d + shift) .* G2 for G1 (K x b, ld K) and G2 (n x b, ld n),
+// all in backend memory: with standard normals in G1 and G2, the columns of Zout are draws of N(0, P).  Zout is neither G1 nor G2.
+void precond_sample(const LowRankPrecond& pc, const double* G1, const double* G2, int64_t b, double* Zout);
 // breakdown_kind: 1 = p'(A + D)p, 2 = r'z was not positive and finite.  Paths and GSI_CG_POLL / GSI_CG_COMPOSED as block_cg.
 struct BlockPcgInfo { int64_t products = 0, converged = 0, path = 0, breakdown_column = 0, breakdown_kind = 0, K = 0; };
 void block_pcg_check(const Operator& A, const LowRankPrecond& pc, int64_t b, double tol, int64_t maxiter);
 BlockPcgInfo block_pcg(const Operator& A, const double* diag, const LowRankPrecond& pc, const double* B, double* X, int64_t b,
-                       double tol, int64_t maxiter, double* relres, int64_t* iters);
+                       double tol, int64_t maxiter, double* relres, int64_t* iters, CgTrace* trace = nullptr);
+// ---- the Gauss quadrature of a coefficient trace (slq_state.hpp): out[j] (HOST, b) = rho0_j e1'
+//      log(T_j) e1 from the first steps[j] (HOST, b; 0 .. qmax) coefficients of column j.  alpha, beta (qmax x b, step k of
+//      column j at k * b + j) and rho0 (b) in backend memory.  The backend's kernel (one thread per column), or the same
+//      function on the host where the backend has none.
+void slq_quadrature_check(int64_t qmax, int64_t b);
+void slq_quadrature(Context& c, const double* alpha, const double* beta, const int64_t* steps, const double* rho0, int64_t qmax,
+                    int64_t b, double* out);
 // ---- diagonal-pivoted Cholesky of a covariance read by entries (pchol_state.hpp): L L' ~ A from K
 //      columns of A, without an operator product.  A: OP_DENSE (one rank, all rows resident, nothing pending),
 //      OP_GRIDCOV_IMPLICIT or OP_POINTCOV, square.  L: n x >= K in backend memory, ld n; columns rank .. K - 1 are zeros.

@@ -43,6 +43,37 @@ class Preconditioner(_Handle):
     def __exit__(self, *exc):
         self.close()
 
+    @property
+    def logdet(self):
+        """log det P = sum log(d + shift) + 2 sum log R_kk (`gsi_precond_logdet`), computed when the handle was made."""
+        v = C.c_double()
+        L.check(self.ctx.lib.gsi_precond_logdet(self.h, C.byref(v)), self.ctx.lib)
+        return float(v.value)
+
+    def sample(self, G1, G2):
+        """`Z G1 + sqrt(d + shift) .* G2` (`gsi_precond_sample`): with standard normals in `G1` (rank x s) and `G2` (n x s) the
+        columns are draws of N(0, P).  Two `DeviceMatrix` give a `DeviceMatrix`, two host arrays a host array."""
+        ctx, lib = self.ctx, self.ctx.lib
+        if isinstance(G1, DeviceMatrix) and isinstance(G2, DeviceMatrix):
+            Z = DeviceMatrix(ctx, *G2.shape)
+            try:
+                L.check(lib.gsi_precond_sample(ctx.h, self.h, G1.h, G2.h, Z.h), lib)
+            except Exception:
+                Z.close()
+                raise
+            return Z
+        G1f, G2f = L.fmat(G1, "G1"), L.fmat(G2, "G2")
+        if G2f.shape[0] != self.n or G1f.shape != (self.rank, G2f.shape[1]):
+            raise ValueError(f"G1 must be {self.rank} x s and G2 {self.n} x s")
+        handles = [DeviceMatrix.from_host(ctx, G1f)]
+        try:
+            handles.append(DeviceMatrix.from_host(ctx, G2f))
+            handles.append(self.sample(handles[0], handles[1]))
+            return handles[2].to_host()
+        finally:
+            for h in handles:
+                h.close()
+
     def apply(self, R):
         """`P^-1 R` (`gsi_precond_apply`): a host vector or matrix, or a `DeviceMatrix`; the result is of the same kind."""
         ctx, lib = self.ctx, self.ctx.lib
@@ -199,6 +230,128 @@ def kriging_weights(op, y, noise=None, drift=None, **cg):
     My, MG = S[:, 0], S[:, 1:]
     beta = np.linalg.solve(G.T @ MG, G.T @ My)
     return My - MG @ beta, beta
+
+
+def _probe_matrix(op, precond, probes, seed):
+    """The n x s host matrix of probes z with E[zz'] = P (P = I without a preconditioner)."""
+    ctx, n = op.ctx, op.shape[0]
+    if isinstance(probes, (int, np.integer)):
+        s = int(probes)
+        if s < 1:
+            raise ValueError("probes must be at least 1")
+        handles = [DeviceMatrix(ctx, n, s)]
+        try:
+            handles[0].randn(int(seed) + 1)
+            if precond is None:
+                return handles[0].to_host()
+            handles.append(DeviceMatrix(ctx, precond.rank, s))
+            handles[1].randn(int(seed))
+            handles.append(precond.sample(handles[1], handles[0]))
+            return handles[2].to_host()
+        finally:
+            for h in handles:
+                h.close()
+    Z = probes.to_host() if isinstance(probes, DeviceMatrix) else L.fmat(probes, "probes")
+    if Z.shape[0] != n or Z.shape[1] < 1:
+        raise ValueError(f"probes must have one row per row of the operator, {n}, and at least one column; got {Z.shape}")
+    return Z
+
+
+def solve_trace(op, B, nquad, diag=None, precond=None, tol=1e-8, maxiter=None, qmax=512):
+    """`gsi_op_solve_trace` on a host matrix `B` (n x b): `(A + diag) X = B` as `solve` computes it, and the Gauss rule of
+    stochastic Lanczos quadrature for the last `nquad` columns.  Returns X and a dict: what `solve` reports, `quad` and `rho0`
+    per column, `truncated` (the columns that went beyond `qmax` iterations)."""
+    op, _ = RMF._as_operator(op)
+    ctx, lib = op.ctx, op.ctx.lib
+    n = op.shape[0]
+    d = _diag_arg(diag, n)
+    Bf = L.fmat(B, "B")
+    b = Bf.shape[1]
+    maxiter = 10 * n if maxiter is None else int(maxiter)
+    info = (C.c_int64 * 7)()
+    relres, iters, quad = np.zeros(b), np.zeros(b, dtype=np.int64), np.zeros(2 * b)
+    handles = [DeviceMatrix.from_host(ctx, Bf)]
+    try:
+        handles.append(DeviceMatrix(ctx, n, b))
+        L.check(lib.gsi_op_solve_trace(ctx.h, op.h, L.dptr(d) if d is not None else None, precond.h if precond is not None else None,
+                                       handles[0].h, handles[1].h, int(nquad), int(qmax), float(tol), maxiter, info,
+                                       L.dptr(relres), iters.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(quad)), lib)
+        X = handles[1].to_host()
+    finally:
+        for h in handles:
+            h.close()
+    rep = {"products": int(info[0]), "converged": int(info[1]), "path": PATHS.get(int(info[2]), int(info[2])),
+           "breakdown": int(info[3]), "breakdown_kind": int(info[4]), "rank": int(info[5]), "truncated": int(info[6]),
+           "relres": relres, "iters": iters, "columns": b, "quad": quad[:b].copy(), "rho0": quad[b:].copy()}
+    return X, rep
+
+
+def _slq_report(rep, s, logdet_P):
+    q = rep["quad"][-s:]
+    return {"values": q, "rho0": rep["rho0"][-s:], "stderr": float(np.std(q, ddof=1) / np.sqrt(s)) if s > 1 else float("nan"),
+            "iters": rep["iters"], "relres": rep["relres"], "products": rep["products"], "converged": rep["converged"],
+            "truncated": rep["truncated"], "logdet_P": logdet_P, "path": rep["path"], "probes": s}
+
+
+def logdet(op, diag=None, precond=None, probes=16, seed=0, tol=1e-8, maxiter=None, qmax=512, return_info=False):
+    """log det(A + diag) by stochastic Lanczos quadrature from the coefficients of one (preconditioned) multi-column CG run
+    on the probes (`gsi_op_solve_trace`): `precond.logdet` + the mean over the probes z of
+    (z'P^-1 z) e1' log(T_z) e1.  `probes`: a count -- G1, G2 are drawn by `gsi_mat_randn` with `seed` and `seed + 1` and
+    nothing else, so the same seed gives the same normals whatever the parameters of `op` are --, or an n x s host array /
+    `DeviceMatrix` of probes with E[zz'] = P (the identity without `precond`).  `qmax`: the coefficients kept per probe.
+    `return_info`: also a dict with the per-probe `values` and `rho0`, `stderr` = std / sqrt(s), `iters`, `products`,
+    `truncated`, `logdet_P`."""
+    op, _ = RMF._as_operator(op)
+    Z = _probe_matrix(op, precond, probes, seed)
+    s = Z.shape[1]
+    _, rep = solve_trace(op, Z, s, diag=diag, precond=precond, tol=tol, maxiter=maxiter, qmax=qmax)
+    ldP = precond.logdet if precond is not None else 0.0
+    val = ldP + float(np.mean(rep["quad"]))
+    return (val, _slq_report(rep, s, ldP)) if return_info else val
+
+
+def log_likelihood(op, y, noise=None, drift=None, restricted=True, precond=None, probes=16, seed=0, tol=1e-8, maxiter=None,
+                   qmax=512, return_info=False):
+    """The Gaussian log-likelihood of the data `y` under M = A + diag(noise) with the drift G (m x p) profiled out, from ONE
+    traced solve of the columns [y, G, probes]: with r = y - G beta the generalised-least-squares residual (`kriging_weights`)
+        ML    -1/2 [r'M^-1 r + log det M + m log 2 pi]
+        REML  -1/2 [r'M^-1 r + log det M + log det(G'M^-1 G) + (m - p) log 2 pi]        (`restricted`, the default)
+    log det M as `logdet` estimates it; `probes`, `seed`, `tol`, `maxiter`, `qmax`, `precond` as there.  A data column that
+    does not reach `tol` raises RuntimeError.  `return_info`: also a dict with `xi`, `beta` (the kriging weights), `quadform`,
+    `logdet`, `logdet_GMG` and what `logdet` reports."""
+    op, _ = RMF._as_operator(op)
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    m = yv.size
+    if op.shape[0] != m:
+        raise ValueError(f"y must hold one value per row of the operator, {op.shape[0]}")
+    G = np.zeros((m, 0)) if drift is None else np.asarray(drift, dtype=np.float64).reshape(m, -1)
+    p = G.shape[1]
+    Z = _probe_matrix(op, precond, probes, seed)
+    s = Z.shape[1]
+    X, rep = solve_trace(op, np.column_stack([yv, G, Z]), s, diag=noise, precond=precond, tol=tol, maxiter=maxiter, qmax=qmax)
+    if (rep["relres"][:1 + p] > tol).any():
+        raise RuntimeError(f"log_likelihood: a data column did not reach tol = {tol:g} (largest relative residual "
+                           f"{rep['relres'][:1 + p].max():.3e})")
+    My, MG = X[:, 0], X[:, 1:1 + p]
+    if p:
+        GMG = G.T @ MG
+        beta = np.linalg.solve(GMG, G.T @ My)
+        xi = My - MG @ beta
+        ld_gmg = float(np.linalg.slogdet(0.5 * (GMG + GMG.T))[1])
+    else:
+        beta, xi, ld_gmg = np.zeros(0), My, 0.0
+    quadform = float((yv - G @ beta) @ xi)
+    ldP = precond.logdet if precond is not None else 0.0
+    ld = ldP + float(np.mean(rep["quad"][-s:]))
+    if restricted:
+        val = -0.5 * (quadform + ld + ld_gmg + (m - p) * np.log(2.0 * np.pi))
+    else:
+        val = -0.5 * (quadform + ld + m * np.log(2.0 * np.pi))
+    if not return_info:
+        return val
+    info = _slq_report(rep, s, ldP)
+    info.update({"xi": xi, "beta": beta, "quadform": quadform, "logdet": ld, "logdet_GMG": ld_gmg, "restricted": bool(restricted)})
+    return val, info
 
 
 def _grid_product(at_op, G):

@@ -609,6 +609,36 @@ function solve(A::DeviceOperator, B::DeviceMatrix; diag::Union{Nothing, Vector{F
 		A.c.h, A.h, diag === nothing ? C_NULL : diag, B.h, X.h, tol, maxiter, info, relres, iters))
 	return X, (products=info[1], converged=info[2], path=info[3], breakdown=info[4], relres=relres, iters=iters)
 end
+"`solve_trace(A, B, nquad; diag, qmax, tol, maxiter)`: the same solve of the resident `B` with the conjugate-gradient
+coefficients of every column kept on the device, and the Gauss rule of stochastic Lanczos quadrature `rho0 * e1' log(T) e1` for
+the last `nquad` columns (gsi_op_solve_trace without a preconditioner): with columns `z ~ N(0, I)` the mean of the values
+estimates `logdet(A + Diagonal(diag))`.  Returns `(X, info)`, `info` as `solve` plus `truncated`, `quad` and `rho0` per column."
+function solve_trace(A::DeviceOperator, B::DeviceMatrix, nquad::Int; diag::Union{Nothing, Vector{Float64}}=nothing,
+		qmax::Int=512, tol::Float64=1e-8, maxiter::Int=10 * A.n)
+	b = B.cols
+	X = DeviceMatrix(B.rows, b; c=A.c)
+	info = zeros(Int64, 7)
+	relres = zeros(Float64, b)
+	iters = zeros(Int64, b)
+	quad = zeros(Float64, 2 * b)
+	check(ccall((:gsi_op_solve_trace, libgsi), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+			Int64, Int64, Float64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+		A.c.h, A.h, diag === nothing ? C_NULL : diag, C_NULL, B.h, X.h, nquad, qmax, tol, maxiter, info, relres, iters, quad))
+	return X, (products=info[1], converged=info[2], path=info[3], breakdown=info[4], truncated=info[7], relres=relres,
+		iters=iters, quad=quad[1:b], rho0=quad[b+1:2b])
+end
+"`slq_quadrature(alpha, beta, steps, rho0)`: the quadrature alone (gsi_slq_quadrature).  `alpha`, `beta`: b x qmax, column j's
+step k at `[j, k]` (the library's step-major layout); `steps`: the entries of each column to use."
+function slq_quadrature(alpha::Matrix{Float64}, beta::Matrix{Float64}, steps::Vector{Int64}, rho0::Vector{Float64};
+		c::Context=ctx())
+	b, qmax = size(alpha)
+	size(beta) == (b, qmax) && length(steps) == b && length(rho0) == b || throw(DimensionMismatch("slq_quadrature: shapes differ"))
+	out = zeros(Float64, b)
+	check(ccall((:gsi_slq_quadrature, libgsi), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int64,
+			Int64, Ptr{Float64}),
+		c.h, alpha, beta, steps, rho0, qmax, b, out))
+	return out
+end
 "`pivoted_cholesky(A, K; tol)`: the diagonal-pivoted Cholesky factor `L L' ~ A` of a dense, implicit grid-covariance or implicit
 point-covariance device operator from K columns of A and no operator product (gsi_op_pivoted_cholesky).  Returns
 `(L, piv, info)`: `L` a `DeviceMatrix` of n x K with zeros from column `rank + 1` on, `piv` the 1-based pivot rows (the rank
