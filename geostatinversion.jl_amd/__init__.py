@@ -15,7 +15,7 @@ from .context import (Context, Operator, DeviceMatrix, dense_operator, gridcov_o
                       gridcov_implicit_operator, pointcov_implicit_operator, fft_powerlaw_operator, fft_gridcov_operator, lowrank_synthetic_operator,
                       default_context)
 from . import randmatfact as RandMatFact
-from .randmatfact import rangefinder, randsvd, randsvd_rows, eig_nystrom, colnorms, lu_L, lu_L_dev, lu_L_sharded, lu_L_sharded_virtual, qr_thinQ, svd_tall, gemm, gemm_view, pivoted_cholesky, principal_factor
+from .randmatfact import rangefinder, randsvd, randsvd_rows, eig_nystrom, colnorms, lu_L, lu_L_dev, lu_L_sharded, lu_L_sharded_virtual, qr_thinQ, svd_tall, gemm, gemm_view, cq_gram_round, pivoted_cholesky, principal_factor
 from .lowrank import LowRankCovMatrix, PCGALowRankMatrix, device_samples
 from .getxis import getxis, getxis_iwantfields, getxis_device, getxis_fftrf, getxis_pivchol, randsvdwithseed
 from . import fftrf as FFTRF
@@ -31,7 +31,7 @@ from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBa
 __all__ = [
     "GsiError", "load", "LIB_PATH", "Context", "Operator", "DeviceMatrix", "dense_operator",
     "gridcov_operator", "gridcov_implicit_operator", "pointcov_implicit_operator", "fft_powerlaw_operator", "fft_gridcov_operator", "lowrank_synthetic_operator", "default_context", "RandMatFact", "rangefinder", "randsvd", "randsvd_rows", "eig_nystrom",
-    "colnorms", "lu_L", "lu_L_dev", "lu_L_sharded", "lu_L_sharded_virtual", "qr_thinQ", "svd_tall", "gemm", "gemm_view", "LowRankCovMatrix", "PCGALowRankMatrix", "device_samples",
+    "colnorms", "lu_L", "lu_L_dev", "lu_L_sharded", "lu_L_sharded_virtual", "qr_thinQ", "svd_tall", "gemm", "gemm_view", "cq_gram_round", "LowRankCovMatrix", "PCGALowRankMatrix", "device_samples",
     "getxis", "getxis_iwantfields", "getxis_device", "getxis_fftrf", "randsvdwithseed", "FFTRF", "lowrank_fftrf_operator", "fft_operator_at", "FFTOperatorAt", "GridCov", "GridCovSampler",
     "gridcov_sampler", "lowrank_gridcov_operator", "gridcov_structuredgrid", "pcgadirect", "pcgalsqr", "rga", "pcga",
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",

@@ -95,6 +95,8 @@ SIGNATURES = {
     "gsi_gemm": (C.c_int, [c_vp, C.c_int, c_i64, c_i64, c_i64, C.c_double, c_dp, c_i64, c_dp, c_i64, c_dp, c_i64]),
     "gsi_gemm_view": (C.c_int, [c_vp, C.c_int, C.c_int, c_i64, c_i64, c_i64, C.c_double, C.c_double, c_dp, c_i64, c_i64,
                                 c_dp, c_i64, c_i64, c_dp, c_i64, c_i64, c_i64, c_i64, C.POINTER(c_i64)]),
+    "gsi_cq_gram_round": (C.c_int, [c_vp, c_i64, C.c_int, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_double)]),
     "gsi_pcga_params": (C.c_int, [c_vp, c_dp, c_i64, c_i64, c_dp, c_dp, C.c_double, c_dp]),
     "gsi_pcga_update": (C.c_int, [c_vp, c_dp, c_i64, c_i64, c_dp, C.c_double, c_dp, c_i64, c_dp, c_dp]),
     "gsi_pcga_params_dev": (C.c_int, [c_vp, c_vp, c_i64, c_dp, c_dp, C.c_double, c_dp]),

@@ -95,8 +95,8 @@ class Context:
         last phase_reset, the ranks the communicator joined, LU time-outs seen / hidden by a transparent re-run; randsvd calls that
         finished in the sample space of a LowRankCovMatrix, range-finder power steps formed there and the ones declined, panels
         of those steps factored as two column halves and the ones factored again whole; sample-space tails that formed part of
-        Z beside the small SVD."""
-        n = 19
+        Z beside the small SVD, and their refinement rounds factored by the series of chol(I + E)."""
+        n = 20
         out = (C.c_int64 * n)()
         L.check(self.lib.gsi_ctx_path_info(self.h, out, n), self.lib)
         forms = {self.LU_FORMS[f]: int(out[6 + f]) for f in range(1, 6) if out[6 + f]}
@@ -105,7 +105,7 @@ class Context:
                 "lu_timeouts": int(out[4]), "lu_timeouts_recovered": int(out[5]), "svd_sweep_cap_hits": int(out[12]),
                 "lowrank_tails": int(out[13]), "lowrank_power_steps": int(out[14]), "lowrank_power_declines": int(out[15]),
                 "lowrank_split_lus": int(out[16]), "lowrank_split_declines": int(out[17]),
-                "lowrank_tail_overlaps": int(out[18])}
+                "lowrank_tail_overlaps": int(out[18]), "lowrank_tail_series_rounds": int(out[19])}
 
     def release_cache(self):
         """Return cached device memory (released panels, idle workspaces) to the driver (`gsi_ctx_release_cache`)."""

@@ -233,6 +233,7 @@ int gsi_ctx_path_info(gsi_ctx* ctx, int64_t* out, int64_t n_out) {
     v[GSI_PATH_LOWRANK_SPLIT_LUS] = c.lowrank_split_lus;
     v[GSI_PATH_LOWRANK_SPLIT_DECLINES] = c.lowrank_split_declines;
     v[GSI_PATH_LOWRANK_TAIL_OVERLAPS] = c.be->lowrank_tail_overlaps();
+    v[GSI_PATH_LOWRANK_TAIL_SERIES_ROUNDS] = c.be->lowrank_tail_series_rounds();
     for (int64_t i = 0; i < n_out; ++i) out[i] = i < GSI_PATH_INFO_COUNT ? v[i] : 0;
   });
 }
@@ -1271,6 +1272,25 @@ int gsi_gemm_view(gsi_ctx* ctx, int form, int trans, int64_t m, int64_t l, int64
     be->gemm_view(form, trans != 0, m, l, k, alpha, Ad.p + a_off, lda, Bd.p + b_off, ldb, beta, Cd.p + c_off, ldc, m_full, r0,
                   plan_out);
     be->download2d(C, (int64_t)nc, Cd.p, (int64_t)nc, (int64_t)nc, 1);
+    check_async_errors(ctx->c);
+  });
+}
+
+int gsi_cq_gram_round(gsi_ctx* ctx, int64_t l, int check, const double* gram, double* R, double* X, int32_t* flag_out,
+                      int32_t* series_out, double* norm_out) {
+  return guarded([&] {
+    REQUIRE(ctx && gram && R && X && flag_out && series_out && norm_out, "NULL argument");
+    REQUIRE(l >= 1 && l <= 384, "cq_gram_round: 1 <= l <= 384");
+    Backend* be = ctx->c.be.get();
+    Buf Gd(be, (size_t)l * l), Xd(be, (size_t)l * l);
+    be->fill_bytes(Xd.p, 0xFF, (size_t)l * l);                // (NaN: X has to be written whole)
+    be->upload2d(Gd.p, l, gram, l, l, l);
+    int32_t out2[2] = {0, 0};
+    be->cq_gram_round_view(Gd.p, l, Xd.p, check != 0, out2, norm_out);
+    be->download2d(R, l, Gd.p, l, l, l);
+    be->download2d(X, l, Xd.p, l, l, l);
+    *flag_out = out2[0];
+    *series_out = out2[1];
     check_async_errors(ctx->c);
   });
 }

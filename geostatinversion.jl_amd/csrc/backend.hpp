@@ -250,7 +250,7 @@ class Backend {
   // round's Gram matrix was not near the identity, l > N - 1 (centred samples span N - 1 dimensions), or a shape it does not
   // cover; pipeline.cpp:randsvd_lowrank_single then forms Y = S (c T) and runs the ordinary deferred-Q ending.
   // scratch (optional, scratch_doubles doubles): a dead panel of the caller's that the backend may overwrite instead of taking
-  // a temporary of its own (the rows of S B1 formed beside the small SVD; contents undefined on return, whatever the verdict).
+  // a temporary of its own (the rows of S B0 formed beside the small SVD; contents undefined on return, whatever the verdict).
   virtual bool lowrank_tail(const double* S, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
                             int64_t K, double c, double* Z, int64_t ldz, double* Sv, double* scratch = nullptr,
                             size_t scratch_doubles = 0) {
@@ -260,6 +260,16 @@ class Backend {
   }
   // calls of lowrank_tail that formed part of Z beside the small SVD
   virtual int64_t lowrank_tail_overlaps() { return 0; }
+  // refinement rounds of lowrank_tail's two CholeskyQR2s whose triangular factor came from its series
+  virtual int64_t lowrank_tail_series_rounds() { return 0; }
+  // One round of the sample-space tail on a Gram matrix the caller has on the device (gsi_cq_gram_round, the kernel tests):
+  // Gm (l x l) <- R in place, X (l x l) <- R^-1; check: a refinement round (the 0.1 test, and the series form where it
+  // applies).  out3: the CholeskyQR flag, 1 if the series form ran, 0 if the Cholesky did; norm_out: |Gm - I|_F as the series
+  // kernel measured it (0 where it did not run).
+  virtual void cq_gram_round_view(double* Gm, int64_t l, double* X, bool check, int32_t* out2, double* norm_out) {
+    (void)Gm; (void)l; (void)X; (void)check; (void)out2; (void)norm_out;
+    throw Error(1 /* GSI_ERR_ARG */, "cq_gram_round: not available on this backend");
+  }
   // One power step of the range finder in sample space.  The panel Y = c S T (T: N x l, ld N) was
   // factored by lu_L_keep into ipiv and L (n x l, ld ldl): P Y = L U, so L = (P S) C with C = c T U^-1, where
   // U = L11^-1 (P Y)[0:l] comes from the pivot rows, and

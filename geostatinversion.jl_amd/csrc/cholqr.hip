@@ -326,7 +326,9 @@ __device__ __forceinline__ void cqf_tri_inverse(const double* __restrict__ G, in
                                                 double* Ds, int tid, int lane, int wave, unsigned long long* trace,
                                                 unsigned long long& t_last);
 __global__ __launch_bounds__(CQF_THREADS) void cq_chol_inv_kernel(double* __restrict__ G, int l, double* __restrict__ X,
-                                                                  int32_t* __restrict__ flag, unsigned long long* __restrict__ trace) {
+                                                                  int32_t* __restrict__ flag, unsigned long long* __restrict__ trace,
+                                                                  const int32_t* __restrict__ skip) {
+  if (skip != nullptr && *skip != 0) return;               // cq_series_kernel has written R and X already
   unsigned long long t_last = (trace != nullptr) ? wall_clock64() : 0ull;
   extern __shared__ double cqf_lds[];
   double* Us = cqf_lds;                                   // [32][CQF_LDU] block row / (inverse) Wt[32][CQF_LDK]
@@ -548,6 +550,173 @@ __global__ __launch_bounds__(CQF_THREADS) void cq_tri_inv_kernel(const double* _
   cqf_tri_inverse(R, l, X, cqf_lds, cqf_lds + CQ_TB * CQF_LDU, tid, lane, wave, nullptr, t_last);
 }
 
+// G <- symmetric as cq_mirror_upper_kernel, and C <- a copy of it (what cq_series_kernel reads while it writes over G)
+__global__ void cq_mirror_copy_kernel(double* __restrict__ G, int l, double* __restrict__ C) {
+  const int64_t total = (int64_t)l * l;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(e % l), c = (int)(e / l);
+    const double v = (r > c) ? G[c + (int64_t)r * l] : G[e];
+    if (r > c) G[e] = v;
+    C[e] = v;
+  }
+}
+
+// ---- R = chol(I + E) and X = R^-1 by their series, for the Gram matrix of a refinement round (cq_gram_round) ----
+// With Phi(A) = striu(A) + diag(A) / 2:  R = I + R1 + R2 + O(|E|^3), R1 = Phi(E), R2 = -Phi(R1'R1), and
+// X = R^-1 = I - R1 + R1 R1 - R2 + O(|E|^3).  The gate: the dropped terms are O(|E|_2^3), |E|_2 <= |E|_F, and (6e-6)^3 = 2.2e-16 =
+// eps.  Below 1e-9 the second-order terms (<= |E|_F^2 = 1e-18) are far under eps and are not formed.
+// Two launches.  cq_series_norm_kernel, one workgroup: |E|_F of the mirrored Gram matrix in a fixed order (the same bits on
+// every call) and the verdict in `word`, which cq_chol_inv_kernel looks at too.  cq_series_kernel, one workgroup per 64 x 64
+// tile of the output: above the gate it leaves G and X alone; under it, it writes R over G, and X (both with zeros below the
+// diagonal), reading tmp, the copy of G its launcher made.  (On ONE workgroup the second-order sums took 0.85 ms at l = 320,
+// twice the Cholesky they replace: 44 MFLOP at a CU's 0.3 TFLOP/s)  An entry (i, j), i <= j, takes
+//   T_ij = (R1'R1)_ij = sum_{k < i} E_ik E_jk + d_i R1_ij,   Q_ij = (R1 R1)_ij = sum_{i < k < j} E_ik E_jk + (d_i + d_j) R1_ij
+// (d = diag(E) / 2; E symmetric): both sums run along rows i and j of tmp.  In a tile (I <= J) lane = row i, wave = 8 columns
+// j; per step 32 values of k of rows I and of rows J go through LDS (the next step's are loaded into registers while this one
+// is summed).  k below the tile's rows: T only; between its rows and its columns: Q only; the steps that cross either: both,
+// masked entry by entry.
+// word: [0] += 1 per round taken, [1] = 1 taken / 0 not, [2..3] |E|_F as a double.
+constexpr double CQS_GATE = 6e-6;
+constexpr double CQS_FIRST_ORDER = 1e-9;
+constexpr int CQS_T = 64;            // the output tile
+constexpr int CQS_KT = 32;           // values of k per step
+constexpr int CQS_NJ = CQS_T / (CQF_THREADS / 64);            // columns per wave
+constexpr int CQS_LD = CQS_T * CQS_KT / CQF_THREADS;          // elements of a tile step per thread
+static_assert(CQS_NJ == 8 && CQS_LD == 4, "cq_series_kernel's tiling");
+__global__ __launch_bounds__(CQF_THREADS) void cq_series_norm_kernel(const double* __restrict__ G, int l, double gate,
+                                                                     int32_t* __restrict__ word) {
+  __shared__ double red[CQF_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NC = 4, NR = CQF_MAXL / 64;                // a wave takes 4 columns at a time, a lane up to 6 rows of each:
+  double s = 0.0;                                          // 24 loads in flight, summed in a fixed order
+  for (int c0 = wave * NC; c0 < l; c0 += NC * (CQF_THREADS / 64)) {
+    double v[NC][NR];
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+      for (int m = 0; m < NR; ++m) {
+        const int c = c0 + cc, r = lane + 64 * m;
+        v[cc][m] = (c < l && r < l) ? G[r + (int64_t)c * l] - (r == c ? 1.0 : 0.0) : 0.0;
+      }
+#pragma unroll
+    for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+      for (int m = 0; m < NR; ++m) s = fma(v[cc][m], v[cc][m], s);
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int w2 = 0; w2 < CQF_THREADS / 64; ++w2) t += red[w2];
+    const double nrm = sqrt(t);
+    const bool take = nrm <= gate;                         // (NaN: not taken)
+    if (take) word[0] += 1;
+    word[1] = take ? 1 : 0;
+    *reinterpret_cast<double*>(word + 2) = nrm;
+  }
+}
+__global__ __launch_bounds__(CQF_THREADS) void cq_series_kernel(double* __restrict__ G, int l, double* __restrict__ X,
+                                                                const double* __restrict__ tmp, const int32_t* __restrict__ word) {
+  __shared__ double As[CQS_KT][CQS_T], Bs[CQS_KT][CQS_T];   // [k][row i] of the rows I, [k][row j] of the rows J
+  __shared__ double dI[CQS_T], dJ[CQS_T];
+  if (word[1] == 0) return;
+  const double nrm = *reinterpret_cast<const double*>(word + 2);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool second = nrm > CQS_FIRST_ORDER;
+  const int nb = (l + CQS_T - 1) / CQS_T;
+  const int I = (int)blockIdx.x % nb, J = (int)blockIdx.x / nb;
+  const int i = I * CQS_T + lane, j0 = J * CQS_T + wave * CQS_NJ;
+  if (tid < CQS_T) {
+    const int gi = I * CQS_T + tid, gj = J * CQS_T + tid;
+    dI[tid] = gi < l ? 0.5 * (tmp[gi + (int64_t)gi * l] - 1.0) : 0.0;
+    dJ[tid] = gj < l ? 0.5 * (tmp[gj + (int64_t)gj * l] - 1.0) : 0.0;
+  }
+  __syncthreads();
+  double accT[CQS_NJ], accQ[CQS_NJ];
+#pragma unroll
+  for (int jj = 0; jj < CQS_NJ; ++jj) { accT[jj] = 0.0; accQ[jj] = 0.0; }
+  if (second && I <= J) {
+    // k < j <= the tile's last column
+    const int nsteps = (min(l, (J + 1) * CQS_T) + CQS_KT - 1) / CQS_KT;
+    double ra[CQS_LD], rb[CQS_LD];
+    auto fetch = [&](int step) __attribute__((always_inline)) {
+#pragma unroll
+      for (int m = 0; m < CQS_LD; ++m) {
+        const int e = tid + m * CQF_THREADS, kk = e / CQS_T, rr = e % CQS_T;
+        const int k = step * CQS_KT + kk, gi = I * CQS_T + rr, gj = J * CQS_T + rr;
+        ra[m] = (k < l && gi < l) ? tmp[gi + (int64_t)k * l] : 0.0;
+        rb[m] = (k < l && gj < l) ? tmp[gj + (int64_t)k * l] : 0.0;
+      }
+    };
+    fetch(0);
+    for (int step = 0; step < nsteps; ++step) {
+#pragma unroll
+      for (int m = 0; m < CQS_LD; ++m) {
+        const int e = tid + m * CQF_THREADS;
+        As[e / CQS_T][e % CQS_T] = ra[m];
+        Bs[e / CQS_T][e % CQS_T] = rb[m];
+      }
+      __syncthreads();
+      if (step + 1 < nsteps) fetch(step + 1);
+      const int k0 = step * CQS_KT;
+      if (k0 + CQS_KT <= I * CQS_T) {                  // k < every row of the tile: T only
+#pragma unroll 8
+        for (int kk = 0; kk < CQS_KT; ++kk) {
+          const double a = As[kk][lane];
+#pragma unroll
+          for (int jj = 0; jj < CQS_NJ; ++jj) accT[jj] = fma(a, Bs[kk][wave * CQS_NJ + jj], accT[jj]);
+        }
+      } else if (k0 >= (I + 1) * CQS_T && k0 + CQS_KT <= J * CQS_T) {   // between the tile's rows and its columns: Q only
+#pragma unroll 8
+        for (int kk = 0; kk < CQS_KT; ++kk) {
+          const double a = As[kk][lane];
+#pragma unroll
+          for (int jj = 0; jj < CQS_NJ; ++jj) accQ[jj] = fma(a, Bs[kk][wave * CQS_NJ + jj], accQ[jj]);
+        }
+      } else {
+#pragma unroll 4
+        for (int kk = 0; kk < CQS_KT; ++kk) {
+          const int k = k0 + kk;
+          const double a = As[kk][lane];
+          const double aT = (k < i) ? a : 0.0, aQ = (k > i) ? a : 0.0;
+#pragma unroll
+          for (int jj = 0; jj < CQS_NJ; ++jj) {
+            const double b = Bs[kk][wave * CQS_NJ + jj];
+            accT[jj] = fma(aT, b, accT[jj]);
+            accQ[jj] = fma(aQ, (k < j0 + jj) ? b : 0.0, accQ[jj]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (i >= l) return;
+#pragma unroll
+  for (int jj = 0; jj < CQS_NJ; ++jj) {
+    const int j = j0 + jj;
+    if (j >= l) continue;
+    double rv = 0.0, xv = 0.0;
+    if (i <= j) {
+      const bool diag = (i == j);
+      const double di = dI[lane];
+      const double r1 = diag ? di : tmp[i + (int64_t)j * l];
+      double phiT = 0.0, q = 0.0;
+      if (second) {
+        const double t = accT[jj] + di * r1;
+        phiT = diag ? 0.5 * t : t;
+        q = diag ? di * di : accQ[jj] + (di + dJ[wave * CQS_NJ + jj]) * r1;
+      }
+      const double one = diag ? 1.0 : 0.0;
+      rv = (one + r1) - phiT;
+      xv = (one - r1) + (q + phiT);
+    }
+    G[i + (int64_t)j * l] = rv;
+    X[i + (int64_t)j * l] = xv;
+  }
+}
+
 static inline int grid_for(int64_t total, int cap = 2048) {
   int64_t g = (total + 255) / 256;
   if (g > cap) g = cap;
@@ -631,7 +800,8 @@ void cq_round(hipStream_t st, const double* src, int64_t lds, double* dst, int64
     static const bool trace_on = (getenv("GSI_CQ_TRACE") != nullptr);            // measurement only: synchronises and prints
     unsigned long long* trace = nullptr;
     if (trace_on && hipMalloc((void**)&trace, 8 * sizeof(unsigned long long)) == hipSuccess) hipMemsetAsync(trace, 0, 8 * sizeof(unsigned long long), st);
-    hipLaunchKernelGGL(cq_chol_inv_kernel, dim3(1), dim3(CQF_THREADS), CQF_LDS_BYTES, st, Rp, l, X, flag, trace);
+    hipLaunchKernelGGL(cq_chol_inv_kernel, dim3(1), dim3(CQF_THREADS), CQF_LDS_BYTES, st, Rp, l, X, flag, trace,
+                       (const int32_t*)nullptr);
     if (trace != nullptr) {
       unsigned long long h[8];
       hipMemcpyAsync(h, trace, sizeof(h), hipMemcpyDeviceToHost, st);
@@ -708,18 +878,28 @@ void mirror_upper(hipStream_t st, double* G, int64_t l) {
 }
 // One CholeskyQR round on a Gram matrix the caller formed (M'(G M) for the panel S M): made symmetric from its upper triangle,
 // the orthogonality check of a second round (check: flag |= 2 when max |Gm - I| > 0.1, as cq_round), then R = chol(Gm) in
-// place and X = R^-1 by the fused kernel (flag |= 1 on a negligible pivot).  false: l beyond the fused kernel (nothing queued).
-bool cq_gram_round(hipStream_t st, double* Gm, int64_t l64, double* X, bool check, int32_t* flag) {
+// place and X = R^-1 by the fused kernel (flag |= 1 on a negligible pivot).  With check, series (four device words, see
+// cq_series_kernel) and tmp (l x l): R and X by their series where |Gm - I|_F <= 6e-6, the fused kernel then returns at once
+// (GSI_CQ_SERIES=0: never).  false: l beyond the fused kernel (nothing queued).
+bool cq_gram_round(hipStream_t st, double* Gm, int64_t l64, double* X, bool check, int32_t* flag, int32_t* series, double* tmp) {
   const int l = (int)l64;
   if (l < 1 || l > CQF_MAXL) return false;
-  hipLaunchKernelGGL(cq_mirror_upper_kernel, dim3(64), dim3(256), 0, st, Gm, l);
+  static const bool series_off = (getenv("GSI_CQ_SERIES") != nullptr && getenv("GSI_CQ_SERIES")[0] == '0');
+  const bool by_series = check && !series_off && series != nullptr && tmp != nullptr;
+  if (by_series) hipLaunchKernelGGL(cq_mirror_copy_kernel, dim3(64), dim3(256), 0, st, Gm, l, tmp);
+  else hipLaunchKernelGGL(cq_mirror_upper_kernel, dim3(64), dim3(256), 0, st, Gm, l);
   if (check)
     hipLaunchKernelGGL(cq_orth_check_kernel, dim3(grid_for((int64_t)l * l, 64)), dim3(256), 0, st, Gm, l, 0.1, flag);
+  if (by_series) {
+    const int nb = (l + CQS_T - 1) / CQS_T;
+    hipLaunchKernelGGL(cq_series_norm_kernel, dim3(1), dim3(CQF_THREADS), 0, st, tmp, l, CQS_GATE, series);
+    hipLaunchKernelGGL(cq_series_kernel, dim3(nb * nb), dim3(CQF_THREADS), 0, st, Gm, l, X, tmp, (const int32_t*)series);
+  }
   static std::atomic<uint64_t> attr_mask{0};
   if (first_use_on_this_device(attr_mask))
     (void)hipFuncSetAttribute((const void*)cq_chol_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CQF_LDS_BYTES);
   hipLaunchKernelGGL(cq_chol_inv_kernel, dim3(1), dim3(CQF_THREADS), CQF_LDS_BYTES, st, Gm, l, X, flag,
-                     (unsigned long long*)nullptr);
+                     (unsigned long long*)nullptr, by_series ? (const int32_t*)(series + 1) : (const int32_t*)nullptr);
   return true;
 }
 // R (l x l) <- R2 R1, both upper triangular

@@ -84,6 +84,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
     FLAG_ERROR_WORDS = 8, FLAG_SVD_ROTATIONS = 8,     // (behind the error words:) the Jacobi SVD's rotation counter
     FLAG_CHOLQR = 9,             // the verdict of a CholeskyQR attempt: non-zero = this tier does not apply (read_flag)
     FLAG_CHOL_LOWER = 10,        // chol_lower / saddle_solve: 0 or the 1-based column of the first bad pivot (read_flag)
+    FLAG_CQ_SERIES = 12,         // four words of cq_gram_round's series form: rounds taken, taken this time, |Gram - I|_F (a double)
     FLAG_COUNT = 16
   };
   struct GemmWs { double* p; size_t doubles; };      // the contractions' split-K workspace and how many doubles it holds
@@ -129,6 +130,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   int64_t lu_timeouts() override { return n_lu_timeouts_; }
   int64_t svd_cap_hits() override { return n_svd_cap_hits_; }
   int64_t lowrank_tail_overlaps() override { return n_tail_overlaps_; }
+  int64_t lowrank_tail_series_rounds() override { return n_tail_series_rounds_; }
   void set_ranks_sharing_device(int n) override { ranks_sharing_device_ = n; }
 
   // ---- hip_backend_products.hip ----
@@ -221,6 +223,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   bool sample_gram(const double* S, int64_t ld, int64_t n, int64_t N, double* G) override;
   bool lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T, int64_t l,
                     int64_t K, double c, double* Z, int64_t ldz, double* Sv, double* scratch, size_t scratch_doubles) override;
+  void cq_gram_round_view(double* Gm, int64_t l, double* X, bool check, int32_t* out2, double* norm_out) override;
   bool lowrank_power_step(const double* Sm, int64_t lds, int64_t n, int64_t N, const double* G, const double* T,
                           const int32_t* ipiv, const double* L, int64_t ldl, int64_t l, double c, double* Tn) override;
   bool lowrank_split_ok(int64_t n, int64_t N, int64_t l, int64_t l1) override;
@@ -376,6 +379,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   int64_t n_svd_cap_hits_ = 0;
   int64_t n_cholqr_ = 0, n_householder_ = 0, n_scholqr3_ = 0;
   int64_t n_tail_overlaps_ = 0;
+  int64_t n_tail_series_rounds_ = 0;
 
   // ---- the QR tiers ----
   std::map<std::pair<int64_t, bool>, int> skip_tier1_by_height_;

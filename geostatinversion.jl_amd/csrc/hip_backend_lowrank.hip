@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "hip_backend_impl.hpp"
 
 namespace gsi {
@@ -31,8 +32,10 @@ RowLists row_lists(int64_t moved, int64_t chk) {
 }
 
 // Both constants were measured at the headline: with 8 or 16 CUs left free the first kernel behind the
-// fork waited for the whole side product; 0.40 n rows at 224 CUs end just before M is ready (0.34 and 0.46 were slower).
-constexpr double TAIL_OVERLAP_FRACTION = 0.40;
+// fork waited for the whole side product; forked at B0 and with the refinement rounds by series, 0.46 n rows at 224 CUs end
+// 0.4 ms before M is ready and 0.52 n 0.2 ms after it (in that bracket 0.40, 0.52, 0.58 and 0.64 were slower; with the fork
+// alone, a longer chain, 0.52 and 0.58 were the faster ones).
+constexpr double TAIL_OVERLAP_FRACTION = 0.46;
 constexpr int TAIL_RESERVE_CUS = 32;
 constexpr int64_t SPLIT_MAX_L1 = 192;
 
@@ -58,10 +61,13 @@ bool HipBackend::sample_gram(const double* S, int64_t ld, int64_t n, int64_t N, 
 // product (Z, K = N) is left.  Each Gram matrix is the exact one of its panel up to eps |M|^2 |G| (against eps |S M|^2 when
 // the panel is formed): the second rounds' check catches a panel whose coefficients grew too large for that to hold.
 //
-// The overlap.  Between the last Gram round and M = (XW2 U sqrt(S))[:, 0:K] lies a chain of small dependent launches (the
-// Cholesky, the Jacobi sweeps) on a few workgroups, and behind it the one tall product.  C = B1 M, and B1 is known before the
-// chain: Y_f = S[0:n_f] B1 (n_f x l) is formed on the side stream while the chain runs, on all but TAIL_RESERVE_CUS CUs
-// (hipk::gemm_f64_nn_capped), and those rows of Z then cost a reduction of length l instead of N: Z[0:n_f] = Y_f M.  The rows
+// The overlap.  Between the second Gram round and M = (XW2 U sqrt(S))[:, 0:K] lies a chain of small dependent launches (the
+// Gram rounds of W, the Jacobi sweeps) on a few workgroups, and behind it the one tall product.  C = B1 M = B0 (XW1 M), and B0
+// = c G A1 is known behind the first product of the second round: Y_f = S[0:n_f] B0 (n_f x l) is formed on the side stream
+// while the chain runs, on all but TAIL_RESERVE_CUS CUs (hipk::gemm_f64_nn_capped), and those rows of Z then cost a reduction
+// of length l instead of N: Z[0:n_f] = Y_f (XW1 M).  (Not forked earlier: from G A0 the coefficient carries X1, and cond(R1)
+// goes into the rows -- 6e-10 in the model of DESIGN.md.  GSI_LOWRANK_TAIL_FORK=late: from B1, behind the fourth round.)  The
+// last l - K columns of Z are cleared on the side stream behind the product.  The rows
 // from n_f on are the row block of today's product (the same tiles in the same order: the same bits).  n_f is a multiple of
 // the contraction's row tile fixed by (n, the fraction), so repeated calls give the same bits.  Y_f goes into `scratch` (the
 // caller's dead panel) or a pooled temporary.  On by default where the capped product runs persistent;
@@ -83,13 +89,20 @@ bool HipBackend::lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t 
     const int v = e ? atoi(e) : TAIL_RESERVE_CUS;
     return (v >= 8 && (v & 7) == 0) ? v : TAIL_RESERVE_CUS;
   }();
+  static const bool trace = (getenv("GSI_LOWRANK_POWER_TRACE") != nullptr || getenv("GSI_CQ_SERIES_TRACE") != nullptr);
+  static const bool series_off = (getenv("GSI_CQ_SERIES") != nullptr && getenv("GSI_CQ_SERIES")[0] == '0');
+  // experiments and the tests: "late" forks where B1 is known (behind the fourth round) instead of at B0
+  static const bool fork_late = [] {
+    const char* e = getenv("GSI_LOWRANK_TAIL_FORK");
+    return e != nullptr && strcmp(e, "late") == 0;
+  }();
   const size_t Nl = (size_t)N * l, ll = (size_t)l * l;
   Carve cv;
-  const size_t o_A0 = cv.take(Nl), o_A1 = cv.take(Nl), o_P = cv.take(Nl);
+  const size_t o_A0 = cv.take(Nl), o_A1 = cv.take(Nl), o_P = cv.take(Nl), o_B0 = cv.take(Nl);
   size_t o_Gr[4], o_X[4];
   for (int i = 0; i < 4; ++i) o_Gr[i] = cv.take(ll);
   for (int i = 0; i < 4; ++i) o_X[i] = cv.take(ll);
-  const size_t o_R = cv.take(ll), o_Rf = cv.take(ll), o_U = cv.take(ll), o_Mm = cv.take(ll);
+  const size_t o_R = cv.take(ll), o_Rf = cv.take(ll), o_U = cv.take(ll), o_Mm = cv.take(ll), o_Np = cv.take(ll);
   Scratch buf(this, cv.total);
   const int cap = std::max(8, ((ncus_ - reserve) / 8) * 8);
   int64_t nf = 0;
@@ -97,9 +110,10 @@ bool HipBackend::lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t 
     nf = (int64_t)((ov_env > 0.0 ? ov_env : TAIL_OVERLAP_FRACTION) * (double)n) / 128 * 128;
     if (nf >= n) nf = (n - 1) / 128 * 128;
   }
-  double* A0 = buf.p + o_A0;          // c T; then B0; then C
+  double* A0 = buf.p + o_A0;          // c T
   double* A1 = buf.p + o_A1;          // A0 X1; then B1
-  double* P = buf.p + o_P;            // G times the current coefficients
+  double* P = buf.p + o_P;            // G times the current coefficients; then C
+  double* B0 = buf.p + o_B0;          // c G A1: the side stream reads it from the fork to the join, nothing else goes there
   double* Gr[4];                      // the four Gram matrices, each R in place afterwards
   for (int i = 0; i < 4; ++i) Gr[i] = buf.p + o_Gr[i];
   double* X[4];                       // X1, X2, XW1, XW2
@@ -108,16 +122,19 @@ bool HipBackend::lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t 
   double* Rf = buf.p + o_Rf;
   double* U = buf.p + o_U;
   double* Mm = buf.p + o_Mm;
+  double* Np = buf.p + o_Np;          // XW1 M (l x K): what Y_f = S[0:n_f] B0 is multiplied by
   size_t gmax = hipk::gemm_workspace_doubles(N, l, N);
   gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, N));
   gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, l, l));
   gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, l, l));
+  gmax = std::max(gmax, hipk::gemm_workspace_doubles(l, K, l));
   gmax = std::max(gmax, hipk::gemm_workspace_doubles(N, K, l));
   gmax = std::max(gmax, hipk::gemm_workspace_doubles(n, K, N));
+  const double* side_B = fork_late ? A1 : B0;             // the coefficients the side product reads
   if (nf >= 128) {
-    // (the capped launch reads its operands' alignment: A1 is where B1 will be)
+    // (the capped launch reads its operands' alignment)
     hipk::GemmPlan plan = {0, 0, 0, 0, 0, 0, 0, 0};
-    const bool takes = hipk::gemm_f64_nn_capped(st_, nf, l, N, Sm, lds, A1, N, A1, nf, cap, true, &plan);
+    const bool takes = hipk::gemm_f64_nn_capped(st_, nf, l, N, Sm, lds, side_B, N, A1, nf, cap, true, &plan);
     if (!takes || (ov_env < 0.0 && plan.persistent == 0)) nf = 0;
   } else {
     nf = 0;
@@ -127,57 +144,101 @@ bool HipBackend::lowrank_tail(const double* Sm, int64_t lds, int64_t n, int64_t 
   if (nf > 0) gmax = std::max(gmax, hipk::gemm_workspace_doubles(nf, K, l));
   const GemmWs ws = gemm_ws(gmax + 64);
   SideJoin side(this);                                    // (after every buffer the side stream touches: joined before they go)
+  auto fork_side = [&] {
+    side.fork();
+    (void)hipk::gemm_f64_nn_capped(st2_, nf, l, N, Sm, lds, side_B, N, Yf, nf, cap);     // Y_f = S[0:n_f] B0 (late: B1)
+    check_launch("lowrank_tail (side product)");
+  };
   // one round on the panel S M: P = G M, Gram = M'P, R = chol(Gram) in place, X = R^-1
   auto round = [&](const double* M, int i, bool check) {
     gemm("lowrank_tail", ws, false, N, l, N, 1.0, G, N, M, N, 0.0, P, N);
+    if (i == 1) {
+      hipk::scal_copy(st_, (int64_t)N * l, c, P, B0);                                      // W = A'Q1 = S (c G A1) = S B0
+      if (nf > 0 && !fork_late) fork_side();
+    }
     gemm("lowrank_tail", ws, true, l, l, N, 1.0, M, N, P, N, 0.0, Gr[i], l);
-    (void)hipk::cq_gram_round(st_, Gr[i], l, X[i], check, flags_ + FLAG_CHOLQR);
+    // (a refinement round: R and X by their series where the Gram matrix is the identity to 6e-6; Rf is free until the SVD)
+    (void)hipk::cq_gram_round(st_, Gr[i], l, X[i], check, flags_ + FLAG_CHOLQR, flags_ + FLAG_CQ_SERIES, Rf);
+    if (check && trace && !series_off) {                   // (GSI_CQ_SERIES=0: nobody measures the norm)
+      double nrm = 0.0;
+      HIP_CHECK(hipMemcpyAsync(&nrm, flags_ + FLAG_CQ_SERIES + 2, sizeof(double), hipMemcpyDeviceToHost, st_));
+      HIP_CHECK(hipStreamSynchronize(st_));
+      fprintf(stderr, "lowrank_tail: n %lld N %lld l %lld, refinement round %d: |Gram - I|_F = %.3e (series form up to 6e-6)\n",
+              (long long)n, (long long)N, (long long)l, i, nrm);
+    }
   };
   phase_begin(PH_QR);
   HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOLQR, 0, sizeof(int32_t), st_));
+  HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CQ_SERIES, 0, 4 * sizeof(int32_t), st_));
   hipk::scal_copy(st_, (int64_t)N * l, c, T, A0);                                          // Y = S A0
   round(A0, 0, false);
   gemm("lowrank_tail", ws, false, N, l, l, 1.0, A0, N, X[0], l, 0.0, A1, N);               // Q1 = Y R1^-1 = S A1
-  round(A1, 1, true);                                                                       // X2 = R2^-1: Q = Q1 X2
-  hipk::scal_copy(st_, (int64_t)N * l, c, P, A0);                                          // W = A'Q1 = S (c G A1) = S B0
-  round(A0, 2, false);
-  gemm("lowrank_tail", ws, false, N, l, l, 1.0, A0, N, X[2], l, 0.0, A1, N);               // W RW1^-1 = S B1
+  round(A1, 1, true);                                                                       // X2 = R2^-1: Q = Q1 X2; B0, the fork
+  round(B0, 2, false);
+  gemm("lowrank_tail", ws, false, N, l, l, 1.0, B0, N, X[2], l, 0.0, A1, N);               // W RW1^-1 = S B1
   round(A1, 3, true);
   check_launch("lowrank_tail");
-  if (nf > 0) {
-    side.fork();
-    (void)hipk::gemm_f64_nn_capped(st2_, nf, l, N, Sm, lds, A1, N, Yf, nf, cap);        // Y_f = S[0:n_f] B1
-    check_launch("lowrank_tail (side product)");
-  }
-  if (read_flag(FLAG_CHOLQR) != 0) {
+  if (nf > 0 && fork_late) fork_side();
+  // (the verdict and the count of series rounds in one copy: FLAG_CHOLQR .. FLAG_CQ_SERIES)
+  int32_t verdict[FLAG_CQ_SERIES - FLAG_CHOLQR + 1];
+  HIP_CHECK(hipMemcpyAsync(verdict, flags_ + FLAG_CHOLQR, sizeof(verdict), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  if (verdict[0] != 0) {
     side.join();
     phase_end(PH_QR);
     return false;                                         // nothing of Z or Sv written: the caller's path takes over
   }
+  // the last l - K columns of Z are zero by definition (RandMatFact.jl:87); nobody else touches them: behind the side product
+  // where there is one
+  auto clear_rest = [&](hipStream_t st) {
+    if (K < l) HIP_CHECK(hipMemsetAsync(Z + (size_t)K * ldz, 0, sizeof(double) * ((size_t)(l - K - 1) * ldz + n), st));
+  };
+  if (nf > 0) clear_rest(st2_);
   hipk::tri_product(st_, Gr[3], Gr[2], l, R);                                               // R_W = RW2 RW1
   gemm("lowrank_tail", ws, false, l, l, l, 1.0, R, l, X[1], l, 0.0, Rf, l);                // svd(W X2) = svd(R_W X2)
   phase_end(PH_QR);
   n_cholqr_ += 2;
+  n_tail_series_rounds_ += verdict[FLAG_CQ_SERIES - FLAG_CHOLQR];
   phase_begin(PH_SVD);
   svd_small(Rf, l, U, Sv);
   hipk::scale_cols_sqrt(st_, U, l, Sv, K);
   phase_end(PH_SVD);
   phase_begin(PH_SMALL_GEMM);
-  gemm("lowrank_tail", ws, false, l, K, l, 1.0, X[3], l, U, l, 0.0, Mm, l);                // XW2 U sqrt(S), first K columns
-  gemm("lowrank_tail", ws, false, N, K, l, 1.0, A1, N, Mm, l, 0.0, A0, N);                 // C = B1 (XW2 U sqrt(S))
+  gemm("lowrank_tail", ws, false, l, K, l, 1.0, X[3], l, U, l, 0.0, Mm, l);                // M = XW2 U sqrt(S), first K columns
+  gemm("lowrank_tail", ws, false, N, K, l, 1.0, A1, N, Mm, l, 0.0, P, N);                  // C = B1 M
   if (nf > 0) {
+    const double* Mf = Mm;
+    if (!fork_late) {
+      gemm("lowrank_tail", ws, false, l, K, l, 1.0, X[2], l, Mm, l, 0.0, Np, l);           // B1 M = B0 (XW1 M)
+      Mf = Np;
+    }
     side.join();
-    gemm("lowrank_tail", ws, false, nf, K, l, 1.0, Yf, nf, Mm, l, 0.0, Z, ldz);            // Z[0:n_f] = Y_f M
-    gemm_rowblock("lowrank_tail", ws, n, nf, n - nf, K, N, Sm, lds, A0, N, Z, ldz);        // Z[n_f:n] = S[n_f:n] C
+    gemm("lowrank_tail", ws, false, nf, K, l, 1.0, Yf, nf, Mf, l, 0.0, Z, ldz);            // Z[0:n_f] = Y_f (XW1 M) (late: Y_f M)
+    gemm_rowblock("lowrank_tail", ws, n, nf, n - nf, K, N, Sm, lds, P, N, Z, ldz);         // Z[n_f:n] = S[n_f:n] C
     ++n_tail_overlaps_;
   } else {
-    gemm("lowrank_tail", ws, false, n, K, N, 1.0, Sm, lds, A0, N, 0.0, Z, ldz);            // Z = S C
+    gemm("lowrank_tail", ws, false, n, K, N, 1.0, Sm, lds, P, N, 0.0, Z, ldz);             // Z = S C
+    clear_rest(st_);
   }
-  // the last l - K columns of Z are zero by definition (RandMatFact.jl:87)
-  if (K < l) HIP_CHECK(hipMemsetAsync(Z + (size_t)K * ldz, 0, sizeof(double) * ((size_t)(l - K - 1) * ldz + n), st_));
   check_launch("lowrank_tail");
   phase_end(PH_SMALL_GEMM);
   return true;
+}
+// gsi_cq_gram_round: one round of the tail on a Gram matrix of the caller's (the kernel tests)
+void HipBackend::cq_gram_round_view(double* Gm, int64_t l, double* X, bool check, int32_t* out2, double* norm_out) {
+  bind();
+  Scratch tmp(this, (size_t)l * (size_t)l);
+  HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CHOLQR, 0, sizeof(int32_t), st_));
+  HIP_CHECK(hipMemsetAsync(flags_ + FLAG_CQ_SERIES, 0, 4 * sizeof(int32_t), st_));
+  if (!hipk::cq_gram_round(st_, Gm, l, X, check, flags_ + FLAG_CHOLQR, flags_ + FLAG_CQ_SERIES, tmp.p))
+    throw Error(GSI_ERR_ARG, "cq_gram_round: l is beyond the fused Cholesky kernel");
+  check_launch("cq_gram_round");
+  int32_t w[FLAG_CQ_SERIES - FLAG_CHOLQR + 4];
+  HIP_CHECK(hipMemcpyAsync(w, flags_ + FLAG_CHOLQR, sizeof(w), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  out2[0] = w[0];
+  out2[1] = w[FLAG_CQ_SERIES - FLAG_CHOLQR + 1];
+  memcpy(norm_out, w + (FLAG_CQ_SERIES - FLAG_CHOLQR + 2), sizeof(double));
 }
 // One power step of the range finder in sample space (Backend::lowrank_power_step).  The LU of
 // Y = c S T gives L = P Y U^-1 = (P S) C, C = c T U^-1, so S'L = S'P S C = G C + S'(P - I) S C, and P - I is non-zero on

@@ -314,8 +314,11 @@ void cholqr2_R(hipStream_t st, int64_t l, double* small_ws, double* R);         
 const double* cholqr2_X2(const double* small_ws, int64_t l);                    // R2^-1 (l x l) after cholqr2_factor
 void mirror_upper(hipStream_t st, double* G, int64_t l);                          // strictly lower <- upper
 // R = chol(Gm) in place and X = R^-1 for a Gram matrix formed by the caller (upper triangle read, then mirrored); check: the
-// second round's |Gm - I| test.  false: l > 384 (nothing queued)
-bool cq_gram_round(hipStream_t st, double* Gm, int64_t l, double* X, bool check, int32_t* flag);
+// second round's |Gm - I| test.  series (four device words, 8-byte aligned: rounds taken, taken this time, |Gm - I|_F as a
+// double) and tmp (l x l), with check: R and X by their second-order series where |Gm - I|_F <= 6e-6.  false: l > 384 (nothing
+// queued)
+bool cq_gram_round(hipStream_t st, double* Gm, int64_t l, double* X, bool check, int32_t* flag, int32_t* series = nullptr,
+                   double* tmp = nullptr);
 void tri_product(hipStream_t st, const double* R2, const double* R1, int64_t l, double* R);   // R = R2 R1 (upper triangular)
 // X = R^-1 of an upper triangular R by the inverse half of the fused Cholesky kernel (false: l > 384, nothing queued)
 bool tri_inverse(hipStream_t st, const double* R, int64_t l, double* X);

@@ -381,3 +381,21 @@ def gemm_view(A, B, C_image, *, m, l, k, form=0, trans=False, alpha=1.0, beta=0.
                                   a_off, None if Bf is None else L.dptr(Bf), ldb, b_off, L.dptr(img), ldc, c_off, m_full, r0,
                                   plan.ctypes.data_as(C.POINTER(L.c_i64))), ctx.lib)
     return img, dict(zip(GEMM_PLAN_FIELDS, (int(v) for v in plan)))
+
+
+def cq_gram_round(gram, *, check=True, ctx=None):
+    """One CholeskyQR round of the sample-space tail on an l x l Gram matrix (`gsi_cq_gram_round`, the kernel tests' entry).
+
+    Returns (R, X, flag, series, norm): the upper triangular factor of `gram` (its upper triangle is read), its inverse, the
+    round's verdict, whether R and X came from the series of chol(I + E) (a refinement round, check=True, with
+    |gram - I|_F <= 6e-6) and that norm as the device measured it."""
+    ctx = ctx or default_context()
+    Gf = L.fmat(gram, "gram")
+    l = Gf.shape[0]
+    if Gf.shape != (l, l):
+        raise ValueError("gram must be square")
+    Rm, Xm = np.empty((l, l), order="F"), np.empty((l, l), order="F")
+    flag, series, norm = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+    L.check(ctx.lib.gsi_cq_gram_round(ctx.h, l, int(bool(check)), L.dptr(Gf), L.dptr(Rm), L.dptr(Xm), C.byref(flag),
+                                      C.byref(series), C.byref(norm)), ctx.lib)
+    return Rm, Xm, int(flag.value), int(series.value), float(norm.value)
