@@ -322,7 +322,7 @@ void HipBackend::qr_thinQ(double* Y, int64_t m, int64_t l, int64_t ld, double* R
   const size_t o_coef = c.take(2 + NB + 2), o_part = c.take((size_t)nb * NB), o_tau = c.take(l),
                o_T = c.take((size_t)npan * NB * NB), o_G = c.take(NB * NB),
                o_Wt = c.take((size_t)l * NB), o_W2 = c.take((size_t)l * NB), o_small = c.take(hipk::cholqr_small_doubles(l)),
-               o_Q = c.take((size_t)(m + 1) * l);
+               o_Q = c.take((size_t)(m + 1) * l), o_amax = c.take(1 + hipk::QR_AMAX_PARTS);
   grow(ws_qr_, c.total * sizeof(double));
   TrimGuard trim_qr{this, &ws_qr_}, trim_hh{this, &ws_qr_hh_};
   double* base = (double*)ws_qr_.p;
@@ -371,7 +371,17 @@ void HipBackend::qr_thinQ(double* Y, int64_t m, int64_t l, int64_t ld, double* R
   ++n_householder_;
   grow(ws_qr_hh_, (size_t)m * NB * sizeof(double));       // the reflector block: only this tier needs it
   w.Vbuf = (double*)ws_qr_hh_.p;
+  // Range guard: the reflectors are formed from plain sums of squares, so a panel whose largest entry
+  // lies outside [2^-400, 2^400] is factored as 2^-e Y (same Q, bit for bit) and R is scaled back by 2^e.  One pass over
+  // the panel and one 8-byte read; inside the window nothing else runs.
+  hipk::qr_absmax(st_, Y, m, l, ld, base + o_amax);
+  double amax = 0.0;
+  HIP_CHECK(hipMemcpyAsync(&amax, base + o_amax, sizeof(double), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  const int e = hipk::qr_prescale_exponent(amax);
+  if (e != 0) hipk::qr_scale(st_, Y, m, l, ld, std::ldexp(1.0, -e));
   hipk::qr_thinQ(st_, Y, m, l, ld, R, w, ws);
+  if (e != 0 && R != nullptr) hipk::qr_scale(st_, R, l, l, l, std::ldexp(1.0, e));
   check_launch("qr_thinQ");
 }
 // CholeskyQR2 stopped one tall product short (Backend::qr_thinQ_deferred): T = Y R1^-1 stays in the QR workspace, X2 = R2^-1

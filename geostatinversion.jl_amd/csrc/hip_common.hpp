@@ -303,6 +303,12 @@ struct QrWork {
 int64_t qr_max_blocks(int64_t m);
 void qr_thinQ(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, double* R, const QrWork& w,
               double* gemm_ws);
+// the Householder tier's range guard: amax_ws[0] <- max |Y| (amax_ws: 1 + QR_AMAX_PARTS doubles), the exponent e of the
+// exact prescale 2^-e that max calls for (0: none), and A *= s
+constexpr int QR_AMAX_PARTS = 256;
+void qr_absmax(hipStream_t st, const double* Y, int64_t m, int64_t l, int64_t ld, double* amax_ws);
+int qr_prescale_exponent(double amax);
+void qr_scale(hipStream_t st, double* A, int64_t rows, int64_t cols, int64_t ld, double s);
 
 // ---- cholqr.hip ----
 size_t cholqr_small_doubles(int64_t l);

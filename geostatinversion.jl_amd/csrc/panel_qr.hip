@@ -215,6 +215,64 @@ static inline int grid_for(int64_t total, int cap = 2048) {
   return (int)g;
 }
 
+// ---- range guard (the QR tiers): qr_house_kernel forms alpha^2 + sigma from plain squares, so the panel as a
+// whole is brought to max|Y| in [1/2, 1) by an exact power of two when it lies outside [2^-400, 2^400] ----
+// partial[b] = max |Y| over workgroup b's share (fmax drops NaN: a NaN panel is left alone and stays NaN)
+__global__ __launch_bounds__(256) void qr_absmax_partial_kernel(const double* __restrict__ Y, int64_t ld, int64_t m,
+                                                                int64_t l, double* __restrict__ partial) {
+  __shared__ double s_max[4];
+  const int tid = threadIdx.x;
+  double v = 0.0;
+  for (int64_t c = 0; c < l; ++c) {
+    const double* col = Y + c * ld;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < m; i += (int64_t)gridDim.x * 256) v = fmax(v, fabs(col[i]));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+  if ((tid & 63) == 0) s_max[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) partial[blockIdx.x] = fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3]));
+}
+// one workgroup: out[0] = max of the nparts <= QR_AMAX_PARTS partials
+__global__ __launch_bounds__(256) void qr_absmax_final_kernel(const double* __restrict__ partial, int nparts,
+                                                              double* __restrict__ out) {
+  __shared__ double s_max[4];
+  const int tid = threadIdx.x;
+  double v = (tid < nparts) ? partial[tid] : 0.0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+  if ((tid & 63) == 0) s_max[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) out[0] = fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3]));
+}
+// A (rows x cols, ld) *= s, s a power of two
+__global__ void qr_scale_kernel(double* __restrict__ A, int64_t ld, int64_t rows, int64_t cols, double s) {
+  const int64_t total = rows * cols;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x)
+    A[(e % rows) + (e / rows) * ld] *= s;
+}
+
+void qr_absmax(hipStream_t st, const double* Y, int64_t m, int64_t l, int64_t ld, double* amax_ws) {
+  const int nparts = grid_for(m, QR_AMAX_PARTS);
+  hipLaunchKernelGGL(qr_absmax_partial_kernel, dim3(nparts), dim3(256), 0, st, Y, ld, m, l, amax_ws + 1);
+  hipLaunchKernelGGL(qr_absmax_final_kernel, dim3(1), dim3(256), 0, st, amax_ws + 1, nparts, amax_ws);
+}
+void qr_scale(hipStream_t st, double* A, int64_t rows, int64_t cols, int64_t ld, double s) {
+  hipLaunchKernelGGL(qr_scale_kernel, dim3(grid_for(rows * cols)), dim3(256), 0, st, A, ld, rows, cols, s);
+}
+// The exponent e of the prescale 2^-e for a panel with max|Y| = amax; 0 inside the window, for a zero panel and for
+// a panel that holds an infinity.  |e| <= 1000 keeps 2^-e and 2^e normal numbers; a subnormal amax still lands far
+// inside the window.
+int qr_prescale_exponent(double amax) {
+  if (!(amax > 0.0) || std::isinf(amax)) return 0;
+  if (amax >= 0x1p-400 && amax <= 0x1p400) return 0;
+  int e = std::ilogb(amax) + 1;
+  if (e > 1000) e = 1000;
+  if (e < -1000) e = -1000;
+  return e;
+}
+
 // C (mr x t, ld) <- (I - V op(T) V') C
 static void apply_block_reflector(hipStream_t st, const QrWork& w, int64_t mr, int b, const double* T,
                                   int transT, double* C, int64_t ldc, int64_t t, double* gemm_ws) {
