@@ -24,9 +24,10 @@ from . import gridcov as GridCov
 from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, gridcov_structuredgrid
 from . import kriging as Kriging
 from .kriging import (solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy, lowrank_preconditioner,
-                      Preconditioner, logdet, log_likelihood, solve_trace)
+                      Preconditioner, logdet, log_likelihood, solve_trace, estimate_field, linear_inversion,
+                      condition_on_linear_data)
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
-                   posterior_realizations)
+                   posterior_realizations, LinearDataOperator, linear_data_operator)
 
 __all__ = [
     "GsiError", "load", "LIB_PATH", "Context", "Operator", "DeviceMatrix", "dense_operator",
@@ -37,4 +38,5 @@ __all__ = [
     "DeviceBasis", "ShardedDeviceBasis", "LinearForwardModel", "posterior_variance", "posterior_realizations",
     "Kriging", "solve", "kriging_weights", "krige_to_grid", "condition_fields", "mat_axpy",
     "lowrank_preconditioner", "Preconditioner", "logdet", "log_likelihood", "solve_trace", "pivoted_cholesky", "principal_factor", "getxis_pivchol",
+    "LinearDataOperator", "linear_data_operator", "estimate_field", "linear_inversion", "condition_on_linear_data",
 ]

@@ -138,6 +138,10 @@ SIGNATURES = {
     "gsi_fwd_destroy": (C.c_int, [c_vp]),
     "gsi_fwd_info": (C.c_int, [c_vp, C.POINTER(c_i64), c_i64]),
     "gsi_fwd_apply": (C.c_int, [c_vp, c_vp, c_dp, c_i64, c_i64, c_dp, c_i64]),
+    "gsi_fwd_apply_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "gsi_fwd_adjoint_dev": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "gsi_fwd_adjoint_info": (C.c_int, [c_vp, C.POINTER(c_i64), c_i64]),
+    "gsi_op_fwd_cov": (C.c_int, [c_vp, C.POINTER(c_vp), c_vp, c_vp]),
     "gsi_pcga_forward_basis": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp, C.c_double, c_dp]),
     "gsi_basis_quadform": (C.c_int, [c_vp, c_vp, c_dp, c_i64, c_i64, C.c_int, c_dp, c_dp, c_dp, c_dp, C.POINTER(c_i64)]),
     "gsi_pcgamat_posterior": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_dp, C.POINTER(c_i64)]),

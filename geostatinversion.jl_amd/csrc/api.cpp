@@ -50,7 +50,9 @@ struct gsi_basis {
 
 struct gsi_fwd {
   gsi_ctx* ctx;
-  FwdModel m;
+  // shared with every OP_FWD_COV operator built on the model (gsi_op_fwd_cov): the last holder frees the resident arrays
+  std::shared_ptr<FwdModel> shared = std::make_shared<FwdModel>();
+  FwdModel& m = *shared;
 };
 
 struct gsi_sampler {
@@ -1861,6 +1863,85 @@ int gsi_fwd_apply(gsi_ctx* ctx, const gsi_fwd* fwd, const double* P, int64_t ldp
     REQUIRE(ncols >= 1 && ldp >= fwd->m.n && ldo >= fwd->m.nobs, "gsi_fwd_apply: bad ncols / leading dimension");
     fwd_apply(ctx->c, fwd->m, P, ldp, ncols, out, ldo);
     check_async_errors(ctx->c);
+  });
+}
+int gsi_fwd_apply_dev(gsi_ctx* ctx, const gsi_fwd* fwd, const gsi_mat* P, gsi_mat* out) {
+  return guarded([&] {
+    REQUIRE(ctx && fwd && P && out, "gsi_fwd_apply_dev: NULL argument");
+    REQUIRE(fwd->ctx == ctx, "gsi_fwd_apply_dev: the forward model belongs to another context");
+    REQUIRE(P->ctx == ctx && out->ctx == ctx, "gsi_fwd_apply_dev: P or out belongs to another context");
+    REQUIRE(P != out, "gsi_fwd_apply_dev: P and out must be different matrices");
+    const FwdModel& m = fwd->m;
+    if (P->rows != m.n || P->cols < 1)
+      throw Error(GSI_ERR_ARG, "gsi_fwd_apply_dev: P is " + std::to_string(P->rows) + " x " + std::to_string(P->cols) +
+                                   ", the model needs n = " + std::to_string(m.n) + " rows and at least one column");
+    if (out->rows != m.nobs || out->cols != P->cols)
+      throw Error(GSI_ERR_ARG, "gsi_fwd_apply_dev: out is " + std::to_string(out->rows) + " x " + std::to_string(out->cols) +
+                                   ", not nobs x columns of P = " + std::to_string(m.nobs) + " x " + std::to_string(P->cols));
+    fwd_apply_dev(ctx->c, m, P->buf.p, P->rows, P->cols, out->buf.p, out->rows);
+    check_async_errors(ctx->c);
+  });
+}
+int gsi_fwd_adjoint_dev(gsi_ctx* ctx, const gsi_fwd* fwd, const gsi_mat* V, gsi_mat* G) {
+  return guarded([&] {
+    REQUIRE(ctx && fwd && V && G, "gsi_fwd_adjoint_dev: NULL argument");
+    REQUIRE(fwd->ctx == ctx, "gsi_fwd_adjoint_dev: the forward model belongs to another context");
+    REQUIRE(V->ctx == ctx && G->ctx == ctx, "gsi_fwd_adjoint_dev: V or G belongs to another context");
+    REQUIRE(V != G, "gsi_fwd_adjoint_dev: V and G must be different matrices");
+    const FwdModel& m = fwd->m;
+    if (m.link != 0)
+      throw Error(GSI_ERR_ARG, "gsi_fwd_adjoint_dev: the model has link = " + std::to_string(m.link) +
+                                   " (exp): only a linear model (link = 0) has an adjoint");
+    if (V->rows != m.nobs || V->cols < 1)
+      throw Error(GSI_ERR_ARG, "gsi_fwd_adjoint_dev: V is " + std::to_string(V->rows) + " x " + std::to_string(V->cols) +
+                                   ", the model needs nobs = " + std::to_string(m.nobs) + " rows and at least one column");
+    if (G->rows != m.n || G->cols != V->cols)
+      throw Error(GSI_ERR_ARG, "gsi_fwd_adjoint_dev: G is " + std::to_string(G->rows) + " x " + std::to_string(G->cols) +
+                                   ", not n x columns of V = " + std::to_string(m.n) + " x " + std::to_string(V->cols));
+    fwd_adjoint(ctx->c, m, V->buf.p, V->rows, V->cols, G->buf.p, G->rows);
+    check_async_errors(ctx->c);
+  });
+}
+int gsi_fwd_adjoint_info(const gsi_fwd* fwd, int64_t* out, int64_t n_out) {
+  return guarded([&] {
+    REQUIRE(fwd && out && n_out >= 0, "gsi_fwd_adjoint_info: bad argument");
+    const FwdModel& m = fwd->m;
+    const FwdAdjointPlan& ap = m.aplan;
+    const int64_t v[7] = {m.aplan_built ? 1 : 0, m.adj_bytes, ap.nlong(), ap.nchunk(), ap.maxlen, m.adj_products,
+                          m.adj_host_products};
+    for (int64_t i = 0; i < n_out; ++i) out[i] = i < 7 ? v[i] : 0;
+  });
+}
+// A = H C H' (OP_FWD_COV): C = grid_op's covariance, whose plan is shared, H = the model's matrix, which is
+// shared too.  Nothing is allocated here: the model's arrays are resident already, its inverted index comes with the
+// first product.
+int gsi_op_fwd_cov(gsi_ctx* ctx, gsi_op** op, const gsi_op* grid_op, const gsi_fwd* fwd) {
+  return guarded([&] {
+    REQUIRE(ctx && op && grid_op && fwd, "gsi_op_fwd_cov: NULL argument");
+    *op = nullptr;
+    const Operator& C = grid_op->op;
+    REQUIRE(C.ctx == &ctx->c, "gsi_op_fwd_cov: the grid operator (grid_op) belongs to another context");
+    REQUIRE(fwd->ctx == ctx, "gsi_op_fwd_cov: the forward model (fwd) belongs to another context");
+    REQUIRE(C.kind == OP_FFT_COV && C.plan != nullptr,
+            "gsi_op_fwd_cov: grid_op must be an FFT covariance operator (gsi_op_fft_powerlaw[_fftrf], gsi_op_fft_gridcov[_table])");
+    REQUIRE(!ctx->c.comm, "gsi_op_fwd_cov: one GPU only -- not available on a context with a communicator");
+    REQUIRE(C.fft_ndims == 2 || C.fft_ndims == 3, "gsi_op_fwd_cov: grid_op must have 2 or 3 axes (a 1-D grid is not supported)");
+    const FwdModel& m = fwd->m;
+    if (m.n != C.n)
+      throw Error(GSI_ERR_ARG, "gsi_op_fwd_cov: fwd has n = " + std::to_string(m.n) + " cells, the grid of grid_op n_grid = " +
+                                   std::to_string(C.n));
+    if (m.link != 0)
+      throw Error(GSI_ERR_ARG, "gsi_op_fwd_cov: fwd has link = " + std::to_string(m.link) +
+                                   " (exp): H C H' needs a linear model (link = 0)");
+    std::unique_ptr<gsi_op> o(new gsi_op());
+    Operator& A = o->op;
+    A.ctx = &ctx->c; A.kind = OP_FWD_COV; A.m = m.nobs; A.n = m.nobs; A.row0 = 0; A.mloc = m.nobs; A.ld = 0;
+    A.fft_ndims = C.fft_ndims;
+    for (int a = 0; a < 3; ++a) A.fft_N[a] = C.fft_N[a];
+    A.plan = C.plan;
+    A.plan_ref = C.plan_ref;
+    A.fwd = fwd->shared;
+    *op = o.release();
   });
 }
 int gsi_pcga_forward_basis(gsi_ctx* ctx, const gsi_basis* basis, const gsi_fwd* fwd, const double* s, const double* X,

@@ -53,6 +53,26 @@ struct FwdProduct {
   int64_t ncols() const { return plain ? K : K + 3; }
 };
 
+// One adjoint product of that model, G (n x b, ld ldg) = H' V (nobs x b, ld ldv), every pointer in backend memory: the
+// inverted index of fwd_adjoint_plan.hpp (arrays as documented there) and the operands.  Every entry of G is written; a
+// cell no observation reaches gets +0.0.  partial: nchunk x b doubles for the chunk sums, or null: the backend takes a
+// temporary of its own.
+struct FwdAdjoint {
+  int64_t n = 0, nobs = 0, nnz = 0, chunk = 0, nlong = 0, nchunk = 0;
+  const int64_t* colptr = nullptr;
+  const int32_t* row = nullptr;
+  const double* val = nullptr;
+  const int32_t* long_col = nullptr;
+  const int64_t* long_chunk0 = nullptr;
+  const int64_t* chunk_off = nullptr;
+  const int32_t* chunk_len = nullptr;
+  const double* V = nullptr;
+  int64_t ldv = 0, b = 0;
+  double* G = nullptr;
+  int64_t ldg = 0;
+  double* partial = nullptr;
+};
+
 struct FftrfPointsPlan;   // fftrf_points.hpp
 
 // All pointers below are "backend memory" (HBM for the HIP backend), column-major fp64.
@@ -549,6 +569,9 @@ class Backend {
   // Returns the form that computed a.out -- 1: one lane per output, 2: one wave per segment -- or 0: "not mine", nothing
   // ran, and pcga.cpp forms the batch with pcga_params and multiplies on the host.
   virtual int fwd_products(const FwdProduct& a) { (void)a; return 0; }
+  // The adjoint product (FwdAdjoint above; fwd_adjoint.hip).  Returns 1 when it computed a.G, or 0: "not mine", nothing
+  // ran, and pcga.cpp downloads V and sums on the host in the plan's order (fwd_adjoint_host.hpp).
+  virtual int fwd_adjoint(const FwdAdjoint& a) { (void)a; return 0; }
 
   // ---- pcgadirect's saddle-point system by Cholesky ----
   // The m x n trapezoid A (m >= n, ld; lower triangle of the top n x n read) <- [L; (L^-1 B')'] in place, B = rows n .. m-1.

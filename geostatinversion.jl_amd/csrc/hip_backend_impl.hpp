@@ -279,6 +279,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   void basis_gemv_f32(const void* Z32, int64_t n, int64_t K, const double* w, double beta, const double* X,
                       double* y) override;
   int fwd_products(const FwdProduct& a) override;
+  int fwd_adjoint(const FwdAdjoint& a) override;
   int64_t chol_lower(double* A, int64_t m, int64_t n, int64_t ld) override;
   int64_t saddle_solve(const double* E, int64_t nobs, int64_t K, const double* HX, const double* R, bool r_diag, const double* b,
                        double* x, bool* singular) override;

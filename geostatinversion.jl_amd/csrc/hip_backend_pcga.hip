@@ -212,6 +212,25 @@ int HipBackend::fwd_products(const FwdProduct& a) {
   return form;
 }
 
+// The adjoint of the forward model (fwd_adjoint.hip): FADJ_MAX_COLS columns per launch; the chunk sums of the long columns
+// live in a pooled temporary of nchunk x (columns of the launch) unless the caller brought one.
+int HipBackend::fwd_adjoint(const FwdAdjoint& a) {
+  bind();
+  if (a.b <= 0 || a.n <= 0) return 1;
+  const int64_t step = a.b < hipk::FADJ_MAX_COLS ? a.b : hipk::FADJ_MAX_COLS;
+  Scratch partial(this, a.partial ? 0 : (size_t)a.nchunk * (size_t)step);
+  for (int64_t f0 = 0; f0 < a.b; f0 += step) {
+    FwdAdjoint s = a;
+    s.b = (a.b - f0 < step) ? (a.b - f0) : step;
+    s.V = a.V + f0 * a.ldv;
+    s.G = a.G + f0 * a.ldg;
+    s.partial = a.partial ? a.partial + f0 * a.nchunk : partial.p;
+    hipk::fwd_adjoint(st_, s);
+  }
+  check_launch("fwd_adjoint");
+  return 1;
+}
+
 // The blocked Cholesky and the saddle-point solve (chol_saddle.hip).  The pivot flag has a slot
 // of its own behind the error words: the caller gets the column as a return value, not through take_error.
 int64_t HipBackend::chol_lower(double* A, int64_t m, int64_t n, int64_t ld) {

@@ -6,7 +6,7 @@
 #include <cstddef>
 #include "pointcov.hpp"
 
-namespace gsi { struct FwdProduct; }   // backend.hpp
+namespace gsi { struct FwdProduct; struct FwdAdjoint; }   // backend.hpp
 
 namespace gsi { namespace hipk {
 
@@ -404,6 +404,10 @@ void fwd_lane(hipStream_t st, const FwdProduct& a);
 void fwd_wave(hipStream_t st, const FwdProduct& a);
 // out[r, c] = the partial sums of row r's segments, added in segment order (only when rows were split)
 void fwd_reduce(hipStream_t st, const FwdProduct& a);
+// ---- fwd_adjoint.hip: G = H' V through the inverted index of fwd_adjoint_plan.hpp (backend.hpp: FwdAdjoint) ----
+// throws std::runtime_error for a shape one launch cannot take (the caller batches the columns: FADJ_MAX_COLS)
+constexpr int64_t FADJ_MAX_COLS = 4096;
+void fwd_adjoint(hipStream_t st, const FwdAdjoint& a);
 
 // ---- chol_saddle.hip: blocked Cholesky and the saddle-point solve of pcgadirect ----
 // C (mc x nc lower trapezoid, mc >= nc) = beta C + alpha P P' (+ R): rmode 0 none, 1 dense lower (ld ldr), 2 diagonal entries.

@@ -4,6 +4,7 @@
 #include "pcga.hpp"
 #include "saddle_host.hpp"
 #include "posterior_host.hpp"
+#include "fwd_adjoint_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -327,17 +328,20 @@ void upload_as_doubles(Backend* be, Buf& dst, const T* src, size_t count) {
 
 // The backend's product: the caller has set the operand (Z, zbits, ldz, K, plain, and s, X, delta unless plain); this fills
 // in the model and the outputs, runs, and brings the nobs x a.ncols() results to out (host, ld ldo).
-bool fwd_on_backend(Backend* be, const FwdModel& F, FwdProduct& a, double* out, int64_t ldo) {
-  const int64_t nobs = F.nobs, nc = a.ncols();
-  Buf O(be, (size_t)nobs * nc), part;
-  if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * nc);
-  a.nobs = nobs; a.n = F.n; a.nnz = F.nnz; a.nseg = F.plan.nseg(); a.maxlen = F.plan.maxlen;
+void fwd_model_args(const FwdModel& F, FwdProduct& a) {
+  a.nobs = F.nobs; a.n = F.n; a.nnz = F.nnz; a.nseg = F.plan.nseg(); a.maxlen = F.plan.maxlen;
   a.segptr = reinterpret_cast<const int64_t*>(F.d_segptr.p);
   a.rowseg = F.plan.nsplit ? reinterpret_cast<const int64_t*>(F.d_rowseg.p) : nullptr;
   a.colidx = reinterpret_cast<const int32_t*>(F.d_colidx.p);
   a.vals = F.d_vals.p;
   a.w = F.w.empty() ? nullptr : F.d_w.p;
   a.link = F.link;
+}
+bool fwd_on_backend(Backend* be, const FwdModel& F, FwdProduct& a, double* out, int64_t ldo) {
+  const int64_t nobs = F.nobs, nc = a.ncols();
+  Buf O(be, (size_t)nobs * nc), part;
+  if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * nc);
+  fwd_model_args(F, a);
   a.out = O.p; a.ldo = nobs; a.partial = part.p;
   const int form = be->fwd_products(a);
   if (form == 0) return false;
@@ -443,6 +447,90 @@ void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int6
     if (fwd_on_backend(be, F, a, out, ldo)) return;
   }
   fwd_on_host(F, P, ldp, ncols, out, ldo);
+}
+
+void fwd_apply_dev(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo) {
+  Backend* be = c.be.get();
+  const int64_t n = F.n, nobs = F.nobs;
+  F.products += 1;
+  if (!env_forces_host("GSI_FWD_HOST")) {
+    Buf part;
+    if (F.plan.nsplit) part = Buf(be, (size_t)F.plan.nseg() * ncols);
+    FwdProduct a;
+    a.Z = P; a.zbits = 64; a.ldz = ldp; a.K = ncols; a.plain = true;
+    fwd_model_args(F, a);
+    a.out = out; a.ldo = ldo; a.partial = part.p;
+    const int form = be->fwd_products(a);
+    if (form != 0) { F.last_form = form; return; }
+  }
+  std::vector<double> Ph((size_t)n * ncols), Oh((size_t)nobs * ncols);
+  be->download2d(Ph.data(), n, P, ldp, n, ncols);
+  fwd_on_host(F, Ph.data(), n, ncols, Oh.data(), nobs);
+  be->upload2d(out, ldo, Oh.data(), nobs, nobs, ncols);
+}
+
+// ---- the adjoint of the forward model -----------------------------------------------------------
+namespace {
+// the index resident in backend memory: one allocation, integers as the bytes of doubles
+void fwd_adjoint_upload(Backend* be, const FwdModel& F) {
+  const FwdAdjointPlan& ap = F.aplan;
+  auto words = [](size_t bytes) { return (bytes + 7) / 8; };
+  size_t total = 0;
+  auto take = [&](size_t w) { const size_t o = total; total += w; return o; };
+  const size_t nnz = (size_t)ap.nnz, nl = (size_t)ap.nlong(), nc = (size_t)ap.nchunk();
+  const size_t o_ptr = take((size_t)ap.n + 1), o_val = take(nnz), o_row = take(words(4 * nnz)), o_lchunk = take(nl + 1),
+               o_coff = take(nc), o_lcol = take(words(4 * nl)), o_clen = take(words(4 * nc));
+  F.d_adj = Buf(be, total);
+  double* d = F.d_adj.p;
+  std::vector<double> packed;
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes == 0) return;
+    packed.assign(words(bytes), 0.0);
+    std::memcpy(packed.data(), src, bytes);
+    be->upload2d(d + off, (int64_t)packed.size(), packed.data(), (int64_t)packed.size(), (int64_t)packed.size(), 1);
+  };
+  put(o_ptr, ap.colptr.data(), 8 * ((size_t)ap.n + 1));
+  put(o_val, ap.val.data(), 8 * nnz);
+  put(o_row, ap.row.data(), 4 * nnz);
+  put(o_lchunk, ap.long_chunk0.data(), 8 * (nl + 1));
+  put(o_coff, ap.chunk_off.data(), 8 * nc);
+  put(o_lcol, ap.long_col.data(), 4 * nl);
+  put(o_clen, ap.chunk_len.data(), 4 * nc);
+  FwdAdjoint& a = F.adev;
+  a.n = ap.n; a.nobs = ap.nobs; a.nnz = ap.nnz; a.chunk = ap.chunk; a.nlong = ap.nlong(); a.nchunk = ap.nchunk();
+  a.colptr = reinterpret_cast<const int64_t*>(d + o_ptr);
+  a.val = d + o_val;
+  a.row = reinterpret_cast<const int32_t*>(d + o_row);
+  a.long_chunk0 = reinterpret_cast<const int64_t*>(d + o_lchunk);
+  a.chunk_off = reinterpret_cast<const int64_t*>(d + o_coff);
+  a.long_col = reinterpret_cast<const int32_t*>(d + o_lcol);
+  a.chunk_len = reinterpret_cast<const int32_t*>(d + o_clen);
+  F.adj_bytes = (int64_t)(8 * total);
+}
+}  // namespace
+
+void fwd_adjoint(Context& c, const FwdModel& F, const double* V, int64_t ldv, int64_t b, double* G, int64_t ldg) {
+  if (F.link != 0)
+    throw Error(GSI_ERR_ARG, "gsi_fwd_adjoint: the model has link = " + std::to_string(F.link) +
+                                 " (exp): only a linear model (link = 0) has an adjoint");
+  if (b <= 0) return;
+  Backend* be = c.be.get();
+  if (!F.aplan_built) {
+    F.aplan = fwd_adjoint_plan(F.nobs, F.n, F.rowptr.data(), F.colidx.data(), F.vals.data(), F.w.empty() ? nullptr : F.w.data());
+    F.aplan_built = true;
+  }
+  F.adj_products += 1;
+  if (!env_forces_host("GSI_FWD_HOST")) {
+    if (F.d_adj.p == nullptr) fwd_adjoint_upload(be, F);
+    FwdAdjoint a = F.adev;
+    a.V = V; a.ldv = ldv; a.b = b; a.G = G; a.ldg = ldg; a.partial = nullptr;
+    if (be->fwd_adjoint(a) != 0) return;
+  }
+  std::vector<double> Vh((size_t)F.nobs * b), Gh((size_t)F.n * b);
+  be->download2d(Vh.data(), F.nobs, V, ldv, F.nobs, b);
+  fwd_adjoint_host::apply(F.aplan, Vh.data(), F.nobs, b, Gh.data(), F.n);
+  be->upload2d(G, ldg, Gh.data(), F.n, F.n, b);
+  F.adj_host_products += 1;
 }
 
 }  // namespace gsi

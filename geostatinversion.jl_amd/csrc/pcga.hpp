@@ -5,6 +5,7 @@
 #pragma once
 #include "pipeline.hpp"
 #include "fwd_plan.hpp"
+#include "fwd_adjoint_plan.hpp"
 
 namespace gsi {
 
@@ -76,6 +77,13 @@ struct FwdModel {
   // what ran (gsi_fwd_info): form of the last product (0 none yet, 1 lane-per-output, 2 wave-per-segment, 3 host path),
   // products that took the host path, products in total
   mutable int64_t last_form = 0, host_products = 0, products = 0;
+  // The adjoint H' (DESIGN.md section 4.6l): the inverted index of fwd_adjoint_plan.hpp.  Built by the first adjoint
+  // product, not by fwd_create; uploaded (one allocation, d_adj; adev points into it) by the first one that asks the backend.
+  mutable FwdAdjointPlan aplan;
+  mutable bool aplan_built = false;
+  mutable Buf d_adj;
+  mutable FwdAdjoint adev;
+  mutable int64_t adj_bytes = 0, adj_products = 0, adj_host_products = 0;
 };
 enum : int64_t { FWD_DEFAULT_SEG_LIMIT = 16384 };   // nonzeros per segment, from the sweep of DESIGN.md section 4.7b; GSI_FWD_SEG overrides
 // Validates (GSI_ERR_ARG naming the offending row or entry, before anything is allocated), plans and uploads.
@@ -86,5 +94,12 @@ void fwd_create(Context& c, FwdModel& F, int64_t nobs, int64_t n, const int64_t*
 void fwd_forward_basis(Context& c, const FwdModel& F, BasisRef Z, const double* s, const double* X, double delta, double* out);
 // out (host, nobs x ncols, ld ldo): column c = h(P[:, c]) for the host matrix P (n x ncols, ld ldp)
 void fwd_apply(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo);
+// the same with P (n x ncols, ld ldp) and out (nobs x ncols, ld ldo) in backend memory: nothing crosses the host link on the
+// backend's path; on the host path (the backend declined, or GSI_FWD_HOST=1) P is downloaded and out uploaded
+void fwd_apply_dev(Context& c, const FwdModel& F, const double* P, int64_t ldp, int64_t ncols, double* out, int64_t ldo);
+// G (n x b, ld ldg) = H' V (nobs x b, ld ldv), both in backend memory, H = diag-weighted CSR matrix of a model with link 0
+// (link 1: GSI_ERR_ARG).  Every entry of G is written; sums in the order of fwd_adjoint_plan.hpp on either path:
+// Backend::fwd_adjoint, or -- when it declines or GSI_FWD_HOST=1 -- download, fwd_adjoint_host.hpp, upload.
+void fwd_adjoint(Context& c, const FwdModel& F, const double* V, int64_t ldv, int64_t b, double* G, int64_t ldg);
 
 }  // namespace gsi

@@ -11,6 +11,7 @@
 //   final Q      TSQR: local Householder QR, AllGather of the l x l R factors, replicated
 //                QR of the stack, local fix-up Q_g <- Q_g * Q2_g
 #include "pipeline.hpp"
+#include "pcga.hpp"
 #include "lsqr_state.hpp"
 #include "block_cg_host.hpp"
 #include "block_pcg_host.hpp"
@@ -130,10 +131,45 @@ static void fft_at_mul(const Operator& A, const double* X, int64_t ldx, int64_t 
   }
 }
 
+// OP_FWD_COV: Y (nobs x l) = H C H' X, one rank.  As fft_at_mul with the model's products in
+// place of the interpolation's: the adjoint H' into G (fwd_adjoint.hip), the grid product into H, the forward product
+// (pcga_forward.hip, its output left in backend memory) into the caller's rows, lb columns at a time.  lb is even and keeps
+// both n x lb panels within 2 GiB; GSI_FWD_COV_BATCH=<b> (read at every call) overrides it.  A is symmetric to rounding: A' X
+// is the same product.  Profiling: H' as gemm_t, C as gemm_n, H as other (tools/fwd_cov_bench.py).
+static int64_t fwd_cov_batch(int64_t n, int64_t l) {
+  int64_t lb = (((int64_t)2 << 30) / (int64_t)sizeof(double)) / (2 * std::max<int64_t>(n, 1));
+  if (const char* e = getenv("GSI_FWD_COV_BATCH")) { if (atoll(e) >= 1) lb = atoll(e); }
+  lb += lb & 1;
+  lb = std::min(lb, l + (l & 1));
+  return std::max<int64_t>(lb, 2);
+}
+static void fwd_cov_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Y, int64_t ldy) {
+  Context& c = *A.ctx;
+  Backend* be = c.be.get();
+  if (c.comm) throw Error(GSI_ERR_INTERNAL, "an FFT covariance under a forward model runs on one rank only");
+  if (l <= 0) return;
+  const FwdModel& F = *A.fwd;
+  const int64_t n = A.fft_N[0] * A.fft_N[1] * A.fft_N[2], lb = fwd_cov_batch(n, l);
+  Buf G(be, (size_t)n * lb), H(be, (size_t)n * lb);
+  for (int64_t c0 = 0; c0 < l; c0 += lb) {
+    const int64_t b = std::min(lb, l - c0);
+    const bool first = c0 == 0;
+    auto stage = [&](Phase ph, auto&& f) {      // one counted entry per product and phase, the later batches add their time
+      be->phase_begin(ph);
+      try { f(); } catch (...) { be->phase_end(ph); throw; }
+      if (first) be->phase_end(ph); else be->phase_end_more(ph);
+    };
+    stage(PH_GEMM_T, [&] { fwd_adjoint(c, F, X + c0 * ldx, ldx, b, G.p, n); });
+    stage(PH_GEMM_N, [&] { be->fftcov_apply(A.plan, b, G.p, n, H.p, n); });
+    stage(PH_OTHER, [&] { fwd_apply_dev(c, F, H.p, n, b, Y + c0 * ldy, ldy); });
+  }
+}
+
 void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Yloc, int64_t ldy) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();
   if (A.kind == OP_FFT_COV_AT) { fft_at_mul(A, X, ldx, l, Yloc, ldy); return; }
+  if (A.kind == OP_FWD_COV) { fwd_cov_mul(A, X, ldx, l, Yloc, ldy); return; }
   // a rank without rows (m < rank * ceil(m / G)) has nothing to compute, but it still takes part in every
   // collective below: only the collective-free operator kinds may leave early
   if (A.mloc == 0 && A.kind != OP_LOWRANK && !(A.kind == OP_FFT_COV && c.comm)) return;
@@ -307,6 +343,7 @@ void op_mul_t(const Operator& A, const double* Xloc, int64_t ldx, int64_t l, dou
   Context& c = *A.ctx;
   Backend* be = c.be.get();
   if (A.kind == OP_FFT_COV_AT) { fft_at_mul(A, Xloc, ldx, l, Z, ldz); return; }   // symmetric to rounding, as OP_FFT_COV
+  if (A.kind == OP_FWD_COV) { fwd_cov_mul(A, Xloc, ldx, l, Z, ldz); return; }     // the same
   if (A.kind == OP_FFT_COV) {     // symmetric: A' X = A X
     if (!c.comm) {
       ScopedPhase ph(be, PH_GEMM_T);
@@ -393,6 +430,7 @@ static Buf op_mul_t_sharded(const Operator& A, const double* Xloc, int64_t ldx, 
   const int G = c.nranks();
   const int64_t n = A.n, pad = (n + G - 1) / G;
   if (A.kind == OP_FFT_COV_AT) throw Error(GSI_ERR_INTERNAL, "an FFT covariance at scattered points runs on one rank only");
+  if (A.kind == OP_FWD_COV) throw Error(GSI_ERR_INTERNAL, "an FFT covariance under a forward model runs on one rank only");
   if (A.kind == OP_LOWRANK) {
     Buf T(be, (size_t)A.N * l);
     lowrank_StX(A, Xloc, ldx, l, T.p);

@@ -54,7 +54,10 @@ struct Context {
   int nranks() const { return comm ? comm->nranks : 1; }
 };
 
-enum OpKind { OP_DENSE = 0, OP_LOWRANK = 1, OP_GRIDCOV_IMPLICIT = 2, OP_FFT_COV = 3, OP_POINTCOV = 4, OP_FFT_COV_AT = 5 };
+enum OpKind { OP_DENSE = 0, OP_LOWRANK = 1, OP_GRIDCOV_IMPLICIT = 2, OP_FFT_COV = 3, OP_POINTCOV = 4, OP_FFT_COV_AT = 5,
+              OP_FWD_COV = 6 };
+
+struct FwdModel;   // pcga.hpp
 
 // A linear operator m x n; this rank holds rows [row0, row0 + mloc).
 struct Operator {
@@ -79,6 +82,10 @@ struct Operator {
   // index, resident for the operator's lifetime; at_info = what that call reported.
   void* at = nullptr;
   int64_t at_info[4] = {0, 0, 0, 0};
+  // OP_FWD_COV (nobs x nobs, one rank): A = H C H', C the grid operator whose plan is shared above, H the sparse matrix of a
+  // forward model (gsi_fwd, link 0) over the n = prod fft_N cells of that grid.  The model is shared with its gsi_fwd handle:
+  // its resident arrays live until the last of the two is destroyed, in whatever order.
+  std::shared_ptr<const FwdModel> fwd;
   // OP_DENSE whose rows are still crossing PCIe (gsi_randsvd_dense_host / gsi_rangefinder_dense_host): the handle of
   // Backend::upload2d_begin and its row-block height.  The FIRST product A*X consumes it -- block by block as the rows land,
   // bit-identical to the product of the resident matrix -- and clears it; the entry point's guard ends the upload on every

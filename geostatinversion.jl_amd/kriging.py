@@ -389,6 +389,112 @@ def krige_to_grid(at_op, xi, beta=None, drift_grid=None):
     return out[:, 0].copy() if xv.ndim == 1 else out
 
 
+def _prior_adjoint(op, xi):
+    """C H' xi for a `LinearDataOperator` and a DeviceMatrix xi (nobs x b): a new DeviceMatrix (n_grid x b)."""
+    G = op.model.adjoint(xi)
+    try:
+        return _grid_product(op, G)
+    finally:
+        G.close()
+
+
+def estimate_field(op, xi, beta=None, drift_grid=None):
+    """The best estimate on the grid of a `LinearDataOperator` (`linear_data_operator`): X beta + C H' xi, from the model's
+    adjoint and the grid operator's device product.  `xi`: nobs weights (or nobs x k); `drift_grid`: n_grid x p, the drift
+    functions X at the cells.  Returns a host array of n_grid values (or n_grid x k), vec() order."""
+    xv = np.asarray(xi, dtype=np.float64)
+    Xi = DeviceMatrix.from_host(op.ctx, L.fmat(xv, "xi"))
+    try:
+        S = _prior_adjoint(op, Xi)
+        try:
+            out = S.to_host()
+        finally:
+            S.close()
+    finally:
+        Xi.close()
+    if beta is not None and np.size(beta) > 0:
+        if drift_grid is None:
+            raise ValueError("beta needs drift_grid, the drift functions at the grid cells")
+        out = out + (np.asarray(drift_grid, dtype=np.float64).reshape(out.shape[0], -1) @ np.asarray(beta, dtype=np.float64)
+                     ).reshape(out.shape[0], -1)
+    return out[:, 0].copy() if xv.ndim == 1 else out
+
+
+def linear_inversion(grid_op, model, y, noise, drift_grid=None, precond=None, return_info=False, **cg):
+    """The exact linear geostatistical inversion of the data `y` = H s + v of a `LinearForwardModel` (identity link), with the
+    prior s ~ N(X beta, C), C the covariance of the FFT operator `grid_op`, beta unknown, and v ~ N(0, diag(noise)):
+        (H C H' + R) xi + H X beta = y,   (H X)' xi = 0,   s_hat = X beta + C H' xi.
+    No rank-K basis, no finite differences, no sampling: the operator is `linear_data_operator(grid_op, model)` and the
+    system is solved as `kriging_weights` solves it, by ONE solve of the 1 + p columns [y, H X]; H X is `model.apply_dev` of
+    `drift_grid` (n_grid x p, the drift functions at the cells; None: no drift, beta empty).  `precond`: a `Preconditioner`
+    built on such an operator; `cg`: `tol`, `maxiter`, `strict` of `solve`.  Returns `s_hat` (n_grid, host), `xi`, `beta`;
+    with `return_info` also the report of `solve`."""
+    from .pcga import linear_data_operator
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    if yv.size != model.nobs:
+        raise ValueError(f"y must hold one value per observation of the model, {model.nobs}")
+    op = linear_data_operator(grid_op, model)
+    try:
+        X = None if drift_grid is None else L.fmat(np.asarray(drift_grid, dtype=np.float64).reshape(model.n, -1), "drift_grid")
+        B = yv[:, None] if X is None else np.column_stack([yv, model.apply_dev(X)])
+        S, rep = solve(op, B, diag=noise, precond=precond, return_info=True, **cg)
+        My, MG = S[:, 0], S[:, 1:]
+        if X is None:
+            xi, beta = My.copy(), np.zeros(0)
+        else:
+            HX = B[:, 1:]
+            beta = np.linalg.solve(HX.T @ MG, HX.T @ My)
+            xi = My - MG @ beta
+        s_hat = estimate_field(op, xi, beta, X)
+    finally:
+        op.close()
+    return (s_hat, xi, beta, rep) if return_info else (s_hat, xi, beta)
+
+
+def condition_on_linear_data(op, F, y, noise, eps=None, seed=None, **cg):
+    """Conditional simulation on the data of a linear forward model, by residual kriging.  `op`: a `LinearDataOperator`
+    H C H'; `F`: a `DeviceMatrix` of n_grid x b holding zero-mean unconditional fields with the grid operator's covariance
+    C; `y`: the nobs data; `noise`: their error variances D (a scalar or nobs values).  Returns
+        F + C H' (H C H' + D)^-1 (y 1' + sqrt(D) .* eps - H F)
+    as a new `DeviceMatrix`; `F` is not modified.  `eps`: nobs x b standard normals, given, or drawn by `RandMatFact.randn`
+    (after `RandMatFact.seed(seed)` if `seed` is given).  Forward product, solve, adjoint, grid product, axpy -- all on the
+    device: only the nobs x b right-hand side crosses the host link, nothing of the grid's size."""
+    ctx = op.ctx
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    m, b = yv.size, F.shape[1]
+    if op.shape[0] != m:
+        raise ValueError(f"y must hold one value per observation of op, {op.shape[0]}")
+    d = _diag_arg(noise, m)
+    if d is None:
+        d = np.zeros(m)
+    if eps is None:
+        if seed is not None:
+            RMF.seed(seed)
+        eps = RMF.randn(m, b)
+    E = np.asarray(eps, dtype=np.float64).reshape(m, -1)
+    if E.shape != (m, b):
+        raise ValueError(f"eps must be nobs x b = {m} x {b}")
+    handles = []
+    try:
+        rhs = DeviceMatrix.from_host(ctx, yv[:, None] + np.sqrt(d)[:, None] * E)
+        handles.append(rhs)
+        HF = op.model.apply_dev(F)
+        handles.append(HF)
+        mat_axpy(-1.0, HF, rhs)
+        xi = solve(op, rhs, diag=d, **cg)
+        handles.append(xi)
+        out = _prior_adjoint(op, xi)
+        try:
+            mat_axpy(1.0, F, out)
+        except Exception:
+            out.close()
+            raise
+        return out
+    finally:
+        for h in handles:
+            h.close()
+
+
 def condition_fields(at_op, F, y, noise, eps=None, seed=None, **cg):
     """Conditional simulation by residual kriging.  `F`: a `DeviceMatrix` of n_grid x b holding zero-mean unconditional
     fields with the grid operator's covariance C (e.g. `GridCovSampler.fields` of the same kind, ell and sigma2);

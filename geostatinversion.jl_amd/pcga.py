@@ -8,7 +8,7 @@ the device straight from the resident basis, and the perturbation batch is never
 import numpy as np
 
 from . import _lib as L
-from .context import default_context
+from .context import default_context, Operator
 from .lowrank import PCGALowRankMatrix
 
 SQRT_EPS = float(np.sqrt(np.finfo(np.float64).eps))
@@ -243,6 +243,79 @@ class LinearForwardModel:
 
     def __call__(self, s):
         return self.apply(np.asarray(s, dtype=np.float64).reshape(-1, 1))[:, 0]
+
+    def _dev(self, fn, X, rows_in, rows_out, what):
+        """out = fn(X) for a `DeviceMatrix` (a new `DeviceMatrix`) or a host vector / matrix (a host array of the same kind)."""
+        from .context import DeviceMatrix
+        ctx, lib = self.ctx, self.ctx.lib
+        if isinstance(X, DeviceMatrix):
+            out = DeviceMatrix(ctx, rows_out, X.shape[1])
+            try:
+                L.check(fn(ctx.h, self.h, X.h, out.h), lib)
+            except Exception:
+                out.close()
+                raise
+            return out
+        Xf = L.fmat(X, what)
+        if Xf.shape[0] != rows_in:
+            raise ValueError(f"{what} must have {rows_in} rows")
+        Xd = DeviceMatrix.from_host(ctx, Xf)
+        try:
+            out = self._dev(fn, Xd, rows_in, rows_out, what)
+            try:
+                h = out.to_host()
+            finally:
+                out.close()
+        finally:
+            Xd.close()
+        return h[:, 0].copy() if np.ndim(X) == 1 else h
+
+    def apply_dev(self, P):
+        """h of every column of P (n x b) with P and the result (nobs x b) resident on the device (`gsi_fwd_apply_dev`): a
+        `DeviceMatrix` gives a new `DeviceMatrix`; a host vector or matrix is uploaded and the result downloaded."""
+        return self._dev(self.ctx.lib.gsi_fwd_apply_dev, P, self.n, self.nobs, "P")
+
+    def adjoint(self, V):
+        """H' V for V (nobs x b): n x b (`gsi_fwd_adjoint_dev`), H the matrix of this model with its
+        weights folded in.  A `DeviceMatrix` gives a new `DeviceMatrix`, a host vector or matrix a host array.  No atomics: the
+        sums follow the inverted index built by the first call, so results are bitwise reproducible.  `link="exp"` has no
+        adjoint: `GsiError`."""
+        return self._dev(self.ctx.lib.gsi_fwd_adjoint_dev, V, self.nobs, self.n, "V")
+
+    def adjoint_info(self):
+        """`gsi_fwd_adjoint_info` as a dict: `built` (the inverted index exists), `resident_bytes`, `long_columns`, `chunks`,
+        `longest_list`, `products`, `host_products`."""
+        import ctypes as C
+        out = (C.c_int64 * 7)()
+        L.check(self.ctx.lib.gsi_fwd_adjoint_info(self.h, out, 7), self.ctx.lib)
+        keys = ["built", "resident_bytes", "long_columns", "chunks", "longest_list", "products", "host_products"]
+        d = {k: int(v) for k, v in zip(keys, out)}
+        d["built"] = bool(d["built"])
+        return d
+
+
+class LinearDataOperator(Operator):
+    """`linear_data_operator`'s result: the nobs x nobs operator H C H' (`gsi_op_fwd_cov`).  `grid_op` and `model` stay
+    referenced."""
+
+    def __init__(self, ctx, h, grid_op, model):
+        super().__init__(ctx, h)
+        self.grid_op, self.model = grid_op, model
+
+
+def linear_data_operator(grid_op, model):
+    """The covariance of the data of a linear forward model under an FFT grid covariance (`gsi_op_fwd_cov`; DESIGN.md
+    section 4.6l): A = H C H', nobs x nobs, with C the covariance of `grid_op` (from `fft_gridcov_operator` or
+    `fft_powerlaw_operator`, 2 or 3 axes) and H the matrix of `model`, a `LinearForwardModel` with the identity link over the
+    cells of that grid in vec() order -- point samples, block averages, ray integrals.  Matrix-free, no rank cap, no sampling
+    noise: one product is `model.adjoint`, the grid product and `model.apply_dev`, O(n log n + nnz) per column, with nothing
+    crossing the host link.  One GPU only.  Usable wherever an `Operator` is: `solve`, `lowrank_preconditioner`, `logdet`,
+    `log_likelihood`, `randsvd`; `Kriging.linear_inversion` builds the exact linear geostatistical inversion on it."""
+    import ctypes as C
+    ctx = model.ctx
+    h = C.c_void_p()
+    L.check(ctx.lib.gsi_op_fwd_cov(ctx.h, C.byref(h), grid_op.h, model.h), ctx.lib)
+    return LinearDataOperator(ctx, h, grid_op, model)
 
 
 class _ReducedForwardModel:
