@@ -1,5 +1,5 @@
 // api.cpp -- the C ABI of include/gsi_hip.h: argument checking, host<->device staging and
-// error translation around pipeline.cpp and pcga.cpp.  No C++ exception crosses the boundary.
+// error translation around pipeline.cpp, solvers.cpp and pcga.cpp.  No C++ exception crosses the boundary.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../include/gsi_hip.h"
 #include "pcga.hpp"
+#include "solvers.hpp"
 #include "pointcov.hpp"
 #include "fftrf_points.hpp"
 #include "cg_state.hpp"
@@ -1363,71 +1364,106 @@ int gsi_op_lowrank_solve(gsi_ctx* ctx, const gsi_op* op, const double* b, double
 }
 
 // ---- kriging systems: block CG on any operator ------------------------------------------
+//      plain (gsi_op_solve_cg, gsi_op_solve), preconditioned (gsi_op_solve_pcg, gsi_op_solve_pcg_host)
+//      and traced (gsi_op_solve_trace; section 4.6k).  info has 4, 6 and 7 entries for the three: INFO_* below, and nothing
+//      here writes beyond the length an entry point passes.
 namespace {
-// the checks that need no memory, the upload of diag, the solve on resident panels, and the report: info, relres and iters
-// are filled before a breakdown is raised
-void solve_cg_resident(gsi_ctx* ctx, const Operator& A, const double* diag, const double* Bd, double* Xd, int64_t b, double tol,
-                       int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+enum { INFO_CG = 4, INFO_PCG = 6, INFO_TRACE = 7 };
+// the checks that need no memory; info is cleared first.  pc may be null unless need_pc.
+void check_solve_args(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, bool need_pc, int64_t b,
+                      double tol, int64_t maxiter, int64_t* info, int ninfo) {
+  if (info) for (int i = 0; i < ninfo; ++i) info[i] = 0;
+  REQUIRE(ctx && op, "gsi_op_solve: ctx or op is NULL");
+  REQUIRE(op->op.ctx == &ctx->c, "gsi_op_solve: op belongs to another context");
+  block_cg_check(op->op, nullptr, b, tol, maxiter);
+  if (diag)
+    for (int64_t i = 0; i < op->op.n; ++i)
+      if (!(diag[i] >= 0.0 && diag[i] <= 1.79769313486231570815e308))
+        throw Error(GSI_ERR_ARG, "gsi_op_solve: diag[" + std::to_string(i) + "] is negative or not finite");
+  REQUIRE(pc || !need_pc, "gsi_op_solve_pcg: pc is NULL");
+  if (pc) {
+    REQUIRE(pc->ctx == ctx, "gsi_op_solve_pcg: pc belongs to another context");
+    block_cg_check(op->op, &pc->pc, b, tol, maxiter);          // (what it refuses about pc: the rest has passed above)
+  }
+}
+// B and X of the entry points that take resident panels
+void check_resident_panels(const std::string& fn, gsi_ctx* ctx, const Operator& A, const gsi_mat* B, const gsi_mat* X) {
+  REQUIRE(B->ctx == ctx && X->ctx == ctx, fn + ": B or X belongs to another context");
+  REQUIRE(B->rows == A.n, fn + ": B must have size(A, 1) rows");
+  REQUIRE(X->rows == A.n && X->cols == B->cols, fn + ": X must have the shape of B");
+  REQUIRE(X != B && X->buf.p != B->buf.p, fn + ": X must not be B");
+}
+// the upload of diag, the solve on resident panels, and the report: info (ninfo entries; the seventh needs a trace), relres
+// and iters are filled before a breakdown is raised.  who: how the message of a breakdown begins.
+void solve_resident(const char* who, gsi_ctx* ctx, const Operator& A, const double* diag, const gsi_precond* pc, const double* Bd,
+                    double* Xd, int64_t b, double tol, int64_t maxiter, int64_t* info, int ninfo, double* relres, int64_t* iters,
+                    CgTrace* trace) {
   Backend* be = ctx->c.be.get();
   Buf dd;
   if (diag) {
     dd = Buf(be, (size_t)A.n);
     be->upload2d(dd.p, A.n, diag, A.n, A.n, 1);
   }
-  const BlockCgInfo r = block_cg(A, diag ? dd.p : nullptr, Bd, Xd, b, tol, maxiter, relres, iters);
-  if (info) { info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column; }
+  const BlockCgInfo r = block_cg(A, diag ? dd.p : nullptr, pc ? &pc->pc : nullptr, Bd, Xd, b, tol, maxiter, relres, iters, trace);
+  if (info) {
+    const int64_t v[INFO_TRACE] = {r.products, r.converged, r.path, r.breakdown_column, r.breakdown_kind, r.K,
+                                   trace ? trace->truncated : 0};
+    for (int i = 0; i < ninfo; ++i) info[i] = v[i];
+  }
   check_async_errors(ctx->c);
   if (r.breakdown_column != 0)
-    throw Error(GSI_ERR_NOT_POSDEF, "conjugate gradients: A + diag is not positive definite along the search direction of column " +
-                                        std::to_string(r.breakdown_column));
+    throw Error(GSI_ERR_NOT_POSDEF, std::string(who) + ": " +
+                                        (r.breakdown_kind == 2 ? "r'z is not positive and finite (the preconditioner is not positive definite)"
+                                                               : "A + diag is not positive definite along the search direction") +
+                                        " of column " + std::to_string(r.breakdown_column));
 }
-void check_solve_args(gsi_ctx* ctx, const gsi_op* op, const double* diag, int64_t b, double tol, int64_t maxiter, int64_t* info) {
-  if (info) info[0] = info[1] = info[2] = info[3] = 0;
-  REQUIRE(ctx && op, "gsi_op_solve: ctx or op is NULL");
-  REQUIRE(op->op.ctx == &ctx->c, "gsi_op_solve: op belongs to another context");
-  block_cg_check(op->op, b, tol, maxiter);
-  if (diag)
-    for (int64_t i = 0; i < op->op.n; ++i)
-      if (!(diag[i] >= 0.0 && diag[i] <= 1.79769313486231570815e308))
-        throw Error(GSI_ERR_ARG, "gsi_op_solve: diag[" + std::to_string(i) + "] is negative or not finite");
-}
-}  // namespace
-
-int gsi_op_solve_cg(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_mat* B, gsi_mat* X, double tol,
-                    int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+// the entry points that stage B and X through the host: fn names the entry point in what it refuses
+int solve_staged(const std::string& fn, const char* who, gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc,
+                 bool need_pc, const double* B, int64_t ldb, int64_t b, double* X, int64_t ldx, double tol, int64_t maxiter,
+                 int64_t* info, int ninfo, double* relres, int64_t* iters) {
   return guarded([&] {
-    REQUIRE(B && X, "gsi_op_solve_cg: B or X is NULL");
-    check_solve_args(ctx, op, diag, B->cols, tol, maxiter, info);
+    REQUIRE(B && X, fn + ": B or X is NULL");
+    check_solve_args(ctx, op, diag, pc, need_pc, b, tol, maxiter, info, ninfo);
     const Operator& A = op->op;
-    REQUIRE(B->ctx == ctx && X->ctx == ctx, "gsi_op_solve_cg: B or X belongs to another context");
-    REQUIRE(B->rows == A.n, "gsi_op_solve_cg: B must have size(A, 1) rows");
-    REQUIRE(X->rows == A.n && X->cols == B->cols, "gsi_op_solve_cg: X must have the shape of B");
-    REQUIRE(X != B && X->buf.p != B->buf.p, "gsi_op_solve_cg: X must not be B");
-    solve_cg_resident(ctx, A, diag, B->buf.p, X->buf.p, B->cols, tol, maxiter, info, relres, iters);
-  });
-}
-
-int gsi_op_solve(gsi_ctx* ctx, const gsi_op* op, const double* diag, const double* B, int64_t ldb, int64_t b, double* X,
-                 int64_t ldx, double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
-  return guarded([&] {
-    REQUIRE(B && X, "gsi_op_solve: B or X is NULL");
-    check_solve_args(ctx, op, diag, b, tol, maxiter, info);
-    const Operator& A = op->op;
-    REQUIRE(ldb >= A.n, "gsi_op_solve: ldb is smaller than size(A, 1), the rows of B");
-    REQUIRE(ldx >= A.n, "gsi_op_solve: ldx is smaller than size(A, 1), the rows of X");
-    REQUIRE(X != B, "gsi_op_solve: X must not be B");
+    REQUIRE(ldb >= A.n, fn + ": ldb is smaller than size(A, 1), the rows of B");
+    REQUIRE(ldx >= A.n, fn + ": ldx is smaller than size(A, 1), the rows of X");
+    REQUIRE(X != B, fn + ": X must not be B");
     Backend* be = ctx->c.be.get();
     Buf Bd(be, (size_t)A.n * b), Xd(be, (size_t)A.n * b);
     be->upload2d(Bd.p, A.n, B, ldb, A.n, b);
     // (the solution comes back also when the solve broke down: what the columns had reached)
     try {
-      solve_cg_resident(ctx, A, diag, Bd.p, Xd.p, b, tol, maxiter, info, relres, iters);
+      solve_resident(who, ctx, A, diag, pc, Bd.p, Xd.p, b, tol, maxiter, info, ninfo, relres, iters, nullptr);
     } catch (const Error& e) {
       if (e.code == GSI_ERR_NOT_POSDEF) be->download2d(X, ldx, Xd.p, A.n, A.n, b);
       throw;
     }
     be->download2d(X, ldx, Xd.p, A.n, A.n, b);
   });
+}
+// ... and the ones whose B and X are resident
+int solve_mats(const std::string& fn, const char* who, gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc,
+               bool need_pc, const gsi_mat* B, gsi_mat* X, double tol, int64_t maxiter, int64_t* info, int ninfo, double* relres,
+               int64_t* iters) {
+  return guarded([&] {
+    REQUIRE(B && X, fn + ": B or X is NULL");
+    check_solve_args(ctx, op, diag, pc, need_pc, B->cols, tol, maxiter, info, ninfo);
+    check_resident_panels(fn, ctx, op->op, B, X);
+    solve_resident(who, ctx, op->op, diag, pc, B->buf.p, X->buf.p, B->cols, tol, maxiter, info, ninfo, relres, iters, nullptr);
+  });
+}
+}  // namespace
+
+int gsi_op_solve_cg(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_mat* B, gsi_mat* X, double tol,
+                    int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  return solve_mats("gsi_op_solve_cg", "conjugate gradients", ctx, op, diag, nullptr, false, B, X, tol, maxiter, info, INFO_CG,
+                    relres, iters);
+}
+
+int gsi_op_solve(gsi_ctx* ctx, const gsi_op* op, const double* diag, const double* B, int64_t ldb, int64_t b, double* X,
+                 int64_t ldx, double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
+  return solve_staged("gsi_op_solve", "conjugate gradients", ctx, op, diag, nullptr, false, B, ldb, b, X, ldx, tol, maxiter, info,
+                      INFO_CG, relres, iters);
 }
 
 // ---- the low-rank-plus-diagonal preconditioner and the preconditioned solve ----
@@ -1469,72 +1505,17 @@ int gsi_precond_apply(gsi_ctx* ctx, const gsi_precond* pc, const gsi_mat* R, gsi
   });
 }
 
-namespace {
-void solve_pcg_resident(gsi_ctx* ctx, const Operator& A, const double* diag, const LowRankPrecond& pc, const double* Bd,
-                        double* Xd, int64_t b, double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
-  Backend* be = ctx->c.be.get();
-  Buf dd;
-  if (diag) {
-    dd = Buf(be, (size_t)A.n);
-    be->upload2d(dd.p, A.n, diag, A.n, A.n, 1);
-  }
-  const BlockPcgInfo r = block_pcg(A, diag ? dd.p : nullptr, pc, Bd, Xd, b, tol, maxiter, relres, iters);
-  if (info) {
-    info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column; info[4] = r.breakdown_kind;
-    info[5] = r.K;
-  }
-  check_async_errors(ctx->c);
-  if (r.breakdown_column != 0)
-    throw Error(GSI_ERR_NOT_POSDEF, std::string("preconditioned conjugate gradients: ") +
-                                        (r.breakdown_kind == 2 ? "r'z is not positive and finite (the preconditioner is not positive definite)"
-                                                               : "A + diag is not positive definite along the search direction") +
-                                        " of column " + std::to_string(r.breakdown_column));
-}
-void check_pcg_args(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, int64_t b, double tol,
-                    int64_t maxiter, int64_t* info) {
-  if (info) info[4] = info[5] = 0;
-  check_solve_args(ctx, op, diag, b, tol, maxiter, info);
-  REQUIRE(pc, "gsi_op_solve_pcg: pc is NULL");
-  REQUIRE(pc->ctx == ctx, "gsi_op_solve_pcg: pc belongs to another context");
-  block_pcg_check(op->op, pc->pc, b, tol, maxiter);
-}
-}  // namespace
-
 int gsi_op_solve_pcg(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, const gsi_mat* B, gsi_mat* X,
                      double tol, int64_t maxiter, int64_t* info, double* relres, int64_t* iters) {
-  return guarded([&] {
-    REQUIRE(B && X, "gsi_op_solve_pcg: B or X is NULL");
-    check_pcg_args(ctx, op, diag, pc, B->cols, tol, maxiter, info);
-    const Operator& A = op->op;
-    REQUIRE(B->ctx == ctx && X->ctx == ctx, "gsi_op_solve_pcg: B or X belongs to another context");
-    REQUIRE(B->rows == A.n, "gsi_op_solve_pcg: B must have size(A, 1) rows");
-    REQUIRE(X->rows == A.n && X->cols == B->cols, "gsi_op_solve_pcg: X must have the shape of B");
-    REQUIRE(X != B && X->buf.p != B->buf.p, "gsi_op_solve_pcg: X must not be B");
-    solve_pcg_resident(ctx, A, diag, pc->pc, B->buf.p, X->buf.p, B->cols, tol, maxiter, info, relres, iters);
-  });
+  return solve_mats("gsi_op_solve_pcg", "preconditioned conjugate gradients", ctx, op, diag, pc, true, B, X, tol, maxiter, info,
+                    INFO_PCG, relres, iters);
 }
 
 int gsi_op_solve_pcg_host(gsi_ctx* ctx, const gsi_op* op, const double* diag, const gsi_precond* pc, const double* B,
                           int64_t ldb, int64_t b, double* X, int64_t ldx, double tol, int64_t maxiter, int64_t* info,
                           double* relres, int64_t* iters) {
-  return guarded([&] {
-    REQUIRE(B && X, "gsi_op_solve_pcg_host: B or X is NULL");
-    check_pcg_args(ctx, op, diag, pc, b, tol, maxiter, info);
-    const Operator& A = op->op;
-    REQUIRE(ldb >= A.n, "gsi_op_solve_pcg_host: ldb is smaller than size(A, 1), the rows of B");
-    REQUIRE(ldx >= A.n, "gsi_op_solve_pcg_host: ldx is smaller than size(A, 1), the rows of X");
-    REQUIRE(X != B, "gsi_op_solve_pcg_host: X must not be B");
-    Backend* be = ctx->c.be.get();
-    Buf Bd(be, (size_t)A.n * b), Xd(be, (size_t)A.n * b);
-    be->upload2d(Bd.p, A.n, B, ldb, A.n, b);
-    try {                                                       // (as gsi_op_solve: the columns come back after a breakdown too)
-      solve_pcg_resident(ctx, A, diag, pc->pc, Bd.p, Xd.p, b, tol, maxiter, info, relres, iters);
-    } catch (const Error& e) {
-      if (e.code == GSI_ERR_NOT_POSDEF) be->download2d(X, ldx, Xd.p, A.n, A.n, b);
-      throw;
-    }
-    be->download2d(X, ldx, Xd.p, A.n, A.n, b);
-  });
+  return solve_staged("gsi_op_solve_pcg_host", "preconditioned conjugate gradients", ctx, op, diag, pc, true, B, ldb, b, X, ldx,
+                      tol, maxiter, info, INFO_PCG, relres, iters);
 }
 
 // ---- log-determinants by stochastic Lanczos quadrature: the traced solve, the quadrature alone, draws of N(0, P) and
@@ -1547,13 +1528,8 @@ int gsi_op_solve_trace(gsi_ctx* ctx, const gsi_op* op, const double* diag, const
     REQUIRE(B && X, "gsi_op_solve_trace: B or X is NULL");
     const int64_t b = B->cols;
     if (quad_out) for (int64_t j = 0; j < 2 * b; ++j) quad_out[j] = 0.0;
-    if (pc) check_pcg_args(ctx, op, diag, pc, b, tol, maxiter, info);
-    else check_solve_args(ctx, op, diag, b, tol, maxiter, info);
-    const Operator& A = op->op;
-    REQUIRE(B->ctx == ctx && X->ctx == ctx, "gsi_op_solve_trace: B or X belongs to another context");
-    REQUIRE(B->rows == A.n, "gsi_op_solve_trace: B must have size(A, 1) rows");
-    REQUIRE(X->rows == A.n && X->cols == b, "gsi_op_solve_trace: X must have the shape of B");
-    REQUIRE(X != B && X->buf.p != B->buf.p, "gsi_op_solve_trace: X must not be B");
+    check_solve_args(ctx, op, diag, pc, false, b, tol, maxiter, info, INFO_TRACE);
+    check_resident_panels("gsi_op_solve_trace", ctx, op->op, B, X);
     REQUIRE(qmax >= 1, "gsi_op_solve_trace: qmax must be at least 1");
     REQUIRE(qmax <= 4096, "gsi_op_solve_trace: qmax exceeds 4096");
     REQUIRE(nquad >= 0 && nquad <= b, "gsi_op_solve_trace: nquad must lie in 0 .. the columns of B");
@@ -1562,33 +1538,11 @@ int gsi_op_solve_trace(gsi_ctx* ctx, const gsi_op* op, const double* diag, const
     trace.qmax = qmax;
     trace.tr = Buf(be, cgst::trace_doubles(b, qmax));
     std::vector<int64_t> its((size_t)b, 0);
-    Buf dd;
-    if (diag) {
-      dd = Buf(be, (size_t)A.n);
-      be->upload2d(dd.p, A.n, diag, A.n, A.n, 1);
-    }
-    int64_t bcol = 0, bkind = 0;
-    if (pc) {
-      const BlockPcgInfo r = block_pcg(A, diag ? dd.p : nullptr, pc->pc, B->buf.p, X->buf.p, b, tol, maxiter, relres, its.data(),
-                                       &trace);
-      if (info) { info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column;
-                  info[4] = r.breakdown_kind; info[5] = r.K; }
-      bcol = r.breakdown_column; bkind = r.breakdown_kind;
-    } else {
-      const BlockCgInfo r = block_cg(A, diag ? dd.p : nullptr, B->buf.p, X->buf.p, b, tol, maxiter, relres, its.data(), &trace);
-      if (info) { info[0] = r.products; info[1] = r.converged; info[2] = r.path; info[3] = r.breakdown_column;
-                  info[4] = r.breakdown_column ? 1 : 0; }
-      bcol = r.breakdown_column; bkind = 1;
-    }
-    if (info) info[6] = trace.truncated;
-    if (iters) for (int64_t j = 0; j < b; ++j) iters[j] = its[(size_t)j];
-    check_async_errors(ctx->c);
-    if (bcol != 0)
-      throw Error(GSI_ERR_NOT_POSDEF, std::string("traced conjugate gradients: ") +
-                                          (bkind == 2 ? "r'z is not positive and finite (the preconditioner is not positive definite)"
-                                                      : "A + diag is not positive definite along the search direction") +
-                                          " of column " + std::to_string(bcol));
+    int64_t* it = iters ? iters : its.data();                              // (filled before a breakdown is raised)
+    solve_resident("traced conjugate gradients", ctx, op->op, diag, pc, B->buf.p, X->buf.p, b, tol, maxiter, info, INFO_TRACE,
+                   relres, it, &trace);
     if (quad_out) {
+      its.assign(it, it + b);
       double* tr = trace.tr.p;
       for (int64_t j = 0; j < b - nquad; ++j) its[(size_t)j] = 0;          // the data columns: no quadrature, 0
       if (nquad > 0)

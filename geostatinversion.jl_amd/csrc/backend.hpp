@@ -450,7 +450,7 @@ class Backend {
   virtual void diag_mul_add(int64_t n, const double* d, const double* x, double* y) = 0;   // y += d .* x
 
   // ---- IterativeSolvers.lsqr with the scalar recurrences resident in backend memory (lsqr_state.hpp): `work` holds
-  //      lsqr_work_doubles() doubles = [state | partial sums]; pipeline.cpp:lsqr sequences the two operator products
+  //      lsqr_work_doubles() doubles = [state | partial sums]; solvers.cpp:lsqr sequences the two operator products
   //      around these and polls the state every few iterations ----
   virtual size_t lsqr_work_doubles() = 0;
   virtual void lsqr_begin(int64_t n, const double* w, double* work) = 0;                       // |w|^2 of the initial w
@@ -460,9 +460,9 @@ class Backend {
 
   // ---- conjugate gradients on (A + diag(d)) X = B, all b columns together, with the per-column recurrences resident in
   //      backend memory (cg_state.hpp): `work` holds block_cg_work_doubles(b) doubles = [state |
-  //      partial sums]; pipeline.cpp:block_cg sequences the operator product Q = A P around these and polls the state's
+  //      partial sums]; solvers.cpp:block_cg sequences the operator product Q = A P around these and polls the state's
   //      header every few iterations.  Panels n x b, ld n; d (n, may be null) >= 0.
-  //      block_cg_work_doubles: 0 = "not mine" (the default), and pipeline.cpp runs the same recurrences column by column
+  //      block_cg_work_doubles: 0 = "not mine" (the default), and solvers.cpp runs the same recurrences column by column
   //      with op_mul, diag_mul_add, dot, axpy and scal.
   virtual size_t block_cg_work_doubles(int64_t b) { (void)b; return 0; }
   // R and P hold B, X is zero: the columns' norms and the state of a fresh solve
@@ -480,7 +480,7 @@ class Backend {
   // ---- the same solver preconditioned by P = Z Z' + diag(d + shift): P^-1 = diag(e) - W W' with
   //      e (n) and W (n x K, ld n) in backend memory.  `work` holds block_pcg_work_doubles(b) doubles = [state | three sets
   //      of partial sums]; S (K x b, ld K) and Y (n x b, ld n) are the caller's.  0 = "not mine" (the default):
-  //      pipeline.cpp runs block_pcg_host.hpp.
+  //      solvers.cpp runs the preconditioned form of block_cg_host.hpp.
   virtual size_t block_pcg_work_doubles(int64_t b) { (void)b; return 0; }
   // R holds B, X is zero: P <- z0 = P^-1 B, the columns' b'b and b'z0, the state of a fresh solve
   virtual void block_pcg_begin(int64_t n, int64_t b, int64_t K, const double* B, const double* e, const double* W, double* S,
@@ -536,7 +536,7 @@ class Backend {
     double pc_ell = 1.0, pc_sigma2 = 1.0, pc_nugget = 0.0;
   };
   // `work` holds pchol_work_doubles doubles and starts with the state block (pchol::state_doubles(K)); d: n doubles;
-  // L: n x >= K, ld ldl, its first K columns cleared by the caller.  0 = "not mine" (the default): pipeline.cpp runs
+  // L: n x >= K, ld ldl, its first K columns cleared by the caller.  0 = "not mine" (the default): solvers.cpp runs
   // pivoted_chol_host.hpp.
   virtual size_t pchol_work_doubles(const PcholSource& a, int64_t n, int64_t K) { (void)a; (void)n; (void)K; return 0; }
   // d <- diag(A), the state of a fresh factorization, the first decision

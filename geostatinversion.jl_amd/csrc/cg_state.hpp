@@ -1,7 +1,7 @@
 // cg_state.hpp -- the scalar side of the multi-column conjugate-gradient solver: plain CG per
 // column on (A + diag(d)) X = B with x0 = 0, the b columns advanced together and sharing only the operator product
 // Q = A P.  The recurrences are written ONCE here and run by the device kernels (block_cg.hip, one thread per column) and
-// by the host-driven path of pipeline.cpp:block_cg (the CPU reference library, GSI_CG_COMPOSED=1), as lsqr_state.hpp
+// by the host-driven path of solvers.cpp:block_cg (the CPU reference library, GSI_CG_COMPOSED=1), as lsqr_state.hpp
 // does for LSQR: the state block lives in backend memory, an iteration needs no scalar on the host, and the host only
 // polls the header every few iterations.
 //

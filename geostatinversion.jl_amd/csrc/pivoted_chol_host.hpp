@@ -1,8 +1,8 @@
 // pivoted_chol_host.hpp -- the host-driven ("composed") form of the diagonal-pivoted Cholesky factorization: pchol_state.hpp's
-// rules around an update loop in the contract's order, every column fetched by the caller (pipeline.cpp: the operator
+// rules around an update loop in the contract's order, every column fetched by the caller (solvers.cpp: the operator
 // product with a unit vector).  What the CPU reference library runs, the in-process A/B leg of the device kernels
 // (GSI_PCHOL_COMPOSED=1) and their first reference.  Plain host code with no backend in it, so that
-// tests/pivchol_host_check.cpp can run it under the sanitizers.  Included by pipeline.cpp only.
+// tests/pivchol_host_check.cpp can run it under the sanitizers.  Included by solvers.cpp only.
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -1,5 +1,5 @@
 // slq_state.hpp -- the Gauss quadrature of stochastic Lanczos quadrature, written ONCE and run by
-// the device kernel (block_slq.hip, one thread per column) and by the host path of pipeline.cpp, as cg_state.hpp and
+// the device kernel (block_slq.hip, one thread per column) and by the host path of solvers.cpp, as cg_state.hpp and
 // lsqr_state.hpp do for their recurrences.
 //
 // The coefficients alpha_k, beta_k of m steps of (preconditioned) CG started from z are the Lanczos tridiagonal T (m x m) of

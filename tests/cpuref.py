@@ -1,5 +1,5 @@
 """Test helper: load the CPU reference build of the SAME C ABI (oracle/_build/libgsi_cpuref.so =
-pipeline.cpp + pcga.cpp + api.cpp + the C restatement) so the host-side logic can run without a GPU.
+pipeline.cpp + solvers.cpp + pcga.cpp + api.cpp + the C restatement) so the host-side logic can run without a GPU.
 Only tests use this; the product loader never opens it."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """`gsi_op_solve_trace` / `gsi_slq_quadrature` / `gsi_precond_sample` / `gsi_precond_logdet` / `logdet` / `log_likelihood` on
-the CPU reference library: the traced form of pipeline.cpp's host drivers (csrc/block_cg_host.hpp, csrc/block_pcg_host.hpp;
+the CPU reference library: the traced form of solvers.cpp's host driver (csrc/block_cg_host.hpp;
 path 3, "composed") and csrc/slq_state.hpp's quadrature run on the host, against numpy.  Cases and checks:
 tests/logdet_cases.py.  tests/test_op_logdet_gpu.py runs the same checks on csrc/block_slq.hip.
 OP_LOGDET_ERRORS=<path>: the largest ratios seen, as profiles/op_logdet_errors.json."""

@@ -1,6 +1,6 @@
 """`gsi_precond_lowrank_create` / `gsi_op_solve_pcg` / `lowrank_preconditioner` / `solve(..., precond=)` on the CPU
-reference library: the host driver of pipeline.cpp with cg_state.hpp's preconditioned recurrences composed from the
-backend's primitives (csrc/block_pcg_host.hpp; path 3, "composed"), against numpy.  Cases and checks: tests/pcg_cases.py on
+reference library: the host driver of solvers.cpp with cg_state.hpp's preconditioned recurrences composed from the
+backend's primitives (csrc/block_cg_host.hpp; path 3, "composed"), against numpy.  Cases and checks: tests/pcg_cases.py on
 top of tests/solve_cases.py.  tests/test_op_pcg_gpu.py runs the same checks on csrc/block_pcg.hip.
 OP_PRECOND_ERRORS=<path>: the largest ratios seen, as profiles/op_precond_errors.json."""
 import json

@@ -1,4 +1,4 @@
-"""`gsi_op_solve_cg` / `Operator.solve` / `kriging_weights` on the CPU reference library: the host driver of pipeline.cpp
+"""`gsi_op_solve_cg` / `Operator.solve` / `kriging_weights` on the CPU reference library: the host driver of solvers.cpp
 with cg_state.hpp's recurrences composed from the backend's BLAS-1 primitives (path 3, "composed"), against numpy.  Cases,
 bars and checks: tests/solve_cases.py.  tests/test_op_solve_gpu.py runs the same checks on the fused device kernels."""
 import numpy as np
