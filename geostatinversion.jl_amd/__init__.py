@@ -25,7 +25,7 @@ from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, 
 from . import kriging as Kriging
 from .kriging import (solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy, lowrank_preconditioner,
                       Preconditioner, logdet, log_likelihood, solve_trace, estimate_field, linear_inversion,
-                      condition_on_linear_data)
+                      condition_on_linear_data, posterior_variance_exact, mat_rowdot_acc)
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
                    posterior_realizations, LinearDataOperator, linear_data_operator)
 
@@ -39,4 +39,5 @@ __all__ = [
     "Kriging", "solve", "kriging_weights", "krige_to_grid", "condition_fields", "mat_axpy",
     "lowrank_preconditioner", "Preconditioner", "logdet", "log_likelihood", "solve_trace", "pivoted_cholesky", "principal_factor", "getxis_pivchol",
     "LinearDataOperator", "linear_data_operator", "estimate_field", "linear_inversion", "condition_on_linear_data",
+    "posterior_variance_exact", "mat_rowdot_acc",
 ]

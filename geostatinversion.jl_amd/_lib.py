@@ -146,6 +146,8 @@ SIGNATURES = {
     "gsi_basis_quadform": (C.c_int, [c_vp, c_vp, c_dp, c_i64, c_i64, C.c_int, c_dp, c_dp, c_dp, c_dp, C.POINTER(c_i64)]),
     "gsi_pcgamat_posterior": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_dp, C.POINTER(c_i64)]),
     "gsi_pcga_posterior_variance": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp, c_dp, C.POINTER(c_i64)]),
+    "gsi_op_posterior_variance": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, C.POINTER(c_i64)]),
+    "gsi_mat_rowdot_acc": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "gsi_ctx_profile": (C.c_int, [c_vp, C.c_int]),
     "gsi_ctx_phase_reset": (C.c_int, [c_vp]),
     "gsi_ctx_phase_times": (C.c_int, [c_vp, c_dp, C.POINTER(c_i64)]),

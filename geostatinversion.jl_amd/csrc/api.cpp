@@ -1959,6 +1959,57 @@ int gsi_pcga_posterior_variance(gsi_ctx* ctx, const gsi_basis* basis, const gsi_
   });
 }
 
+// ---- the exact posterior variance of linear inversion and kriging ----------------
+int gsi_mat_rowdot_acc(gsi_ctx* ctx, const gsi_mat* A, const gsi_mat* B, gsi_mat* acc) {
+  return guarded([&] {
+    REQUIRE(ctx && A && B && acc, "gsi_mat_rowdot_acc: NULL argument");
+    REQUIRE(A->ctx == ctx && B->ctx == ctx && acc->ctx == ctx, "gsi_mat_rowdot_acc: A, B or acc belongs to another context");
+    if (B->rows != A->rows || B->cols != A->cols)
+      throw Error(GSI_ERR_ARG, "gsi_mat_rowdot_acc: B is " + std::to_string(B->rows) + " x " + std::to_string(B->cols) +
+                                   ", A is " + std::to_string(A->rows) + " x " + std::to_string(A->cols) +
+                                   ": the panels must have the same shape");
+    if (acc->rows != A->rows || acc->cols != 1)
+      throw Error(GSI_ERR_ARG, "gsi_mat_rowdot_acc: acc is " + std::to_string(acc->rows) + " x " + std::to_string(acc->cols) +
+                                   ", not rows of A x 1 = " + std::to_string(A->rows) + " x 1");
+    REQUIRE(acc != A && acc != B && acc->buf.p != A->buf.p && acc->buf.p != B->buf.p, "gsi_mat_rowdot_acc: acc must not be A or B");
+    rowdot_acc(ctx->c, A->rows, A->cols, A->buf.p, A->rows, B->buf.p, B->rows, acc->buf.p);
+    check_async_errors(ctx->c);
+  });
+}
+
+int gsi_op_posterior_variance(gsi_ctx* ctx, const gsi_op* op, const double* diag, const double* X, int64_t ldx, int64_t p,
+                              int64_t batch, double* var_out, int64_t* info_out) {
+  PostxInfo info;
+  if (info_out) for (int i = 0; i < 8; ++i) info_out[i] = 0;
+  const int st = guarded([&] {
+    REQUIRE(ctx && op && var_out, "gsi_op_posterior_variance: ctx, op or var_out is NULL");
+    const Operator& A = op->op;
+    REQUIRE(A.ctx == &ctx->c, "gsi_op_posterior_variance: op belongs to another context");
+    REQUIRE(A.kind == OP_FWD_COV || A.kind == OP_FFT_COV_AT,
+            "gsi_op_posterior_variance: op must be an operator H C H' of gsi_op_fwd_cov or W C W' of gsi_op_fft_at");
+    REQUIRE(!ctx->c.comm, "gsi_op_posterior_variance: one GPU only -- ctx has a communicator");
+    if (A.n > 32768)
+      throw Error(GSI_ERR_ARG, "gsi_op_posterior_variance: op has nobs = " + std::to_string(A.n) +
+                                   " rows, beyond the 32768 the Cholesky factorization takes");
+    REQUIRE(p >= 0, "gsi_op_posterior_variance: p must be >= 0");
+    REQUIRE(p == 0 || X != nullptr, "gsi_op_posterior_variance: X is NULL with p > 0");
+    const int64_t n = A.fft_N[0] * A.fft_N[1] * A.fft_N[2];
+    if (ldx < n)
+      throw Error(GSI_ERR_ARG, "gsi_op_posterior_variance: ldx = " + std::to_string(ldx) + " is smaller than n_grid = " +
+                                   std::to_string(n) + ", the rows of X");
+    REQUIRE(batch >= 0, "gsi_op_posterior_variance: batch must be >= 0 (0: the operator's own rule)");
+    if (diag)
+      for (int64_t j = 0; j < A.n; ++j) REQUIRE(std::isfinite(diag[j]), "gsi_op_posterior_variance: diag holds a non-finite value");
+    posterior_variance_exact(A, diag, X, ldx, p, batch, var_out, info);
+    check_async_errors(ctx->c);
+  });
+  if (info_out) {
+    const int64_t v[6] = {info.column, info.path, info.batches, info.width, info.adjoint_columns, info.trapezoid_bytes};
+    for (int i = 0; i < 6; ++i) info_out[i] = v[i];
+  }
+  return st;
+}
+
 // ---- measurement ---------------------------------------------------------------------
 int gsi_ctx_profile(gsi_ctx* ctx, int enable) {
   return guarded([&] {

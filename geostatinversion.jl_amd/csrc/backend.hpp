@@ -604,6 +604,34 @@ class Backend {
     return 0;
   }
 
+  // ---- the exact posterior variance of linear inversion and kriging ----
+  // The row pass: acc[i] += sum over c < b of A[i, c] B[i, c] for column-major n x b panels (ld lda, ldb), every product
+  // rounded on its own and added to the row's sum, which starts from acc[i], in ascending c.  B == A: the sum of squares.
+  // 1, or 0: "not mine", nothing ran, and the caller runs posterior_exact_host.hpp on downloaded panels.
+  virtual int rowdot_acc(int64_t n, int64_t b, const double* A, int64_t lda, const double* B, int64_t ldb, double* acc) {
+    (void)n; (void)b; (void)A; (void)lda; (void)B; (void)ldb; (void)acc;
+    return 0;
+  }
+  // E (nobs x b, ld) <- zeros with a one at (c0 + c, c).  1, or 0: "not mine".
+  virtual int unit_panel(double* E, int64_t ld, int64_t nobs, int64_t b, int64_t c0) {
+    (void)E; (void)ld; (void)nobs; (void)b; (void)c0;
+    return 0;
+  }
+  // The assembly of the (2 nobs + p) x nobs trapezoid T (ld) whose top block holds H C H': diag (nobs values, or null) is
+  // added to the diagonal, rows [nobs, nobs + p) <- Phi' (Phi: nobs x p, ld ldphi), rows [nobs + p, 2 nobs + p) <- I.
+  // 1, or 0: "not mine".
+  virtual int trapezoid_rows(double* T, int64_t ld, int64_t nobs, int64_t p, const double* diag, const double* Phi,
+                             int64_t ldphi) {
+    (void)T; (void)ld; (void)nobs; (void)p; (void)diag; (void)Phi; (void)ldphi;
+    return 0;
+  }
+  // After chol_lower: Wd (nobs x p, ld nobs) <- the transpose of rows [nobs, nobs + p) of T, W_d = L^-1 Phi.
+  // 1, or 0: "not mine".
+  virtual int carried_rows(const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd) {
+    (void)T; (void)ld; (void)nobs; (void)p; (void)Wd;
+    return 0;
+  }
+
   // error flags raised asynchronously by kernels (zero pivot, non-posdef); checked and
   // cleared by the pipeline at the end of each entry point. Returns GSI_* code or 0.
   virtual int take_error(std::string* msg) = 0;

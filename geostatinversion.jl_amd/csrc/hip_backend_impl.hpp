@@ -286,6 +286,11 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   int basis_quadform(const void* Z, int zbits, int64_t n, int64_t ldz, int64_t K, const double* W, int64_t ldw, int64_t ncols,
                      bool upper, const double* u, double* a, double* q, double* t) override;
   int scale_rows(int64_t m, int64_t c, const double* d, const double* src, int64_t lds, double* dst, int64_t ldd) override;
+  int rowdot_acc(int64_t n, int64_t b, const double* A, int64_t lda, const double* B, int64_t ldb, double* acc) override;
+  int unit_panel(double* E, int64_t ld, int64_t nobs, int64_t b, int64_t c0) override;
+  int trapezoid_rows(double* T, int64_t ld, int64_t nobs, int64_t p, const double* diag, const double* Phi,
+                     int64_t ldphi) override;
+  int carried_rows(const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd) override;
 
  private:
   // ---- hip_backend.hip ----

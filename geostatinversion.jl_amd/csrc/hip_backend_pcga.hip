@@ -286,4 +286,38 @@ int HipBackend::scale_rows(int64_t m, int64_t c, const double* d, const double* 
   return 1;
 }
 
+// The row pass and the trapezoid's carried rows of the exact posterior variance (posterior_exact.hip).
+int HipBackend::rowdot_acc(int64_t n, int64_t b, const double* A, int64_t lda, const double* B, int64_t ldb, double* acc) {
+  bind();
+  if (n < 1 || b < 1 || lda < n || ldb < n || A == nullptr || B == nullptr || acc == nullptr)
+    throw Error(GSI_ERR_ARG, "rowdot_acc: need n, b >= 1, lda, ldb >= n and no NULL operand");
+  hipk::px_rowdot_acc(st_, n, b, A, lda, B, ldb, acc);
+  check_launch("rowdot_acc");
+  return 1;
+}
+int HipBackend::unit_panel(double* E, int64_t ld, int64_t nobs, int64_t b, int64_t c0) {
+  bind();
+  if (nobs < 1 || b < 1 || ld < nobs || c0 < 0) throw Error(GSI_ERR_ARG, "unit_panel: need nobs, b >= 1, ld >= nobs, c0 >= 0");
+  hipk::px_unit_panel(st_, E, ld, nobs, b, c0);
+  check_launch("unit_panel");
+  return 1;
+}
+int HipBackend::trapezoid_rows(double* T, int64_t ld, int64_t nobs, int64_t p, const double* diag, const double* Phi,
+                               int64_t ldphi) {
+  bind();
+  if (nobs < 1 || p < 0 || ld < 2 * nobs + p || (p > 0 && (Phi == nullptr || ldphi < nobs)))
+    throw Error(GSI_ERR_ARG, "trapezoid_rows: need nobs >= 1, p >= 0, ld >= 2 nobs + p, Phi (ld >= nobs) when p > 0");
+  hipk::px_trapezoid_rows(st_, T, ld, nobs, p, diag, Phi, ldphi);
+  check_launch("trapezoid_rows");
+  return 1;
+}
+int HipBackend::carried_rows(const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd) {
+  bind();
+  if (nobs < 1 || p < 0 || ld < 2 * nobs + p || (p > 0 && Wd == nullptr))
+    throw Error(GSI_ERR_ARG, "carried_rows: need nobs >= 1, p >= 0, ld >= 2 nobs + p, Wd when p > 0");
+  hipk::px_carried_rows(st_, T, ld, nobs, p, Wd);
+  check_launch("carried_rows");
+  return 1;
+}
+
 }  // namespace gsi

@@ -430,4 +430,13 @@ void pv_quadform(hipStream_t st, const void* Z, int zbits, int64_t n, int64_t ld
 void pv_scale_rows(hipStream_t st, int64_t m, int64_t c, const double* d, const double* src, int64_t lds, double* dst,
                    int64_t ldd);
 
+// ---- posterior_exact.hip: the exact posterior variance of linear inversion and kriging ----
+// acc[i] += sum_c A[i, c] B[i, c] over column-major n x b panels, products rounded one by one and added in ascending c;
+// A == B with lda == ldb takes the instantiation that loads each entry once
+void px_rowdot_acc(hipStream_t st, int64_t n, int64_t b, const double* A, int64_t lda, const double* B, int64_t ldb, double* acc);
+void px_unit_panel(hipStream_t st, double* E, int64_t ld, int64_t nobs, int64_t b, int64_t c0);
+void px_trapezoid_rows(hipStream_t st, double* T, int64_t ld, int64_t nobs, int64_t p, const double* diag, const double* Phi,
+                       int64_t ldphi);
+void px_carried_rows(hipStream_t st, const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd);
+
 }}  // namespace gsi::hipk

@@ -4,6 +4,7 @@
 #include "pcga.hpp"
 #include "saddle_host.hpp"
 #include "posterior_host.hpp"
+#include "posterior_exact_host.hpp"
 #include "fwd_adjoint_host.hpp"
 #include <algorithm>
 #include <cmath>
@@ -531,6 +532,157 @@ void fwd_adjoint(Context& c, const FwdModel& F, const double* V, int64_t ldv, in
   fwd_adjoint_host::apply(F.aplan, Vh.data(), F.nobs, b, Gh.data(), F.n);
   be->upload2d(G, ldg, Gh.data(), F.n, F.n, b);
   F.adj_host_products += 1;
+}
+
+// ---- the exact posterior variance of linear inversion and kriging -------------------------------
+int64_t rowdot_acc(Context& c, int64_t n, int64_t b, const double* A, int64_t lda, const double* B, int64_t ldb, double* acc,
+                   bool force_host) {
+  Backend* be = c.be.get();
+  if (n < 1 || b < 1) return PATH_BACKEND;
+  if (!force_host && !env_forces_host("GSI_POSTX_HOST") && be->rowdot_acc(n, b, A, lda, B, ldb, acc) != 0) return PATH_BACKEND;
+  const bool same = (A == B && lda == ldb);
+  std::vector<double> Ah((size_t)n * (size_t)b), Bh(same ? (size_t)0 : (size_t)n * (size_t)b), ah((size_t)n);
+  be->download2d(Ah.data(), n, A, lda, n, b);
+  if (!same) be->download2d(Bh.data(), n, B, ldb, n, b);
+  be->download2d(ah.data(), n, acc, n, n, 1);
+  postx_host::rowdot_acc(n, b, Ah.data(), n, same ? Ah.data() : Bh.data(), n, ah.data());
+  be->upload2d(acc, n, ah.data(), n, n, 1);
+  return PATH_HOST;
+}
+
+void posterior_variance_exact(const Operator& A, const double* diag, const double* X, int64_t ldx, int64_t p, int64_t batch,
+                              double* var, PostxInfo& info) {
+  Context& c = *A.ctx;
+  Backend* be = c.be.get();
+  const int64_t nobs = A.n, n = A.fft_N[0] * A.fft_N[1] * A.fft_N[2], ld = 2 * nobs + p;
+  info = PostxInfo();
+  info.trapezoid_bytes = (int64_t)sizeof(double) * ld * nobs;
+  const int64_t bw = std::max<int64_t>(1, std::min(batch > 0 ? batch : op_cov_batch(A, nobs), nobs));
+  info.width = bw;
+  bool host = env_forces_host("GSI_POSTX_HOST");
+
+  // V (nobs x b, ld ldv) -> Hh (n x b) = C H' V through G (n x b): the model's adjoint or the interpolation's spread, then
+  // the grid product; profiled as the operator's own products are (gemm_t, gemm_n)
+  auto prior_adjoint = [&](const double* V, int64_t ldv, int64_t b, double* G, double* Hh) {
+    {
+      ScopedPhase ph(be, PH_GEMM_T);
+      if (A.kind == OP_FWD_COV) fwd_adjoint(c, *A.fwd, V, ldv, b, G, n);
+      else be->points_at_spread(A.at, G, n, b, V, ldv);
+    }
+    ScopedPhase ph(be, PH_GEMM_N);
+    be->fftcov_apply(A.plan, b, G, n, Hh, n);
+  };
+
+  Buf T(be, (size_t)ld * (size_t)nobs);
+  {                                                    // the top block: columns [c0, c0 + b) of H C H' from unit columns
+    Buf E(be, (size_t)nobs * (size_t)bw);
+    std::vector<double> Eh;
+    for (int64_t c0 = 0; c0 < nobs; c0 += bw) {
+      const int64_t b = std::min(bw, nobs - c0);
+      if (!host && be->unit_panel(E.p, nobs, nobs, b, c0) == 0) host = true;
+      if (host) {
+        Eh.resize((size_t)nobs * (size_t)b);
+        postx_host::unit_panel(Eh.data(), nobs, nobs, b, c0);
+        be->upload2d(E.p, nobs, Eh.data(), nobs, nobs, b);
+      }
+      op_mul(A, E.p, nobs, b, T.p + (size_t)c0 * (size_t)ld, ld);
+    }
+  }
+  Buf Phi(be, (size_t)nobs * (size_t)std::max<int64_t>(p, 1)), dd;
+  if (p > 0) {                                         // Phi = H X
+    Buf Xd(be, (size_t)n * (size_t)p);
+    be->upload2d(Xd.p, n, X, ldx, n, p);
+    if (A.kind == OP_FWD_COV) fwd_apply_dev(c, *A.fwd, Xd.p, n, p, Phi.p, nobs);
+    else be->points_at_gather(A.at, Phi.p, nobs, p, Xd.p, n);
+  }
+  if (diag) {
+    dd = Buf(be, (size_t)nobs);
+    be->upload2d(dd.p, nobs, diag, nobs, nobs, 1);
+  }
+
+  // [M; Phi'; I] <- [L; W_d'; L^-T] by one factorization of the trapezoid
+  int64_t col = -1;
+  bool assembled = false;
+  if (!host) {
+    if (be->trapezoid_rows(T.p, ld, nobs, p, dd.p, Phi.p, nobs) == 0) host = true;
+    else assembled = true;
+  }
+  if (!host) {
+    ScopedPhase ph(be, PH_LU);
+    col = be->chol_lower(T.p, ld, nobs, ld);
+  }
+  if (col == -1) {                                     // the same on the downloaded trapezoid (saddle_host.hpp)
+    host = true;
+    std::vector<double> Th((size_t)ld * (size_t)nobs);
+    be->download2d(Th.data(), ld, T.p, ld, ld, nobs);
+    if (!assembled) {
+      std::vector<double> Ph((size_t)nobs * (size_t)std::max<int64_t>(p, 1));
+      if (p > 0) be->download2d(Ph.data(), nobs, Phi.p, nobs, nobs, p);
+      postx_host::assemble(Th.data(), ld, nobs, p, diag, Ph.data(), nobs);
+    }
+    col = saddle_host::chol_lower(Th.data(), ld, nobs, ld);
+    if (col == 0) be->upload2d(T.p, ld, Th.data(), ld, ld, nobs);
+  }
+  info.path = host ? PATH_HOST : PATH_BACKEND;
+  if (col > 0) {
+    info.column = col;
+    throw Error(GSI_ERR_NOT_POSDEF, "PosDefException: H C H' + D is not positive definite; Cholesky failed at " + std::to_string(col));
+  }
+  const double* Linvt = T.p + nobs + p;                // L^-T, nobs x nobs upper triangular, ld
+
+  // the p x p algebra: S = W_d'W_d = Ls Ls' on the host, V = L^-T W_d by the contraction
+  std::vector<double> Ls((size_t)std::max<int64_t>(p * p, 1));
+  Buf V;
+  if (p > 0) {
+    Buf Wd(be, (size_t)nobs * (size_t)p), S(be, (size_t)p * (size_t)p);
+    if (host || be->carried_rows(T.p, ld, nobs, p, Wd.p) == 0) {
+      host = true;
+      std::vector<double> rows((size_t)p * (size_t)nobs), Wh((size_t)nobs * (size_t)p);
+      be->download2d(rows.data(), p, T.p + nobs, ld, p, nobs);
+      postx_host::carried_rows(rows.data(), p, nobs, p, Wh.data());
+      be->upload2d(Wd.p, nobs, Wh.data(), nobs, nobs, p);
+    }
+    {
+      ScopedPhase ph(be, PH_SMALL_GEMM);
+      be->gemm_tn(p, p, nobs, 1.0, Wd.p, nobs, Wd.p, nobs, 0.0, S.p, p);
+    }
+    be->download2d(Ls.data(), p, S.p, p, p, p);
+    const int64_t scol = postx_host::chol_small(Ls.data(), p);
+    if (scol != 0)
+      throw Error(GSI_ERR_SINGULAR, "SingularException: the drift columns H X are linearly dependent (X' H' (H C H' + D)^-1 H X is "
+                                    "singular at column " + std::to_string(scol) + ")");
+    V = Buf(be, (size_t)nobs * (size_t)p);
+    ScopedPhase ph(be, PH_SMALL_GEMM);
+    be->gemm_nn(nobs, p, nobs, 1.0, Linvt, ld, Wd.p, nobs, 0.0, V.p, nobs);
+  }
+
+  // the n-sized work: T_J = C H' (L^-T)[:, J] batch by batch and its running row sums of squares; U = C H' V
+  Buf G(be, (size_t)n * (size_t)bw), Hh(be, (size_t)n * (size_t)bw), acc(be, (size_t)n);
+  be->fill_zero(acc.p, (size_t)n);
+  for (int64_t c0 = 0; c0 < nobs; c0 += bw) {
+    const int64_t b = std::min(bw, nobs - c0);
+    prior_adjoint(Linvt + (size_t)c0 * (size_t)ld, ld, b, G.p, Hh.p);
+    ScopedPhase ph(be, PH_OTHER);
+    if (rowdot_acc(c, n, b, Hh.p, n, Hh.p, n, acc.p, host) == PATH_HOST) host = true;     // a pass the backend declined
+    info.batches += 1;
+  }
+  std::vector<double> Uh((size_t)n * (size_t)std::max<int64_t>(p, 1));
+  for (int64_t c0 = 0; c0 < p; c0 += bw) {
+    const int64_t b = std::min(bw, p - c0);
+    prior_adjoint(V.p + (size_t)c0 * (size_t)nobs, nobs, b, G.p, Hh.p);
+    be->download2d(Uh.data() + (size_t)c0 * (size_t)n, n, Hh.p, n, n, b);
+  }
+  info.adjoint_columns = nobs + p;
+  info.path = host ? PATH_HOST : PATH_BACKEND;         // the host path if any of the backend's steps was declined
+  // C_00 = (C e_0)_0: constant over the cells for every FFT grid operator, whatever its convention
+  double c00 = 1.0;
+  be->fill_zero(G.p, (size_t)n);
+  be->upload2d(G.p, n, &c00, 1, 1, 1);
+  be->fftcov_apply(A.plan, 1, G.p, n, Hh.p, n);
+  be->download2d(&c00, 1, Hh.p, n, 1, 1);
+  std::vector<double> ah((size_t)n);
+  be->download2d(ah.data(), n, acc.p, n, n, 1);
+  postx_host::finish(n, p, c00, ah.data(), Uh.data(), n, X, ldx, Ls.data(), var);
 }
 
 }  // namespace gsi

@@ -62,6 +62,27 @@ void posterior_factor(const PcgaLowRank& A, double* W, double* u, double* gamma,
 void posterior_variance(Context& c, BasisRef Z, const PcgaLowRank& A, const double* X, const double* prior, double* var,
                         PathInfo& info);
 
+// ---- the exact posterior variance of linear inversion and kriging (GSI_POSTX_HOST) ----
+// What gsi_op_posterior_variance reports in info_out[0 .. 5].
+struct PostxInfo {
+  int64_t column = 0;            // 0, or the 1-based column at which H C H' + D stopped being positive definite
+  int64_t path = 0;              // PATH_BACKEND / PATH_HOST
+  int64_t batches = 0;           // batches of columns of L^-T that went through the prior adjoint and the row pass
+  int64_t width = 0;             // columns per batch
+  int64_t adjoint_columns = 0;   // columns sent through V -> C H' V in total (nobs + p)
+  int64_t trapezoid_bytes = 0;   // (2 nobs + p) nobs doubles
+};
+// acc (n, backend memory) += the row sums of A .* B for n x b panels in backend memory (Backend::rowdot_acc); when the
+// backend declines, or GSI_POSTX_HOST=1, or force_host: download, posterior_exact_host.hpp, upload.  Returns the path.
+int64_t rowdot_acc(Context& c, int64_t n, int64_t b, const double* A, int64_t lda, const double* B, int64_t ldb, double* acc,
+                   bool force_host = false);
+// var (n_grid, host) = diag(C - C H'(H C H' + D)^-1 H C) + the drift term, for A = H C H' an OP_FWD_COV or OP_FFT_COV_AT
+// operator: diag (host, nobs values, or null), X (host, n_grid x p, ld ldx; null with p = 0), batch columns per batch (0:
+// op_cov_batch).  The arguments are validated by the caller.  Throws GSI_ERR_NOT_POSDEF (info.column) or GSI_ERR_SINGULAR
+// (H X rank deficient) with info filled.
+void posterior_variance_exact(const Operator& A, const double* diag, const double* X, int64_t ldx, int64_t p, int64_t batch,
+                              double* var, PostxInfo& info);
+
 // A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
 // vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
 // double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.

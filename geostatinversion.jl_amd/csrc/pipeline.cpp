@@ -159,6 +159,13 @@ static void fwd_cov_mul(const Operator& A, const double* X, int64_t ldx, int64_t
   }
 }
 
+int64_t op_cov_batch(const Operator& A, int64_t l) {
+  const int64_t n = A.fft_N[0] * A.fft_N[1] * A.fft_N[2];
+  if (A.kind == OP_FFT_COV_AT) return fft_at_batch(n, l);
+  if (A.kind == OP_FWD_COV) return fwd_cov_batch(n, l);
+  throw Error(GSI_ERR_INTERNAL, "op_cov_batch: the operator keeps no grid panels");
+}
+
 void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Yloc, int64_t ldy) {
   Context& c = *A.ctx;
   Backend* be = c.be.get();

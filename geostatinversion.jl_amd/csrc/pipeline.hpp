@@ -109,6 +109,9 @@ void default_shard(int64_t m, int nranks, int rank, int64_t* row0, int64_t* mloc
 
 // Y_loc (mloc x l, ld ldy) = rows [row0,row0+mloc) of A * X, X replicated n x l (ld ldx)
 void op_mul(const Operator& A, const double* X, int64_t ldx, int64_t l, double* Yloc, int64_t ldy);
+// OP_FFT_COV_AT / OP_FWD_COV: the columns per batch op_mul would take for l columns -- even, both n_grid x lb panels within
+// 2 GiB, GSI_FFT_AT_BATCH / GSI_FWD_COV_BATCH (read at every call) overriding it
+int64_t op_cov_batch(const Operator& A, int64_t l);
 // Z (n x l, ld ldz, replicated) = A' * X where Xloc (mloc x l, ld ldx) are this rank's rows of X
 void op_mul_t(const Operator& A, const double* Xloc, int64_t ldx, int64_t l, double* Z, int64_t ldz);
 // Y (m x l, ld m, replicated) <- all ranks' row shards

@@ -216,6 +216,14 @@ def mat_axpy(alpha, X, Y):
     return Y
 
 
+def mat_rowdot_acc(A, B, acc):
+    """`acc[i] += sum_c A[i, c] B[i, c]` for two `DeviceMatrix` of one shape and `acc` of rows x 1 (`gsi_mat_rowdot_acc`);
+    returns acc.  Every product is rounded on its own and added in ascending c, so the result is a pure function of the
+    operands' bits; `B is A` sums the squares and reads each entry once."""
+    L.check(acc.ctx.lib.gsi_mat_rowdot_acc(acc.ctx.h, A.h, B.h, acc.h), acc.ctx.lib)
+    return acc
+
+
 def kriging_weights(op, y, noise=None, drift=None, **cg):
     """The weights of (universal) kriging: with M = A + diag(noise) and the drift matrix G (m x p, e.g. [1, x, y]),
     `xi, beta` such that  M xi + G beta = y,  G' xi = 0  -- from ONE solve of the 1 + p columns [y, G]:
@@ -420,7 +428,129 @@ def estimate_field(op, xi, beta=None, drift_grid=None):
     return out[:, 0].copy() if xv.ndim == 1 else out
 
 
-def linear_inversion(grid_op, model, y, noise, drift_grid=None, precond=None, return_info=False, **cg):
+def _prior_adjoint_any(op, V):
+    """C H' V for a `LinearDataOperator` (H the model's matrix) or an `FFTOperatorAt` (H the interpolation W) and a
+    DeviceMatrix V (nobs x b): a new DeviceMatrix (n_grid x b)."""
+    if hasattr(op, "model"):
+        return _prior_adjoint(op, V)
+    G = FFTRF.spread(op.ctx, op._P, V, op.Ns, box=op._B)
+    try:
+        return _grid_product(op, G)
+    finally:
+        G.close()
+
+
+def _posterior_finish(c00, acc, U, X, S):
+    """v_i = C_00 - acc_i + |Ls^-1 (x_i - u_i)|^2 with S = Ls Ls' (p x p); p = 0: the first two terms."""
+    v = c00 - acc
+    if X.shape[1]:
+        z = np.linalg.solve(np.linalg.cholesky(0.5 * (S + S.T)), (X - U).T)
+        v = v + np.sum(z * z, axis=0)
+    return v
+
+
+POSTX_INFO = ("column", "path", "batches", "batch", "adjoint_columns", "trapezoid_bytes")
+
+
+def posterior_variance_exact(op, noise=None, drift_grid=None, *, method="cholesky", batch=None, precond=None, return_info=False,
+                             **cg):
+    """The exact posterior (estimation) variance of every grid cell for the data y = H s + v of `op` = H C H', a
+    `LinearDataOperator` (`linear_data_operator`) or an `FFTOperatorAt` (H = the interpolation W): with M = H C H' +
+    diag(noise), the prior s ~ N(X beta, C), beta unknown, X = `drift_grid` (n_grid x p; None: no drift) and g_i the rows of
+    C H',
+        v_i = C_ii - g_i' M^-1 g_i + (x_i - Phi' M^-1 g_i)' (Phi' M^-1 Phi)^-1 (x_i - Phi' M^-1 g_i),   Phi = H X
+    -- the universal-kriging variance, with no rank-K basis and no sampling.  Returns n_grid host
+    values in vec() order; they do not depend on the data.
+    `method="cholesky"` (`gsi_op_posterior_variance`, nobs <= 32768): M is formed by nobs products of `op`, factored once on
+    the device, and the columns of C H' L^-T are squared and summed row by row in batches of `batch` columns (None: the rule of
+    the operator's own products).  `method="cg"`: no dense factor -- per batch J of unit columns E_J the solve
+    U_J = M^-1 E_J (`solve` with `precond` and `cg` = `tol`, `maxiter`, `strict`), T_J = C H' U_J, G_J = C H' E_J and
+    acc += rowdot(T_J, G_J) (`mat_rowdot_acc`); the drift terms come from one solve of the p columns of Phi.  `precond` and
+    `cg` belong to `method="cg"` only.  `return_info`: also a dict -- `path` ("fused": the device kernels, "composed": the host
+    path), `batches`, `batch`, `adjoint_columns`, `trapezoid_bytes` and, for "cg", `products` and `iters`."""
+    if method not in ("cholesky", "cg"):
+        raise ValueError("method must be 'cholesky' or 'cg'")
+    if not (hasattr(op, "model") or hasattr(op, "_P")):
+        raise TypeError("posterior_variance_exact needs a LinearDataOperator or an FFTOperatorAt")
+    ctx, lib = op.ctx, op.ctx.lib
+    nobs = op.shape[0]
+    n = int(np.prod(op.grid_op.Ns))
+    d = _diag_arg(noise, nobs)
+    X = np.zeros((n, 0), order="F") if drift_grid is None else L.fmat(np.asarray(drift_grid, dtype=np.float64).reshape(n, -1),
+                                                                       "drift_grid")
+    p = X.shape[1]
+    if batch is not None and int(batch) < 1:
+        raise ValueError("batch must be at least 1 (None: the operator's own rule)")
+    if method == "cholesky":
+        if precond is not None or cg:
+            raise ValueError("precond and the solver's keywords (tol, maxiter, strict) apply to method='cg' only: "
+                             "method='cholesky' runs no iterative solve")
+        var = np.zeros(n)
+        info = (C.c_int64 * 8)()
+        L.check(lib.gsi_op_posterior_variance(ctx.h, op.h, L.dptr(d) if d is not None else None, L.dptr(X) if p else None, n, p,
+                                              0 if batch is None else int(batch), L.dptr(var), info), lib)
+        rep = {k: int(v) for k, v in zip(POSTX_INFO, info)}
+        rep["path"] = PATHS.get(rep["path"], rep["path"])
+        rep["method"] = method
+        return (var, rep) if return_info else var
+    if batch is None:
+        bw = max(2, ((2 << 30) // 8) // (2 * max(n, 1)))
+        bw += bw & 1
+    else:
+        bw = int(batch)
+    bw = max(1, min(bw, nobs))
+    rep = {"method": method, "path": "composed", "batches": 0, "batch": bw, "adjoint_columns": 0, "products": 0, "iters": 0}
+    acc = DeviceMatrix.from_host(ctx, np.zeros((n, 1)))
+    try:
+        for c0 in range(0, nobs, bw):
+            b = min(bw, nobs - c0)
+            Eh = np.zeros((nobs, b), order="F")
+            Eh[np.arange(c0, c0 + b), np.arange(b)] = 1.0
+            handles = [DeviceMatrix.from_host(ctx, Eh)]
+            try:
+                Uj, srep = solve(op, handles[0], diag=d, precond=precond, return_info=True, **cg)
+                handles.append(Uj)
+                handles.append(_prior_adjoint_any(op, Uj))
+                handles.append(_prior_adjoint_any(op, handles[0]))
+                mat_rowdot_acc(handles[2], handles[3], acc)
+            finally:
+                for h in handles:
+                    h.close()
+            rep["batches"] += 1
+            rep["adjoint_columns"] += 2 * b
+            rep["products"] += srep["products"]
+            rep["iters"] = max(rep["iters"], int(srep["iters"].max()))
+        acch = acc.to_host()[:, 0]
+    finally:
+        acc.close()
+    U, S = np.zeros((n, 0)), np.zeros((0, 0))
+    if p:
+        Phi = op.model.apply_dev(X) if hasattr(op, "model") else FFTRF.interpolate(ctx, op._P, X, op.Ns, box=op._B)
+        if isinstance(Phi, DeviceMatrix):
+            Pd, Phi = Phi, Phi.to_host()
+            Pd.close()
+        MPhi, srep = solve(op, Phi, diag=d, precond=precond, return_info=True, **cg)
+        rep["products"] += srep["products"]
+        S = Phi.T @ MPhi
+        Md = DeviceMatrix.from_host(ctx, MPhi)
+        try:
+            Ud = _prior_adjoint_any(op, Md)
+            try:
+                U = Ud.to_host()
+            finally:
+                Ud.close()
+        finally:
+            Md.close()
+        rep["adjoint_columns"] += p
+    e0 = np.zeros(n)
+    e0[0] = 1.0
+    c00 = float(op.grid_op.matmul(e0)[0])
+    var = _posterior_finish(c00, acch, U, X, S)
+    return (var, rep) if return_info else var
+
+
+def linear_inversion(grid_op, model, y, noise, drift_grid=None, precond=None, return_info=False, variance=False,
+                     variance_method="cholesky", **cg):
     """The exact linear geostatistical inversion of the data `y` = H s + v of a `LinearForwardModel` (identity link), with the
     prior s ~ N(X beta, C), C the covariance of the FFT operator `grid_op`, beta unknown, and v ~ N(0, diag(noise)):
         (H C H' + R) xi + H X beta = y,   (H X)' xi = 0,   s_hat = X beta + C H' xi.
@@ -428,7 +558,8 @@ def linear_inversion(grid_op, model, y, noise, drift_grid=None, precond=None, re
     system is solved as `kriging_weights` solves it, by ONE solve of the 1 + p columns [y, H X]; H X is `model.apply_dev` of
     `drift_grid` (n_grid x p, the drift functions at the cells; None: no drift, beta empty).  `precond`: a `Preconditioner`
     built on such an operator; `cg`: `tol`, `maxiter`, `strict` of `solve`.  Returns `s_hat` (n_grid, host), `xi`, `beta`;
-    with `return_info` also the report of `solve`."""
+    with `return_info` also the report of `solve`.  `variance=True` appends the exact posterior variance of every cell
+    (`posterior_variance_exact` with `method=variance_method`; "cg" reuses `precond` and `cg`) to the returned tuple."""
     from .pcga import linear_data_operator
     yv = np.asarray(y, dtype=np.float64).reshape(-1)
     if yv.size != model.nobs:
@@ -446,9 +577,13 @@ def linear_inversion(grid_op, model, y, noise, drift_grid=None, precond=None, re
             beta = np.linalg.solve(HX.T @ MG, HX.T @ My)
             xi = My - MG @ beta
         s_hat = estimate_field(op, xi, beta, X)
+        out = (s_hat, xi, beta, rep) if return_info else (s_hat, xi, beta)
+        if variance:
+            kw = dict(precond=precond, **cg) if variance_method == "cg" else {}
+            out = out + (posterior_variance_exact(op, noise, X, method=variance_method, **kw),)
     finally:
         op.close()
-    return (s_hat, xi, beta, rep) if return_info else (s_hat, xi, beta)
+    return out
 
 
 def condition_on_linear_data(op, F, y, noise, eps=None, seed=None, **cg):
