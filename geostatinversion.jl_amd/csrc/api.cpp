@@ -13,6 +13,7 @@
 #include "pointcov.hpp"
 #include "fftrf_points.hpp"
 #include "cg_state.hpp"
+#include "lu_schedule.hpp"
 
 using namespace gsi;
 
@@ -1124,6 +1125,17 @@ int gsi_lu_L(gsi_ctx* ctx, const double* Y, int64_t m, int64_t l, double* L_out,
       check_async_errors(ctx->c);
     });
     be->download2d(L_out, m, P.p, m, m, l);
+  });
+}
+
+int gsi_lu_schedule(int64_t l, int32_t* widths, int32_t* nblocks) {
+  return guarded([&] {
+    REQUIRE(widths && nblocks, "NULL argument");
+    REQUIRE(l >= 1, "lu_schedule: need l >= 1");
+    std::vector<int> w;
+    REQUIRE(lu_schedule_choose(l, w), "lu_schedule: GSI_LU_SCHEDULE is not a list of block widths (16, 32, 48, 64; a last block of 1 .. 64)");
+    for (size_t i = 0; i < w.size(); ++i) widths[i] = w[i];
+    *nblocks = (int32_t)w.size();
   });
 }
 

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "hip_backend_impl.hpp"
+#include "lu_schedule.hpp"
 
 namespace gsi {
 
@@ -41,8 +42,9 @@ void HipBackend::lu_L_impl(double* Y, int64_t m, int64_t l, int64_t ld, int32_t*
     if (const char* e = getenv("GSI_LU_POLL_LIMIT")) w2.poll_limit = atoi(e);
     if (const char* e = getenv("GSI_LU_TEST_MUTE_EPOCH")) w2.mute_epoch = (uint32_t)atoi(e);
     if (const char* e = getenv("GSI_LU_COOPERATIVE")) w2.cooperative = (e[0] == '1');
-    static const int nb_env = getenv("GSI_LU_NB") ? atoi(getenv("GSI_LU_NB")) : 0;
-    w2.nb = (nb_env == 32 || nb_env == 64) ? nb_env : hipk::LU2_NB;
+    // the block widths: GSI_LU_SCHEDULE=48,48,64 (a list for the panels it sums to), GSI_LU_NB=32|64 (uniform), else the
+    // minimum of the pass model (lu_schedule.hpp)
+    if (!lu_schedule_choose(l, w2.widths)) throw Error(GSI_ERR_ARG, "lu: GSI_LU_SCHEDULE is not a list of block widths (16, 32, 48, 64; a last block of 1 .. 64)");
     grow(ws_lu_, hipk::lu2_work_bytes(l, w2.grid));
     hipk::lu2_carve(w2, l, ws_lu_.p);
     w2.info = flags_ + FLAG_LU_INFO;

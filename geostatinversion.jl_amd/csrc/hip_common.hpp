@@ -4,6 +4,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstddef>
+#include <vector>
 #include "pointcov.hpp"
 
 namespace gsi { struct FwdProduct; struct FwdAdjoint; }   // backend.hpp
@@ -151,15 +152,16 @@ void interp_adjoint(hipStream_t st, const IadjDev& p, const double* X, int64_t l
 // ---- panel_lu_leaf.hip: register-resident leaves (panels of <= 4096 rows per CU, a little more with overflow rows); the
 //      updates between the blocks are panel_lu_blocks.hip's ----
 constexpr int LU2_LEAF = 8;           // leaf width: columns a thread keeps in registers
-constexpr int LU2_NB = 64;            // widest block (left-looking leaves inside, one rank-NB update per block)
+constexpr int LU2_NB = 64;            // widest block (left-looking leaves inside; lu_schedule.hpp: LU_SCHED_MAX_W)
 constexpr int LU2_RES_COPIES = 8;     // copies of the per-step result record (one per group of pollers)
 constexpr int LU2_REC_GRANULES = 64;  // one published record per workgroup and pivot step: 64 8-byte granules (512 B)
 struct Lu2Work {
   unsigned long long* recs;   // [2][grid][LU2_REC_GRANULES] candidate records, then [2][LU2_RES_COPIES][LU2_REC_GRANULES] results
-  double* u12;      // [l * l]: U12 of every block, block i at i * nb * l
+  double* u12;      // [l * l]: the U rows of every block, U(p, c) at p + c * l
   int32_t* ipiv;    // [l]
   int32_t* info;    // [1] first exactly-zero pivot (1-based); -1: the exchange between workgroups timed out
-  int bs, rpt, grid, nb;
+  int bs, rpt, grid;
+  std::vector<int> widths;     // the block schedule (lu_schedule.hpp): 16 .. 64 columns each, a last block of what is left
   int poll_limit = 0;          // polls before a workgroup gives up on a record (0: the default, ~ seconds)
   uint32_t mute_epoch = 0;     // tests only: the last workgroup publishes nothing at this pivot step (1-based)
   bool cooperative = false;    // launch the leaves with hipLaunchCooperativeKernel (co-residency guaranteed by the runtime)

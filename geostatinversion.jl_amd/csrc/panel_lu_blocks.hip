@@ -1,16 +1,17 @@
-// panel_lu_blocks.hip -- what happens BETWEEN the 64-column blocks of `F = lu(Y); Q = F.L`, whichever form factors the leaves
-// inside them (panel_lu_dev.hpp lists the forms).  Every instantiation of these kernels is compiled here and nowhere else.
+// panel_lu_blocks.hip -- what happens BETWEEN the blocks (16 .. 64 columns each: lu_schedule.hpp) of `F = lu(Y); Q = F.L`,
+// whichever form factors the leaves inside them (panel_lu_dev.hpp lists the forms).  Every instantiation of these kernels is
+// compiled here and nowhere else.
 //   * lu_leftlook_kernel + lu_urows_kernel: the LEFT-looking update of the single-rank forms (described further down).
 //   * lu_u12_kernel + lu_rankk_kernel: the right-looking update (every trailing column re-read and rewritten after every
 //     block), kept for the row-sharded form, the bit-identity reference, which reaches it through lus_u12_block / lus_rankk.
-//   * lu_blocks: the loop over the blocks that the resident (lu2_L) and the streamed (lu3_L) form run their leaves in;
-//     lu2_extract_L_kernel ends it.
+//   * lu_blocks: the loop over the blocks of a schedule that the resident (lu2_L) and the streamed (lu3_L) form run their
+//     leaves in; lu2_extract_L_kernel ends it.
 #include "panel_lu_dev.hpp"
 #include <type_traits>
 
 namespace gsi { namespace hipk {
 
-// U12 = L11^-1 A12 for the K x K unit-lower block at (jb, jb) and the columns [c0, c1): out[k + (c - c0) K].
+// U12 = L11^-1 A12 for the K x K unit-lower block at (jb, jb) and the columns [c0, c1): out[k + (c - c0) ldo].
 // Thread = one column; L11 in LDS (broadcast reads), the column in registers.
 // (256 threads bring L11 in -- K^2 / 256 loads each instead of K^2 / 64: the kernel sits between two blocks of the
 // factorization and is all latency -- then the first wave solves its 64 columns.)
@@ -37,7 +38,7 @@ __device__ inline void u12_solve(const double* L11, double (&x)[K]) {
 
 template <int K>
 __global__ __launch_bounds__(256) void lu_u12_kernel(const double* __restrict__ Y, int64_t ld, int64_t jb, int64_t jbrow,
-                                                     int64_t c0, int64_t c1, double* __restrict__ out) {
+                                                     int64_t c0, int64_t c1, double* __restrict__ out, int64_t ldo) {
   // jb: the block's first COLUMN (global); jbrow: the row of Y that holds global row jb (jb - row0 for a row shard)
   __shared__ double L11[K * K];
   u12_stage_L11<K>(L11, Y, ld, jb, jbrow);
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) void lu_u12_kernel(const double* __restrict__ 
 #pragma unroll
   for (int r = 0; r < K; ++r) x[r] = col[r];
   u12_solve<K>(L11, x);
-  double* o = out + (c - c0) * K;
+  double* o = out + (c - c0) * ldo;
 #pragma unroll
   for (int r = 0; r < K; ++r) o[r] = x[r];
 }
@@ -163,16 +164,21 @@ static void launch_rankk(hipStream_t st, unsigned grid, double* Y, int64_t ld, i
 // ---- left-looking order between blocks (the single-rank factorizations; the row-sharded form stays right-looking) ----------
 // Block i's columns are left alone until block i is next; then ONE pass brings rows [jb, m) of them up to date with every
 // finished block to their left, and after its leaves the U rows of block i (rows [jb, jb + NB) of all trailing columns) are
-// brought up to date the same way and solved.  U12 of every block is kept: U12(i, k, c) = U12[i ldu + c NB + k], ldu = NB l.
+// brought up to date the same way and solved.  The solved U rows of every block are kept as the strict block upper triangle of
+// an l x l matrix, U(p, c) = U[p + c ldu], ldu = l: nothing in it depends on where the block boundaries are.
+// The blocks need not be equally wide (lu_schedule.hpp chooses the widths): the kernels walk the finished columns 0 .. jb in
+// 16-column tiles, whatever blocks they were factored in, and are instantiated for the width of the block they update.
 // Every element sees the MFMAs of lu_rankk_kernel -- operands -U12 (A) and L (B) in its lane mapping, k in groups of four,
-// blocks in ascending order -- on an accumulator that stays in registers instead of crossing HBM between the blocks (an fp64
+// in ascending order -- on an accumulator that stays in registers instead of crossing HBM between the blocks (an fp64
 // store + reload is exact), and the U rows are solved by lu_u12_kernel's own u12_solve: the factors are bit for bit the
-// right-looking ones (the row-sharded form is the reference).  Passes over the panel per block update: 64 i (L) + 128 (C).
+// right-looking ones (the row-sharded form is the reference), and the same bits for every schedule: an element's k terms come
+// in the same order wherever a block ends.  Passes over the panel for the update before a b-column block at jb: jb (L) + 2 b (C).
 constexpr int LL_WAVES = 12;                                   // 12 waves x 16 rows: three waves per SIMD, one workgroup per CU
 constexpr int LL_BS = 64 * LL_WAVES;
-constexpr size_t LL_LDS = (size_t)4 * 64 * 66 * sizeof(double);   // -U12 images of up to four earlier 64-column blocks (132 KB)
-template <int NB>
-constexpr int ll_group() { return (int)(LL_LDS / ((size_t)NB * (NB + 2) * sizeof(double))); }
+constexpr int LL_UNIT = 64;                                    // finished columns per -U image and per L fragment set
+constexpr int LL_KP = LL_UNIT + 2;                             // padded k stride of an image (LL_KP / 2 odd, as in lu_rankk_kernel)
+constexpr int LL_GROUP = 4;                                    // images per launch: 256 finished columns
+constexpr size_t LL_LDS = (size_t)LL_GROUP * 64 * LL_KP * sizeof(double);   // -U images of up to 256 finished columns (132 KB)
 
 // a uniform pointer the compiler may not re-derive from its start: one 64-bit SGPR pair walks the columns instead of one
 // hoisted base per column (32 of them ran the kernel out of SGPRs and into spills)
@@ -182,30 +188,32 @@ __device__ __forceinline__ char* ll_advance(char* p, int64_t step) {
   return p;
 }
 
-// A[jb:m, jb:jb+tc] -= sum over the earlier blocks ip0 <= q < ip1 of L[jb:m, q NB:(q+1) NB] U12(q, :, jb:jb+tc).
-// Persistent: the workgroup stages the -U12 images once (LDS [(q NB + c) KP + k], KP / 2 odd as in lu_rankk_kernel), then
-// every wave walks 16-row chunks on its own, no barrier: C tile (16 rows x NB columns) in registers for the whole chunk, the
-// L fragments of block q + 1 in flight behind the NB / 16 x NB / 4 MFMAs of block q (64 cycles each: one LDS read per MFMA is
-// far below the LDS rate).  Addressing: a 32-bit per-lane offset (row, and kk columns over) set once per chunk + one walking
-// uniform column pointer -- no vector address arithmetic between the MFMAs.
+// A[jb:m, jb:jb+tc] -= L[jb:m, p0:p1] U(p0:p1, jb:jb+tc): the tc <= NB columns of the block at jb against the finished columns
+// [p0, p1) (p0 a multiple of 64, p1 - p0 a multiple of 16 and <= 256; more finished columns: one launch per 256, ascending).
+// Persistent: the workgroup stages the -U images once -- one per 64 finished columns, LDS [(u NB + c) KP + k]; the last may
+// hold 16, 32 or 48 -- then every wave walks 16-row chunks on its own, no barrier: C tile (16 rows x NB columns) in registers
+// for the whole chunk, the L fragments of the next 64 columns in flight behind the NB / 16 x 16 MFMAs of these 64 (64 cycles
+// each: one LDS read per MFMA is far below the LDS rate).  Addressing: a 32-bit per-lane offset (row, and kk columns over) set
+// once per chunk + one walking uniform column pointer -- no vector address arithmetic between the MFMAs.
 // WIDE: panels whose 3 ld * 8 bytes do not fit that offset (ld > 1.7e8 rows) take 64-bit per-lane offsets.
 template <int NB, bool WIDE>
 __global__ __launch_bounds__(LL_BS) void lu_leftlook_kernel(double* __restrict__ Y, int64_t ld, int64_t m, int64_t jb, int tc,
-                                                            int ip0, int ip1, const double* __restrict__ U12, int64_t ldu) {
+                                                            int p0, int p1, const double* __restrict__ U, int64_t ldu) {
   typedef double double4_t __attribute__((ext_vector_type(4)));
   typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type off_t;
-  constexpr int KP = NB + 2, NT = NB / 16, NS = NB / 4;
+  constexpr int KP = LL_KP, NT = NB / 16, NS = LL_UNIT / 4;
+  typedef std::integral_constant<int, NS> whole_t;
   extern __shared__ double us[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int jl = lane & 15, kk = lane >> 4;
-  const int nbk = ip1 - ip0;
-  for (int e = tid; e < nbk * NB * NB; e += LL_BS) {
-    const int k = e % NB, c = (e / NB) % NB, q = e / (NB * NB);
-    us[(q * NB + c) * KP + k] = (c < tc) ? -U12[(int64_t)(ip0 + q) * ldu + (jb + c) * NB + k] : 0.0;
+  const int np = p1 - p0, nfull = np / LL_UNIT, rem = np % LL_UNIT;
+  for (int c = wave; c < NB; c += LL_WAVES) {         // a wave per block column, the lanes along k
+    const double* ucol = U + p0 + (jb + c) * ldu;
+    for (int k = lane; k < np; k += 64) us[((k / LL_UNIT) * NB + c) * KP + k % LL_UNIT] = (c < tc) ? -ucol[k] : 0.0;
   }
   __syncthreads();
-  const int lb = jl * KP + kk;                      // this lane's fb: -U12(q, 4 s + kk, 16 tt + jl)
+  const int lb = jl * KP + kk;                      // this lane's fb: -U(64 u + 4 s + kk, 16 tt + jl)
   const int64_t nch = (m - jb + 15) / 16;
   const int64_t cs = ld * (int64_t)sizeof(double);  // bytes per column
   for (int64_t ch = (int64_t)blockIdx.x * LL_WAVES + wave; ch < nch; ch += (int64_t)gridDim.x * LL_WAVES) {
@@ -227,31 +235,49 @@ __global__ __launch_bounds__(LL_BS) void lu_leftlook_kernel(double* __restrict__
         }
     }
     double fa[NS], fn[NS];
-    char* pf = reinterpret_cast<char*>(Y + rb + (int64_t)ip0 * NB * ld);   // walks the L columns, block after block
-    auto load_frag = [&](double (&f)[NS]) {
+    char* pf = reinterpret_cast<char*>(Y + rb + (int64_t)p0 * ld);   // walks the L columns p0 .. p1
+    auto load_frag = [&](auto n, double (&f)[NS]) {  // the next 4 n columns
 #pragma unroll
-      for (int s = 0; s < NS; ++s) {
+      for (int s = 0; s < decltype(n)::value; ++s) {
         f[s] = *at(pf);
         pf = ll_advance(pf, 4 * cs);
       }
     };
-    auto run = [&](const double (&f)[NS], int q) {
-      const double* ub = us + (q - ip0) * NB * KP + lb;
+    auto run = [&](auto n, const double (&f)[NS], int u) {
+      const double* ub = us + u * NB * KP + lb;
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
+      for (int s = 0; s < decltype(n)::value; ++s)
 #pragma unroll
         for (int tt = 0; tt < NT; ++tt)
           acc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(ub[16 * tt * KP + 4 * s], f[s], acc[tt], 0, 0, 0);
     };
-    load_frag(fa);
-    int q = ip0;
-    for (; q + 1 < ip1; ++q) {                      // (the last block peeled: the prefetch is unconditional in the loop)
-      load_frag(fn);
-      run(fa, q);
+    // the 16, 32 or 48 columns behind the last whole 64 (rem is uniform: scalar branches)
+    auto load_rest = [&](double (&f)[NS]) {
+      if (rem == 16) load_frag(std::integral_constant<int, 4>{}, f);
+      else if (rem == 32) load_frag(std::integral_constant<int, 8>{}, f);
+      else if (rem == 48) load_frag(std::integral_constant<int, 12>{}, f);
+    };
+    auto run_rest = [&](const double (&f)[NS]) {
+      if (rem == 16) run(std::integral_constant<int, 4>{}, f, nfull);
+      else if (rem == 32) run(std::integral_constant<int, 8>{}, f, nfull);
+      else if (rem == 48) run(std::integral_constant<int, 12>{}, f, nfull);
+    };
+    if (nfull > 0) {
+      load_frag(whole_t{}, fa);
+      int u = 0;
+      for (; u + 1 < nfull; ++u) {                    // (the last whole 64 peeled: the prefetch is unconditional in the loop)
+        load_frag(whole_t{}, fn);
+        run(whole_t{}, fa, u);
 #pragma unroll
-      for (int s = 0; s < NS; ++s) fa[s] = fn[s];
+        for (int s = 0; s < NS; ++s) fa[s] = fn[s];
+      }
+      load_rest(fn);
+      run(whole_t{}, fa, u);
+      run_rest(fn);
+    } else {
+      load_rest(fa);
+      run_rest(fa);
     }
-    run(fa, q);
     const bool live = rb + jl < m;
     char* p = cbase;
 #pragma unroll
@@ -264,13 +290,13 @@ __global__ __launch_bounds__(LL_BS) void lu_leftlook_kernel(double* __restrict__
   }
 }
 
-// The U rows of block i = jb / K: rows [jb, jb + K) of the trailing columns [c0, c1) brought up to date with the K-column
-// blocks 0 .. i - 1 (the sequence above, -U12 read from L2: a few MB per factorization), then solved by u12_solve as in
-// lu_u12_kernel: out[k + (c - c0) K].  Workgroup = 64 columns; waves 0 .. K / 16 - 1 hold 16 rows x 64 columns each.
+// The U rows of the K-column block at jb: rows [jb, jb + K) of the trailing columns [c0, c1) brought up to date with the
+// finished columns 0 .. jb (the sequence above, -U read from L2: a few MB per factorization), then solved by u12_solve as in
+// lu_u12_kernel and written into U: U[(jb + k) + c ldu].  Workgroup = 64 columns; waves 0 .. K / 16 - 1 hold 16 rows x 64
+// columns each.
 template <int K>
-__global__ __launch_bounds__(256) void lu_urows_kernel(const double* __restrict__ Y, int64_t ld, int64_t jb, int nprev,
-                                                       int64_t c0, int64_t c1, const double* __restrict__ U12, int64_t ldu,
-                                                       double* __restrict__ out) {
+__global__ __launch_bounds__(256) void lu_urows_kernel(const double* __restrict__ Y, int64_t ld, int64_t jb, int64_t c0,
+                                                       int64_t c1, double* U, int64_t ldu) {
   typedef double double4_t __attribute__((ext_vector_type(4)));
   constexpr int TP = K + 1;                    // [col][row] image of the updated rows, padded
   __shared__ double L11[K * K];
@@ -289,15 +315,15 @@ __global__ __launch_bounds__(256) void lu_urows_kernel(const double* __restrict_
         const int64_t c = cb + 16 * tt + kk + 4 * reg;
         acc[tt][reg] = (c < c1) ? Y[row + c * ld] : 0.0;
       }
-    for (int q = 0; q < nprev; ++q) {
-      const double* ub = U12 + (int64_t)q * ldu;
+    for (int64_t p = 0; p < jb; p += 16) {       // (jb is a multiple of 16: only a last block is ragged)
 #pragma unroll
-      for (int s = 0; s < K / 4; ++s) {
-        const double fa = Y[row + ((int64_t)q * K + 4 * s + kk) * ld];
+      for (int s = 0; s < 4; ++s) {
+        const int64_t k = p + 4 * s + kk;
+        const double fa = Y[row + k * ld];
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt) {
           const int64_t c = cb + 16 * tt + jl;
-          const double fb = (c < c1) ? -ub[c * K + 4 * s + kk] : 0.0;
+          const double fb = (c < c1) ? -U[k + c * ldu] : 0.0;
           acc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb, fa, acc[tt], 0, 0, 0);
         }
       }
@@ -315,27 +341,35 @@ __global__ __launch_bounds__(256) void lu_urows_kernel(const double* __restrict_
 #pragma unroll
   for (int r = 0; r < K; ++r) x[r] = T[tid * TP + r];
   u12_solve<K>(L11, x);
-  double* o = out + (c - c0) * K;
+  double* o = U + jb + c * ldu;
 #pragma unroll
   for (int r = 0; r < K; ++r) o[r] = x[r];
 }
 
+// f(std::integral_constant<int, W>) for the kernel width W = 16, 32, 48 or 64 that holds w columns
+template <class F>
+static void lu_for_width(int w, F&& f) {
+  if (w <= 16) f(std::integral_constant<int, 16>{});
+  else if (w <= 32) f(std::integral_constant<int, 32>{});
+  else if (w <= 48) f(std::integral_constant<int, 48>{});
+  else f(std::integral_constant<int, 64>{});
+}
+
 template <int NB, bool WIDE>
 static void launch_leftlook_v(hipStream_t st, unsigned grid, double* Y, int64_t ld, int64_t m, int64_t jb, int tc,
-                              const double* U12, int64_t ldu) {
+                              const double* U, int64_t ldu) {
   static std::atomic<uint64_t> attr_mask{0};
   if (first_use_on_this_device(attr_mask))
     (void)hipFuncSetAttribute((const void*)lu_leftlook_kernel<NB, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LL_LDS);
-  const int nprev = (int)(jb / NB);
-  for (int ip0 = 0; ip0 < nprev; ip0 += ll_group<NB>()) {      // (more than four 64-column blocks: one launch per four)
-    const int ip1 = std::min(nprev, ip0 + ll_group<NB>());
-    const size_t shmem = (size_t)(ip1 - ip0) * NB * (NB + 2) * sizeof(double);
-    hipLaunchKernelGGL((lu_leftlook_kernel<NB, WIDE>), dim3(grid), dim3(LL_BS), shmem, st, Y, ld, m, jb, tc, ip0, ip1, U12, ldu);
+  for (int64_t p0 = 0; p0 < jb; p0 += LL_GROUP * LL_UNIT) {     // (more than 256 finished columns: one launch per 256)
+    const int64_t p1 = std::min<int64_t>(jb, p0 + LL_GROUP * LL_UNIT);
+    const size_t shmem = (size_t)((p1 - p0 + LL_UNIT - 1) / LL_UNIT) * NB * LL_KP * sizeof(double);
+    hipLaunchKernelGGL((lu_leftlook_kernel<NB, WIDE>), dim3(grid), dim3(LL_BS), shmem, st, Y, ld, m, jb, tc, (int)p0, (int)p1, U, ldu);
   }
 }
-// Step 1 of block [jb, jb + b) (jb > 0): its columns, rows [jb, m), brought up to date with every block to their left.
-static void lu_ll_update(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, int64_t jb, int b, int nb,
-                         const double* u12) {
+// Step 1 of block [jb, jb + b) (jb > 0, a multiple of 16): its columns, rows [jb, m), brought up to date with every column to
+// their left.
+static void lu_ll_update(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, int64_t jb, int b, const double* u12) {
   if (jb == 0 || m <= jb) return;
   int dev = 0, ncu = 0;
   (void)hipGetDevice(&dev);
@@ -343,28 +377,23 @@ static void lu_ll_update(hipStream_t st, double* Y, int64_t ld, int64_t m, int64
   const int64_t chunks = (m - jb + 15) / 16;
   const unsigned grid = (unsigned)std::min<int64_t>((chunks + LL_WAVES - 1) / LL_WAVES, ncu);   // one workgroup per CU
   const bool wide = (3 * ld + 32) * (int64_t)sizeof(double) >= ((int64_t)1 << 32);
-  const int64_t ldu = (int64_t)nb * l;
-  if (nb == 64) {
-    if (wide) launch_leftlook_v<64, true>(st, grid, Y, ld, m, jb, b, u12, ldu);
-    else launch_leftlook_v<64, false>(st, grid, Y, ld, m, jb, b, u12, ldu);
-  } else {
-    if (wide) launch_leftlook_v<32, true>(st, grid, Y, ld, m, jb, b, u12, ldu);
-    else launch_leftlook_v<32, false>(st, grid, Y, ld, m, jb, b, u12, ldu);
-  }
+  lu_for_width(b, [&](auto w) {
+    constexpr int NB = decltype(w)::value;
+    if (wide) launch_leftlook_v<NB, true>(st, grid, Y, ld, m, jb, b, u12, l);
+    else launch_leftlook_v<NB, false>(st, grid, Y, ld, m, jb, b, u12, l);
+  });
 }
-// Step 3 of the full block at jb (after its leaves): U12 of the block for every trailing column [jb + nb, l).
-static void lu_ll_urows(hipStream_t st, const double* Y, int64_t ld, int64_t l, int64_t jb, int nb, double* u12) {
-  const int64_t c0 = jb + nb, ldu = (int64_t)nb * l;
+// Step 3 of the block [jb, jb + b) (after its leaves): its U rows for every trailing column [jb + b, l).  Only a block of 16,
+// 32, 48 or 64 columns has columns to its right.
+static void lu_ll_urows(hipStream_t st, const double* Y, int64_t ld, int64_t l, int64_t jb, int b, double* u12) {
+  const int64_t c0 = jb + b;
   if (c0 >= l) return;
   const unsigned gu = (unsigned)((l - c0 + 63) / 64);
-  double* out = u12 + (jb / nb) * ldu + c0 * nb;
-  if (nb == 64) {
-    if (jb == 0) hipLaunchKernelGGL(lu_u12_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, out);
-    else hipLaunchKernelGGL(lu_urows_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, (int)(jb / nb), c0, l, u12, ldu, out);
-  } else {
-    if (jb == 0) hipLaunchKernelGGL(lu_u12_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, out);
-    else hipLaunchKernelGGL(lu_urows_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, (int)(jb / nb), c0, l, u12, ldu, out);
-  }
+  lu_for_width(b, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    if (jb == 0) hipLaunchKernelGGL(lu_u12_kernel<K>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb, c0, l, u12 + c0 * l, l);
+    else hipLaunchKernelGGL(lu_urows_kernel<K>, dim3(gu), dim3(256), 0, st, Y, ld, jb, c0, l, u12, l);
+  });
 }
 
 // top l x l: unit diagonal, zero strict upper triangle (what Julia's F.L returns)
@@ -377,12 +406,15 @@ __global__ void lu2_extract_L_kernel(double* __restrict__ Y, int64_t ld, int64_t
   }
 }
 
-void lu_blocks(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, int nb, double* u12, const LuLeafFn& leaf) {
-  for (int64_t jb = 0; jb < l; jb += nb) {
-    const int b = (int)((l - jb < nb) ? (l - jb) : nb);
-    lu_ll_update(st, Y, ld, m, l, jb, b, nb, u12);         // left-looking: this block's columns, once, before its leaves
+void lu_blocks(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, const std::vector<int>& widths, double* u12,
+               const LuLeafFn& leaf) {
+  if (!lu_schedule_valid(l, widths)) throw std::runtime_error("lu_blocks: the block widths do not fit the panel");
+  int64_t jb = 0;
+  for (const int b : widths) {
+    lu_ll_update(st, Y, ld, m, l, jb, b, u12);             // left-looking: this block's columns, once, before its leaves
     for (int64_t j0 = jb; j0 < jb + b; j0 += LW) leaf(jb, b, j0, (int)((jb + b - j0 < LW) ? (jb + b - j0) : LW));
-    lu_ll_urows(st, Y, ld, l, jb, nb, u12);                // only full blocks have columns to their right
+    lu_ll_urows(st, Y, ld, l, jb, b, u12);                 // (the last block has no columns to its right)
+    jb += b;
   }
   int eb = (int)((l * l + 255) / 256);
   if (eb > 1024) eb = 1024;
@@ -393,8 +425,8 @@ void lu_blocks(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, int 
 void lus_u12_block(hipStream_t st, const double* Y, int64_t ld, int64_t row0, int64_t jb, int b, int64_t c0, int64_t c1,
                    double* U12) {
   const unsigned gu = (unsigned)((c1 - c0 + 63) / 64);
-  if (b == 64) hipLaunchKernelGGL(lu_u12_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb - row0, c0, c1, U12);
-  else hipLaunchKernelGGL(lu_u12_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb - row0, c0, c1, U12);
+  if (b == 64) hipLaunchKernelGGL(lu_u12_kernel<64>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb - row0, c0, c1, U12, (int64_t)64);
+  else hipLaunchKernelGGL(lu_u12_kernel<32>, dim3(gu), dim3(256), 0, st, Y, ld, jb, jb - row0, c0, c1, U12, (int64_t)32);
 }
 void lus_rankk(hipStream_t st, double* Y, int64_t ld, int64_t mloc, int64_t row0, int64_t jb, int b, int64_t c0, int64_t t,
                const double* U12) {

@@ -2,16 +2,19 @@
 // panel_lu_*.hip files include it (the public declarations are in hip_common.hpp).
 //   panel_lu_leaf.hip      resident leaves: one persistent launch per 8-column leaf, the leaf's values in registers
 //   panel_lu_streamed.hip  streamed leaves: panels taller than the register file
-//   panel_lu_blocks.hip    the updates between the 64-column blocks, and the block loop the two forms above run their leaves in
+//   panel_lu_blocks.hip    the updates between the blocks (16 .. 64 columns: lu_schedule.hpp), and the block loop the two forms above run their leaves in
 //   panel_lu_sharded.hip   step primitives of the row-sharded form, the interchanges across ranks
 // Every form finds LAPACK dgetrf's pivots (first maximal |entry| wins), leaves L in pivoted row order and does the same
 // operations on the same values in the same order: the factors are bit-identical between the forms.
 // The device helpers sit in an unnamed namespace: every file that includes this compiles (and inlines) its own.
 #pragma once
 #include "hip_common.hpp"
+#include "lu_schedule.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <functional>
+#include <stdexcept>
+#include <vector>
 
 namespace gsi { namespace hipk {
 
@@ -110,10 +113,12 @@ struct LuMrArgs {
   unsigned long long* peer[LU2_MAX_RANKS];   // every rank's record buffer (peer[rank] == recs)
 };
 
-// The block loop of the single-rank forms (panel_lu_blocks.hip).  Every block [jb, jb + b) of <= nb columns: brought up to
-// date with the blocks to its left, leaf(jb, b, j0, wd) for each of its leaves [j0, j0 + wd) of <= LW columns in turn, its
-// U12 for every trailing column (u12: l * l doubles).  Then the top l x l becomes L's (unit diagonal, zeros above).
+// The block loop of the single-rank forms (panel_lu_blocks.hip).  Every block [jb, jb + b) of the schedule `widths`
+// (lu_schedule.hpp: lu_schedule_valid): brought up to date with the columns to its left, leaf(jb, b, j0, wd) for each of its
+// leaves [j0, j0 + wd) of <= LW columns in turn, its U rows for every trailing column (u12: l * l doubles, the U rows of the
+// panel at [row + column * l]).  Then the top l x l becomes L's (unit diagonal, zeros above).
 using LuLeafFn = std::function<void(int64_t jb, int b, int64_t j0, int wd)>;
-void lu_blocks(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, int nb, double* u12, const LuLeafFn& leaf);
+void lu_blocks(hipStream_t st, double* Y, int64_t ld, int64_t m, int64_t l, const std::vector<int>& widths, double* u12,
+               const LuLeafFn& leaf);
 
 }}  // namespace gsi::hipk

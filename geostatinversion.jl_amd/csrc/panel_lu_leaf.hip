@@ -930,7 +930,7 @@ size_t lu2_work_bytes(int64_t l, int grid) {
 void lu2_carve(Lu2Work& w, int64_t l, void* work) {
   char* base = (char*)work;
   w.recs = (unsigned long long*)base; base += lu2_record_bytes(w.grid);
-  w.u12 = (double*)base; base += sizeof(double) * (size_t)l * (size_t)l;   // U12 of every block (left-looking between blocks)
+  w.u12 = (double*)base; base += sizeof(double) * (size_t)l * (size_t)l;   // the U rows of every block, whatever the schedule
   w.ipiv = (int32_t*)base;
 }
 
@@ -938,7 +938,7 @@ void lu2_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, const Lu
   // the record tags count pivot steps from 1: clear both record sets
   (void)hipMemsetAsync(w.recs, 0, lu2_record_bytes(w.grid), st);
   uint32_t epoch = 0;
-  lu_blocks(st, Y, ld, m, l, w.nb, w.u12, [&](int64_t jb, int, int64_t j0, int wd) {
+  lu_blocks(st, Y, ld, m, l, w.widths, w.u12, [&](int64_t jb, int, int64_t j0, int wd) {
     // every leaf keeps the same grid: workgroups whose rows lie beyond m still take part in the exchange
     if (w.bs == 256 && w.rpt == 1) launch_leaf<256, 1>(st, w.grid, Y, ld, m, l, jb, j0, wd, w, epoch);
     else if (w.bs == 256) launch_leaf<256, 4>(st, w.grid, Y, ld, m, l, jb, j0, wd, w, epoch);

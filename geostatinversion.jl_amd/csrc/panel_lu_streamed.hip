@@ -369,7 +369,9 @@ void lu3_L(hipStream_t st, double* Y, int64_t m, int64_t l, int64_t ld, void* wo
   int32_t* ipiv = (int32_t*)base;
   *ipiv_out = ipiv;
   static const bool fuse = !(getenv("GSI_LU_TALL_NOFUSE") != nullptr);     // A/B: every leaf closed by a pass of its own
-  lu_blocks(st, Y, ld, m, l, LU2_NB, u12, [&](int64_t jb, int b, int64_t j0, int wd) {
+  std::vector<int> widths;               // the streamed leaves keep uniform 64-column blocks
+  lu_schedule_uniform(l, LU2_NB, widths);
+  lu_blocks(st, Y, ld, m, l, widths, u12, [&](int64_t jb, int b, int64_t j0, int wd) {
     Lu3Step p{Y, ld, m, (int32_t)l, (int32_t)j0, 0, wd, pval, pidx, stt, ipiv, info};
     const int g = lu3_grid(m - j0);
     if (j0 == jb) hipLaunchKernelGGL((lu3_open_kernel<false, false>), dim3(g), dim3(T_BS), 0, st, (int32_t)jb, p);
