@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import GsiError, load, LIB_PATH
 from .context import (Context, Operator, DeviceMatrix, dense_operator, gridcov_operator,
                       gridcov_implicit_operator, pointcov_implicit_operator, fft_powerlaw_operator, fft_gridcov_operator, lowrank_synthetic_operator,
-                      default_context)
+                      default_context, fft_gridcov_derivative)
 from . import randmatfact as RandMatFact
 from .randmatfact import rangefinder, randsvd, randsvd_rows, eig_nystrom, colnorms, lu_L, lu_L_dev, lu_L_sharded, lu_L_sharded_virtual, qr_thinQ, svd_tall, gemm, gemm_view, cq_gram_round, pivoted_cholesky, principal_factor
 from .lowrank import LowRankCovMatrix, PCGALowRankMatrix, device_samples
@@ -25,7 +25,8 @@ from .gridcov import GridCovSampler, gridcov_sampler, lowrank_gridcov_operator, 
 from . import kriging as Kriging
 from .kriging import (solve, kriging_weights, krige_to_grid, condition_fields, mat_axpy, lowrank_preconditioner,
                       Preconditioner, logdet, log_likelihood, solve_trace, estimate_field, linear_inversion,
-                      condition_on_linear_data, posterior_variance_exact, mat_rowdot_acc)
+                      condition_on_linear_data, posterior_variance_exact, mat_rowdot_acc, mat_bilinear,
+                      op_bilinear_terms, log_likelihood_grad, covariance_family, CovarianceFamily, fit_covariance)
 from .pcga import (pcgadirect, pcgalsqr, rga, pcga, DeviceBasis, ShardedDeviceBasis, LinearForwardModel, posterior_variance,
                    posterior_realizations, LinearDataOperator, linear_data_operator)
 
@@ -40,4 +41,6 @@ __all__ = [
     "lowrank_preconditioner", "Preconditioner", "logdet", "log_likelihood", "solve_trace", "pivoted_cholesky", "principal_factor", "getxis_pivchol",
     "LinearDataOperator", "linear_data_operator", "estimate_field", "linear_inversion", "condition_on_linear_data",
     "posterior_variance_exact", "mat_rowdot_acc",
+    "fft_gridcov_derivative", "mat_bilinear", "op_bilinear_terms", "log_likelihood_grad", "covariance_family", "CovarianceFamily",
+    "fit_covariance",
 ]

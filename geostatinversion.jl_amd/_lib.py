@@ -61,6 +61,9 @@ SIGNATURES = {
                                      C.c_double]),
     "gsi_op_fft_gridcov_table": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), c_dp, c_dp, C.c_double]),
     "gsi_op_fft_at": (C.c_int, [c_vp, C.POINTER(c_vp), c_vp, c_dp, c_i64, c_dp]),
+    "gsi_op_fft_gridcov_deriv": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.c_int, c_dp, C.c_double, C.c_double,
+                                           C.c_int]),
+    "gsi_op_fft_at_like": (C.c_int, [c_vp, C.POINTER(c_vp), c_vp, c_vp]),
     "gsi_gridcov_sampler_create": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int, C.POINTER(c_i64), C.POINTER(c_i64), C.c_int, c_dp,
                                              C.c_double, C.c_double, C.c_double, C.c_double, c_dp]),
     "gsi_gridcov_sampler_info": (C.c_int, [c_vp, C.POINTER(c_i64), c_dp]),
@@ -149,6 +152,9 @@ SIGNATURES = {
     "gsi_pcga_posterior_variance": (C.c_int, [c_vp, c_vp, c_vp, c_dp, c_dp, c_dp, C.POINTER(c_i64)]),
     "gsi_op_posterior_variance": (C.c_int, [c_vp, c_vp, c_dp, c_dp, c_i64, c_i64, c_i64, c_dp, C.POINTER(c_i64)]),
     "gsi_mat_rowdot_acc": (C.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "gsi_mat_bilinear": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_dp, c_i64, c_dp, c_dp]),
+    "gsi_op_bilinear_terms": (C.c_int, [c_vp, c_vp, c_dp, c_vp, c_i64, c_vp, c_dp, c_dp]),
+    "gsi_mat_copy_cols": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64]),
     "gsi_ctx_profile": (C.c_int, [c_vp, C.c_int]),
     "gsi_ctx_phase_reset": (C.c_int, [c_vp]),
     "gsi_ctx_phase_times": (C.c_int, [c_vp, c_dp, C.POINTER(c_i64)]),

@@ -13,10 +13,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libgsi_hip.so")
-SOURCES = ["gemm_f64.hip", "gemm_f64_gen1.hip", "syrk_f64.hip", "panel_lu_leaf.hip", "panel_lu_blocks.hip", "panel_lu_streamed.hip", "panel_lu_sharded.hip", "panel_qr.hip", "cholqr.hip", "lowrank_power.hip", "jacobi_svd.hip", "misc.hip", "lsqr_dev.hip", "block_cg.hip", "block_pcg.hip", "block_slq.hip", "pivoted_chol.hip", "pointcov_gemm.hip", "fft_cov.hip", "fft_gridcov_plan.hip", "fftrf_sample.hip", "fftrf_interp.hip", "interp_adjoint.hip", "gridcov_sample.hip","pcga_forward.hip", "fwd_adjoint.hip", "chol_saddle.hip", "posterior_var.hip", "posterior_exact.hip",
+SOURCES = ["gemm_f64.hip", "gemm_f64_gen1.hip", "syrk_f64.hip", "panel_lu_leaf.hip", "panel_lu_blocks.hip", "panel_lu_streamed.hip", "panel_lu_sharded.hip", "panel_qr.hip", "cholqr.hip", "lowrank_power.hip", "jacobi_svd.hip", "misc.hip", "lsqr_dev.hip", "block_cg.hip", "block_pcg.hip", "block_slq.hip", "pivoted_chol.hip", "pointcov_gemm.hip", "fft_cov.hip", "fft_gridcov_plan.hip", "fftrf_sample.hip", "fftrf_interp.hip", "interp_adjoint.hip", "gridcov_sample.hip","pcga_forward.hip", "fwd_adjoint.hip", "chol_saddle.hip", "posterior_var.hip", "posterior_exact.hip", "bilinear_terms.hip",
            "hip_backend.hip", "hip_backend_products.hip", "hip_backend_sampler.hip", "hip_backend_panels.hip", "hip_backend_lowrank.hip", "hip_backend_pcga.hip",
            "hip_comm.hip", "pipeline.cpp", "solvers.cpp", "pcga.cpp", "api.cpp"]
-HEADERS = ["backend.hpp", "hip_backend.hpp", "hip_backend_impl.hpp", "hip_common.hpp", "panel_lu_dev.hpp", "lu_schedule.hpp", "pipeline.hpp", "solvers.hpp", "pcga.hpp", "lsqr_state.hpp", "cg_state.hpp", "block_cg_host.hpp", "slq_state.hpp", "pchol_state.hpp", "pivoted_chol_host.hpp", "pointcov.hpp", "pointcov_gen.hpp", "host_staging.hpp", "gemm_f64_kernel.inc.hpp", "fft_line.hpp", "jacobi_sched.hpp", "fwd_plan.hpp", "fwd_adjoint_plan.hpp", "fwd_adjoint_host.hpp", "fftrf_points.hpp", "interp_adjoint_plan.hpp", "saddle_host.hpp", "posterior_host.hpp", "posterior_exact_host.hpp", "../../include/gsi_hip.h"]
+HEADERS = ["backend.hpp", "hip_backend.hpp", "hip_backend_impl.hpp", "hip_common.hpp", "panel_lu_dev.hpp", "lu_schedule.hpp", "pipeline.hpp", "solvers.hpp", "pcga.hpp", "lsqr_state.hpp", "cg_state.hpp", "block_cg_host.hpp", "slq_state.hpp", "pchol_state.hpp", "pivoted_chol_host.hpp", "pointcov.hpp", "pointcov_gen.hpp", "host_staging.hpp", "gemm_f64_kernel.inc.hpp", "fft_line.hpp", "jacobi_sched.hpp", "fwd_plan.hpp", "fwd_adjoint_plan.hpp", "fwd_adjoint_host.hpp", "fftrf_points.hpp", "interp_adjoint_plan.hpp", "saddle_host.hpp", "posterior_host.hpp", "posterior_exact_host.hpp", "bilinear_terms_host.hpp", "../../include/gsi_hip.h"]
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
             "-Wno-unused-result", "-Wno-unused-value"]
 # Every kernel file is compiled with the backend's resource-usage remarks on; what hipcc made of each kernel (VGPRs, AGPRs,

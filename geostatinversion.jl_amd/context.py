@@ -322,6 +322,28 @@ def fft_gridcov_operator(ctx, Ns, kind="exponential", ell=1.0, theta=0.0, sigma2
     return _fft_grid_operator(ctx, h, Ns)
 
 
+COV_DPARAMS = {"log_sigma2": 0, "log_ell": 1, "log_ell0": 2, "log_ell1": 3, "log_ell2": 4, "theta": 5, "nugget": 6}
+
+
+def fft_gridcov_derivative(ctx, Ns, param, kind="exponential", ell=1.0, theta=0.0, sigma2=1.0):
+    """The derivative of `fft_gridcov_operator(ctx, Ns, kind, ell, theta, sigma2, nugget)` with respect to one parameter, as an
+    FFT operator of the same type (`gsi_op_fft_gridcov_deriv`).  `param`: "log_sigma2", "log_ell"
+    (all axes jointly), "log_ell0" / "log_ell1" / "log_ell2", "theta" (2-D only) or "nugget".  The operator remembers `Ns`,
+    so `fft_operator_at` and `linear_data_operator` give W dC W' and H dC H'.  It is not positive semidefinite: it is for
+    products (`log_likelihood_grad`), not for solves."""
+    Ns = [int(v) for v in Ns]
+    arr = (C.c_int64 * len(Ns))(*Ns)
+    h = C.c_void_p()
+    k = POINTCOV_KINDS[kind] if isinstance(kind, str) else int(kind)
+    prm = COV_DPARAMS[param] if isinstance(param, str) else int(param)
+    ells = [float(ell)] * len(Ns) if np.ndim(ell) == 0 else [float(v) for v in ell]
+    if len(ells) != len(Ns):
+        raise ValueError("ell must be one length or one per axis")
+    earr = (C.c_double * len(ells))(*ells)
+    L.check(ctx.lib.gsi_op_fft_gridcov_deriv(ctx.h, C.byref(h), len(Ns), arr, k, earr, float(theta), float(sigma2), prm), ctx.lib)
+    return _fft_grid_operator(ctx, h, Ns)
+
+
 class DeviceMatrix(_Handle):
     """Column-major Float64 matrix resident in HBM (`gsi_mat`)."""
     _destroy = "gsi_mat_destroy"

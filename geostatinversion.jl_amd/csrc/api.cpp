@@ -577,8 +577,10 @@ int gsi_op_fft_powerlaw_fftrf(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_
 // The FFT operator for a covariance function (kind / ell / theta / sigma2) or a table of lags (table / table_mirror) on the
 // grid: OP_FFT_COV with another plan (Backend::fftcov_create_lags).  The arguments are checked here; the limit on the embedded
 // points (2^31) is the backend's, as for the power-law plans: refused before it allocates anything.
+enum { NOT_A_DERIVATIVE = -1000 };     // make_fft_gridcov's dparam for the covariance itself (any other value is checked)
 static void make_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, int kind, const double* ell, double theta,
-                             double sigma2, double nugget, const double* table, const double* table_mirror, bool from_table) {
+                             double sigma2, double nugget, const double* table, const double* table_mirror, bool from_table,
+                             int dparam = NOT_A_DERIVATIVE) {
   REQUIRE(ctx && op && N, "NULL argument");
   *op = nullptr;
   REQUIRE(ndims >= 1 && ndims <= 3, "fft covariance: 1, 2 or 3 grid dimensions");
@@ -619,6 +621,13 @@ static void make_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t
     REQUIRE(std::isfinite(sigma2) && sigma2 > 0.0, "fft grid covariance: sigma2 must be finite and > 0");
     REQUIRE(std::isfinite(theta), "fft grid covariance: theta must be finite");
     REQUIRE(theta == 0.0 || ndims == 2, "fft grid covariance: theta (a rotation) is for 2-D grids only");
+    if (dparam != NOT_A_DERIVATIVE) {
+      REQUIRE(dparam >= 0 && dparam < pointcov::NUM_DPARAMS,
+              "fft grid covariance derivative: param must be one of GSI_DPARAM_LOG_SIGMA2 .. GSI_DPARAM_NUGGET (0 .. 6)");
+      REQUIRE(dparam != pointcov::D_THETA || ndims == 2, "fft grid covariance derivative: GSI_DPARAM_THETA is for 2-D grids only");
+      REQUIRE(dparam < pointcov::D_LOG_ELL0 || dparam > pointcov::D_LOG_ELL2 || dparam - pointcov::D_LOG_ELL0 < ndims,
+              "fft grid covariance derivative: GSI_DPARAM_LOG_ELL<a> needs a < ndims");
+    }
   }
   std::unique_ptr<gsi_op> o(new gsi_op());
   Operator& A = o->op;
@@ -626,7 +635,8 @@ static void make_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t
   default_shard(n, ctx->c.nranks(), ctx->c.rank(), &A.row0, &A.mloc);     // as make_fft_powerlaw: the plan is replicated
   A.fft_ndims = ndims;
   for (int a = 0; a < 3; ++a) A.fft_N[a] = N3[a];
-  own_fft_plan(A, ctx->c.be->fftcov_create_lags(N3, kind, ell3, theta, sigma2, nugget, table, table_mirror));
+  if (dparam != NOT_A_DERIVATIVE) own_fft_plan(A, ctx->c.be->fftcov_create_lags_deriv(N3, kind, ell3, theta, sigma2, dparam));
+  else own_fft_plan(A, ctx->c.be->fftcov_create_lags(N3, kind, ell3, theta, sigma2, nugget, table, table_mirror));
   *op = o.release();
 }
 
@@ -652,7 +662,37 @@ int gsi_op_fft_at(gsi_ctx* ctx, gsi_op** op, const gsi_op* grid_op, const double
     for (int a = 0; a < 3; ++a) A.fft_N[a] = C.fft_N[a];
     A.plan = C.plan;
     A.plan_ref = C.plan_ref;
-    A.at = ctx->c.be->points_at_create(plan, A.at_info);
+    own_points_at(A, ctx->c.be->points_at_create(plan, A.at_info));
+    *op = o.release();
+  });
+}
+
+// A = W C' W' on the points of an existing OP_FFT_COV_AT operator: the points plan and its inverted index are
+// shared (Operator::at_ref), nothing is planned or uploaded.  A fit builds its operators anew at every parameter value.
+int gsi_op_fft_at_like(gsi_ctx* ctx, gsi_op** op, const gsi_op* grid_op, const gsi_op* like) {
+  return guarded([&] {
+    REQUIRE(ctx && op && grid_op && like, "NULL argument");
+    *op = nullptr;
+    const Operator& C = grid_op->op;
+    const Operator& B = like->op;
+    REQUIRE(C.ctx == &ctx->c, "gsi_op_fft_at_like: the grid operator belongs to another context");
+    REQUIRE(B.ctx == &ctx->c, "gsi_op_fft_at_like: the like operator belongs to another context");
+    REQUIRE(C.kind == OP_FFT_COV && C.plan != nullptr,
+            "gsi_op_fft_at_like: the grid operator must be an FFT covariance operator (gsi_op_fft_powerlaw[_fftrf], gsi_op_fft_gridcov[_table], gsi_op_fft_gridcov_deriv)");
+    REQUIRE(B.kind == OP_FFT_COV_AT && B.at != nullptr, "gsi_op_fft_at_like: like must be an operator of gsi_op_fft_at");
+    REQUIRE(!ctx->c.comm, "gsi_op_fft_at_like: one GPU only -- not available on a context with a communicator");
+    REQUIRE(C.fft_ndims == B.fft_ndims && C.fft_N[0] == B.fft_N[0] && C.fft_N[1] == B.fft_N[1] && C.fft_N[2] == B.fft_N[2],
+            "gsi_op_fft_at_like: the grid operator and the like operator must have the same grid shape");
+    std::unique_ptr<gsi_op> o(new gsi_op());
+    Operator& A = o->op;
+    A.ctx = &ctx->c; A.kind = OP_FFT_COV_AT; A.m = B.m; A.n = B.m; A.row0 = 0; A.mloc = B.m; A.ld = 0;
+    A.fft_ndims = C.fft_ndims;
+    for (int a = 0; a < 3; ++a) A.fft_N[a] = C.fft_N[a];
+    A.plan = C.plan;
+    A.plan_ref = C.plan_ref;
+    A.at = B.at;
+    A.at_ref = B.at_ref;
+    for (int k = 0; k < 4; ++k) A.at_info[k] = B.at_info[k];
     *op = o.release();
   });
 }
@@ -688,6 +728,17 @@ int gsi_op_fft_gridcov(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, i
 int gsi_op_fft_gridcov_table(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, const double* table,
                              const double* table_mirror, double nugget) {
   return guarded([&] { make_fft_gridcov(ctx, op, ndims, N, 0, nullptr, 0.0, 1.0, nugget, table, table_mirror, true); });
+}
+
+// d C / d param for the covariance of gsi_op_fft_gridcov: the same checks, then the derivative's plan
+int gsi_op_fft_gridcov_deriv(gsi_ctx* ctx, gsi_op** op, int ndims, const int64_t* N, int kind, const double* ell, double theta,
+                             double sigma2, int param) {
+  return guarded([&] {
+    if (op) *op = nullptr;
+    REQUIRE(param >= 0 && param < pointcov::NUM_DPARAMS,
+            "fft grid covariance derivative: param must be one of GSI_DPARAM_LOG_SIGMA2 .. GSI_DPARAM_NUGGET (0 .. 6)");
+    make_fft_gridcov(ctx, op, ndims, N, kind, ell, theta, sigma2, 0.0, nullptr, nullptr, false, param);
+  });
 }
 
 // ---- Gaussian fields with a grid covariance function (circulant embedding; Backend::gridcov_sampler_*) ----
@@ -1985,6 +2036,74 @@ int gsi_mat_rowdot_acc(gsi_ctx* ctx, const gsi_mat* A, const gsi_mat* B, gsi_mat
                                    ", not rows of A x 1 = " + std::to_string(A->rows) + " x 1");
     REQUIRE(acc != A && acc != B && acc->buf.p != A->buf.p && acc->buf.p != B->buf.p, "gsi_mat_rowdot_acc: acc must not be A or B");
     rowdot_acc(ctx->c, A->rows, A->cols, A->buf.p, A->rows, B->buf.p, B->rows, acc->buf.p);
+    check_async_errors(ctx->c);
+  });
+}
+
+// ---- the bilinear forms of the likelihood gradient ----------------------------------
+static void require_bilinear_g(const char* who, int64_t g, int64_t b) {
+  if (g < 0 || g > b || g > 16)
+    throw Error(GSI_ERR_ARG, std::string(who) + ": g = " + std::to_string(g) + " must be in 0 .. min(b, 16), b = " + std::to_string(b));
+}
+static void require_finite_diag(const char* who, const double* dd, int64_t n) {
+  if (dd)
+    for (int64_t i = 0; i < n; ++i)
+      if (!std::isfinite(dd[i])) throw Error(GSI_ERR_ARG, std::string(who) + ": the diagonal holds a non-finite value");
+}
+
+int gsi_mat_copy_cols(gsi_ctx* ctx, gsi_mat* dst, int64_t dst_col0, const gsi_mat* src, int64_t src_col0, int64_t ncols) {
+  return guarded([&] {
+    REQUIRE(ctx && dst && src, "gsi_mat_copy_cols: NULL argument");
+    REQUIRE(dst->ctx == ctx && src->ctx == ctx, "gsi_mat_copy_cols: dst or src belongs to another context");
+    REQUIRE(dst != src && dst->buf.p != src->buf.p, "gsi_mat_copy_cols: dst must not be src");
+    REQUIRE(dst->rows == src->rows, "gsi_mat_copy_cols: dst and src must have the same number of rows");
+    REQUIRE(ncols >= 0 && dst_col0 >= 0 && src_col0 >= 0 && dst_col0 + ncols <= dst->cols && src_col0 + ncols <= src->cols,
+            "gsi_mat_copy_cols: the column ranges must lie inside dst and src");
+    if (ncols == 0 || dst->rows == 0) return;
+    const int64_t n = dst->rows;
+    ctx->c.be->copy2d(dst->buf.p + (size_t)n * (size_t)dst_col0, n, src->buf.p + (size_t)n * (size_t)src_col0, n, n, ncols);
+  });
+}
+
+int gsi_mat_bilinear(gsi_ctx* ctx, const gsi_mat* L, const gsi_mat* Y, const gsi_mat* R, const double* dd, int64_t g,
+                     double* gram_out, double* t_out) {
+  return guarded([&] {
+    REQUIRE(ctx && L && Y, "gsi_mat_bilinear: ctx, L or Y is NULL");
+    REQUIRE(L->ctx == ctx && Y->ctx == ctx && (R == nullptr || R->ctx == ctx), "gsi_mat_bilinear: L, Y or R belongs to another context");
+    REQUIRE(L->rows >= 1 && L->cols >= 1, "gsi_mat_bilinear: L must have at least one row and one column");
+    REQUIRE(Y->rows == L->rows && Y->cols == L->cols, "gsi_mat_bilinear: Y must have the shape of L");
+    REQUIRE(R == nullptr || (R->rows == L->rows && R->cols == L->cols), "gsi_mat_bilinear: R must have the shape of L");
+    REQUIRE(dd == nullptr || R != nullptr, "gsi_mat_bilinear: dd needs R");
+    require_bilinear_g("gsi_mat_bilinear", g, L->cols);
+    REQUIRE(g == 0 || gram_out != nullptr, "gsi_mat_bilinear: gram_out is NULL with g > 0");
+    REQUIRE(g == L->cols || t_out != nullptr, "gsi_mat_bilinear: t_out is NULL with g < b");
+    require_finite_diag("gsi_mat_bilinear", dd, L->rows);
+    bilinear_terms(ctx->c, L->rows, L->cols, g, L->buf.p, Y->buf.p, R ? R->buf.p : nullptr, dd, gram_out, t_out);
+    check_async_errors(ctx->c);
+  });
+}
+
+int gsi_op_bilinear_terms(gsi_ctx* ctx, const gsi_op* dop, const double* ddiag, const gsi_mat* X, int64_t g, const gsi_mat* Wz,
+                          double* gram_out, double* t_out) {
+  return guarded([&] {
+    REQUIRE(ctx && X, "gsi_op_bilinear_terms: ctx or X is NULL");
+    REQUIRE(!ctx->c.comm, "gsi_op_bilinear_terms: one GPU only -- ctx has a communicator");
+    REQUIRE(X->ctx == ctx && (Wz == nullptr || Wz->ctx == ctx), "gsi_op_bilinear_terms: X or Wz belongs to another context");
+    REQUIRE(dop == nullptr || dop->op.ctx == &ctx->c, "gsi_op_bilinear_terms: dop belongs to another context");
+    const int64_t n = X->rows, b = X->cols;
+    REQUIRE(n >= 1 && b >= 1, "gsi_op_bilinear_terms: X must have at least one row and one column");
+    require_bilinear_g("gsi_op_bilinear_terms", g, b);
+    REQUIRE(b == g || Wz != nullptr, "gsi_op_bilinear_terms: Wz is NULL with g < X's columns");
+    if (Wz != nullptr && (Wz->rows != n || Wz->cols != b - g))
+      throw Error(GSI_ERR_ARG, "gsi_op_bilinear_terms: Wz is " + std::to_string(Wz->rows) + " x " + std::to_string(Wz->cols) +
+                                   ", not rows of X x (columns of X - g) = " + std::to_string(n) + " x " + std::to_string(b - g));
+    if (dop != nullptr && (dop->op.m != n || dop->op.n != n))
+      throw Error(GSI_ERR_ARG, "gsi_op_bilinear_terms: dop is " + std::to_string(dop->op.m) + " x " + std::to_string(dop->op.n) +
+                                   ", X has " + std::to_string(n) + " rows");
+    REQUIRE(g == 0 || gram_out != nullptr, "gsi_op_bilinear_terms: gram_out is NULL with g > 0");
+    REQUIRE(g == b || t_out != nullptr, "gsi_op_bilinear_terms: t_out is NULL with g < X's columns");
+    require_finite_diag("gsi_op_bilinear_terms", ddiag, n);
+    op_bilinear_terms(ctx->c, dop ? &dop->op : nullptr, ddiag, X->buf.p, n, b, g, Wz ? Wz->buf.p : nullptr, gram_out, t_out);
     check_async_errors(ctx->c);
   });
 }

@@ -170,6 +170,12 @@ class Backend {
     (void)N; (void)kind; (void)ell; (void)theta; (void)sigma2; (void)nugget; (void)table; (void)table_mirror;
     throw Error(1 /* GSI_ERR_ARG */, "fft covariance from a covariance function or table: not supported by this backend");
   }
+  // The plan of d A / d param for the covariance function of fftcov_create_lags (gsi_op_fft_gridcov_deriv):
+  // param = pointcov::D_*.  Its spectrum is not positive.  Arguments are validated by the caller.
+  virtual void* fftcov_create_lags_deriv(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, int param) {
+    (void)N; (void)kind; (void)ell; (void)theta; (void)sigma2; (void)param;
+    throw Error(1 /* GSI_ERR_ARG */, "fft covariance derivative: not supported by this backend");
+  }
   virtual void fftcov_destroy(void* plan) = 0;
   // Y (n x l, ld ldy) = A X (n x l, ld ldx)
   virtual void fftcov_apply(void* plan, int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy) = 0;
@@ -629,6 +635,16 @@ class Backend {
   // 1, or 0: "not mine".
   virtual int carried_rows(const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd) {
     (void)T; (void)ld; (void)nobs; (void)p; (void)Wd;
+    return 0;
+  }
+
+  // ---- the bilinear forms of the likelihood gradient ----
+  // L, Y, R: n x b panels in backend memory (ld n); dd: n values in backend memory, or null (then R is not read); with
+  // V = Y + dd .* R: gram (g x g, HOST) [a + g c] = sum_i L[i, a] V[i, c], t (b - g, HOST) [j - g] = sum_i L[i, j] V[i, j], in
+  // the order of bilinear_terms_host.hpp.  1, or 0: "not mine", nothing ran, and the caller runs that header on downloaded panels.
+  virtual int bilinear_terms(int64_t n, int64_t b, int64_t g, const double* L, const double* Y, const double* R, const double* dd,
+                             double* gram, double* t) {
+    (void)n; (void)b; (void)g; (void)L; (void)Y; (void)R; (void)dd; (void)gram; (void)t;
     return 0;
   }
 

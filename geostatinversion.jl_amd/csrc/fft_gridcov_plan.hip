@@ -3,6 +3,8 @@
 // symmetric 2-D kernels, the sine sibling of fft_cos_matrix and the step that turns the re-embedded sums into a plan.
 // The passes that apply the plan are fft_cov.hip's, unchanged; the per-axis factors are applied by the contraction kernel
 // (hip_backend.hip:fftcov_spectrum_of_lags).  Everything here runs once per plan: plain grid-stride kernels.
+// gsi_op_fft_gridcov_deriv is the same plan from the lags of the covariance's derivative with respect to
+// one parameter: fft_lag_table_deriv_kernel, a sibling of fft_lag_table_kernel; nothing behind it differs.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "hip_common.hpp"
@@ -43,6 +45,36 @@ void fft_lag_table(hipStream_t st, double* cp, double* cm, const int64_t N[3], i
                    double sn, double sigma2) {
   hipLaunchKernelGGL(fft_lag_table_kernel, dim3(plan_grid_for(N[0] * N[1] * N[2], 4096)), dim3(256), 0, st, cp, cm, N[0], N[1], N[2],
                      kind, inv_ell[0], inv_ell[1], inv_ell[2], cs, sn, sigma2);
+}
+
+// fft_lag_table_kernel's sibling for gsi_op_fft_gridcov_deriv: cp / cm <- d (sigma2 k(r)) / d param at the
+// same lags, pointcov::dkernel's formulas.  A derivative is neither positive nor (for theta) even along the axes: cm is
+// written whenever the caller passes it, and nothing behind this kernel clamps the spectrum.  rot = ell1/ell0 - ell0/ell1.
+__global__ __launch_bounds__(256) void fft_lag_table_deriv_kernel(double* __restrict__ cp, double* __restrict__ cm, int64_t N0,
+                                                                  int64_t N1, int64_t N2, int kind, int param, double ie0, double ie1,
+                                                                  double ie2, double cs, double sn, double sigma2, double rot) {
+  const int64_t total = N0 * N1 * N2;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = e % N0, r = e / N0, i1 = r % N1, i2 = r / N1;
+    const double t0 = (double)i0, t1 = (double)i1, t2 = (double)i2;
+    const double w = t2 * ie2;
+    {
+      const double u = (cs * t0 + sn * t1) * ie0, v = (-sn * t0 + cs * t1) * ie1;
+      cp[e] = pointcov::dkernel(kind, param, sigma2, u, v, w, rot);
+    }
+    if (cm != nullptr) {
+      const double u = (cs * t0 - sn * t1) * ie0, v = (-sn * t0 - cs * t1) * ie1;
+      cm[e] = pointcov::dkernel(kind, param, sigma2, u, v, w, rot);
+    }
+  }
+}
+// param == D_LOG_SIGMA2 is the covariance itself without its nugget: fft_lag_table's own kernel, hence its bits
+void fft_lag_table_deriv(hipStream_t st, double* cp, double* cm, const int64_t N[3], int kind, int param, const double inv_ell[3],
+                         double cs, double sn, double sigma2) {
+  if (param == pointcov::D_LOG_SIGMA2) { fft_lag_table(st, cp, cm, N, kind, inv_ell, cs, sn, sigma2); return; }
+  const double rot = inv_ell[0] / inv_ell[1] - inv_ell[1] / inv_ell[0];
+  hipLaunchKernelGGL(fft_lag_table_deriv_kernel, dim3(plan_grid_for(N[0] * N[1] * N[2], 4096)), dim3(256), 0, st, cp, cm, N[0], N[1],
+                     N[2], kind, param, inv_ell[0], inv_ell[1], inv_ell[2], cs, sn, sigma2, rot);
 }
 
 // (c+, c-) -> (c_ee, c_oo) = ((c+ + c-) / 2, (c+ - c-) / 2), in place

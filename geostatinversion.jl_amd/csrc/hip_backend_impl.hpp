@@ -151,6 +151,7 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   void* fftcov_create(const int64_t N[3], double beta, int fftrf) override;
   void* fftcov_create_lags(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, double nugget,
                            const double* table, const double* table_mirror) override;
+  void* fftcov_create_lags_deriv(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, int param) override;
   void fftcov_destroy(void* plan) override;
   void fftcov_apply(void* plan, int64_t l, const double* X, int64_t ldx, double* Y, int64_t ldy) override;
   void center_rows(double* S, int64_t n, int64_t N, int64_t ld) override;
@@ -291,6 +292,8 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   int trapezoid_rows(double* T, int64_t ld, int64_t nobs, int64_t p, const double* diag, const double* Phi,
                      int64_t ldphi) override;
   int carried_rows(const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd) override;
+  int bilinear_terms(int64_t n, int64_t b, int64_t g, const double* L, const double* Y, const double* R, const double* dd,
+                     double* gram, double* t) override;
 
  private:
   // ---- hip_backend.hip ----
@@ -324,6 +327,9 @@ class __attribute__((visibility("hidden"))) HipBackend final : public HipDevice 
   void gemm_trmm_upper(const char* who, const GemmWs& ws, int64_t m, int64_t l, int64_t k, const double* A, int64_t lda,
                        const double* B, int64_t ldb, double* C, int64_t ldc, hipk::GemmPlan* plan = nullptr);
   std::unique_ptr<FftCov> fftcov_new_plan(const int64_t N[3], int fftrf, bool* reembed, int* dims);
+  // fftcov_create_lags and fftcov_create_lags_deriv (dparam = pointcov::D_*, or -1: the covariance itself)
+  void* fftcov_plan_of_lags(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, double nugget,
+                            const double* table, const double* table_mirror, int dparam);
   void fft_rotate_apply(Scratch& buf, int64_t cur[3], int64_t& tot, int d, int64_t rows_out, int64_t period, FftFactor f);
   void fftcov_lags_to_spectrum(Scratch& bufh, int64_t cur[3], int64_t& tot, const FftCov* p, int d, bool sine);
   static size_t points_plan_doubles(const FftrfPointsPlan& plan);

@@ -320,4 +320,23 @@ int HipBackend::carried_rows(const double* T, int64_t ld, int64_t nobs, int64_t 
   return 1;
 }
 
+// The bilinear forms of the likelihood gradient (bilinear_terms.hip): per-chunk partial sums and their
+// ordered sum on the device, g g + b - g doubles back to the host.
+int HipBackend::bilinear_terms(int64_t n, int64_t b, int64_t g, const double* L, const double* Y, const double* R, const double* dd,
+                               double* gram, double* t) {
+  bind();
+  if (n < 1 || b < 1 || g < 0 || g > b || g > 16 || b - g > (int64_t)32 * 65534 || L == nullptr || Y == nullptr ||
+      (dd != nullptr && R == nullptr) || (g > 0 && gram == nullptr) || (b > g && t == nullptr))
+    throw Error(GSI_ERR_ARG, "bilinear_terms: need n, b >= 1, 0 <= g <= min(b, 16), L, Y, R with dd, and the outputs");
+  const int64_t nout = g * g + (b - g);
+  Scratch partial(this, hipk::bilinear_partial_doubles(n, b, g)), out(this, (size_t)nout);
+  hipk::bilinear_terms(st_, n, b, g, L, Y, R, dd, partial.p, out.p);
+  check_launch("bilinear_terms");
+  std::vector<double> h((size_t)nout);
+  download2d(h.data(), nout, out.p, nout, nout, 1);
+  for (int64_t e = 0; e < g * g; ++e) gram[e] = h[(size_t)e];
+  for (int64_t e = 0; e < b - g; ++e) t[e] = h[(size_t)(g * g + e)];
+  return 1;
+}
+
 }  // namespace gsi

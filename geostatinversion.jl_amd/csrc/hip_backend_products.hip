@@ -221,6 +221,16 @@ void* HipBackend::fftcov_create(const int64_t N[3], double beta, int fftrf) {
 // stored as (lambda' + nugget) / Mtot: no unit diagonal, and nugget * I on the box exactly.
 void* HipBackend::fftcov_create_lags(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, double nugget,
                                      const double* table, const double* table_mirror) {
+  return fftcov_plan_of_lags(N, kind, ell, theta, sigma2, nugget, table, table_mirror, -1);
+}
+// The derivative of that covariance with respect to one parameter (gsi_op_fft_gridcov_deriv): the same plan
+// from the derivative's lags (fft_lag_table_deriv).  d / d nugget = I: zero lags and a unit shift of the spectrum.  The
+// derivative with respect to theta is odd along each axis even at theta = 0, so it always takes the second quadrant.
+void* HipBackend::fftcov_create_lags_deriv(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, int param) {
+  return fftcov_plan_of_lags(N, kind, ell, theta, sigma2, param == pointcov::D_NUGGET ? 1.0 : 0.0, nullptr, nullptr, param);
+}
+void* HipBackend::fftcov_plan_of_lags(const int64_t N[3], int kind, const double ell[3], double theta, double sigma2, double nugget,
+                                      const double* table, const double* table_mirror, int dparam) {
   bind();
   bool reembed = false;
   int d = 0;
@@ -228,14 +238,15 @@ void* HipBackend::fftcov_create_lags(const int64_t N[3], int kind, const double 
   int64_t cur[3] = {p->N[0], p->N[1], p->N[2]};      // singleton axes do not move an element of the lag table
   int64_t tot = cur[0] * cur[1] * cur[2];
   // a second quadrant only where it differs from the first: both axes of a 2-D grid longer than one point
-  const bool mirrored = (table ? table_mirror != nullptr : theta != 0.0) && d == 2 && N[2] == 1;
+  const bool mirrored = (table ? table_mirror != nullptr : (theta != 0.0 || dparam == pointcov::D_THETA)) && d == 2 && N[2] == 1;
   Scratch cp(this, (size_t)tot), cm(this, mirrored ? (size_t)tot : 0);
   if (table) {
     upload2d(cp.p, tot, table, tot, tot, 1);
     if (mirrored) upload2d(cm.p, tot, table_mirror, tot, tot, 1);
   } else {
     const double inv_ell[3] = {1.0 / ell[0], 1.0 / ell[1], 1.0 / ell[2]};
-    hipk::fft_lag_table(st_, cp.p, cm.p, N, kind, inv_ell, std::cos(theta), std::sin(theta), sigma2);
+    if (dparam < 0) hipk::fft_lag_table(st_, cp.p, cm.p, N, kind, inv_ell, std::cos(theta), std::sin(theta), sigma2);
+    else hipk::fft_lag_table_deriv(st_, cp.p, cm.p, N, kind, dparam, inv_ell, std::cos(theta), std::sin(theta), sigma2);
     check_launch("fft_lag_table");
   }
   if (mirrored) {

@@ -88,6 +88,9 @@ void fft_plan_twiddles(hipStream_t st, double* lam, const int64_t M[3]);   // th
 // cp (and cm = the lags (t0, -t1) of a rotated 2-D kernel, or null) <- sigma2 k(r) over the box N, pointcov::kernel's kinds
 void fft_lag_table(hipStream_t st, double* cp, double* cm, const int64_t N[3], int kind, const double inv_ell[3], double cs,
                    double sn, double sigma2);
+// the same lags of d (sigma2 k(r)) / d param (pointcov::D_*); cm is written whenever it is not null
+void fft_lag_table_deriv(hipStream_t st, double* cp, double* cm, const int64_t N[3], int kind, int param, const double inv_ell[3],
+                         double cs, double sn, double sigma2);
 void fft_even_odd_split(hipStream_t st, double* cp, double* cm, int64_t total);   // -> ((c+ + c-) / 2, (c+ - c-) / 2)
 void fft_sin_matrix(hipStream_t st, double* out, int64_t rows, int64_t cols, int64_t period);   // w_r sin(2 pi r c / period)
 void fft_subtract(hipStream_t st, double* a, const double* b, int64_t total);     // a -= b
@@ -440,5 +443,14 @@ void px_unit_panel(hipStream_t st, double* E, int64_t ld, int64_t nobs, int64_t 
 void px_trapezoid_rows(hipStream_t st, double* T, int64_t ld, int64_t nobs, int64_t p, const double* diag, const double* Phi,
                        int64_t ldphi);
 void px_carried_rows(hipStream_t st, const double* T, int64_t ld, int64_t nobs, int64_t p, double* Wd);
+
+// ---- bilinear_terms.hip: the bilinear forms of the likelihood gradient ----
+// With V = Y + dd .* R (dd, R null: V = Y) over column-major n x b panels of leading dimension n:
+// gram[a + g c] = sum_i L[i, a] V[i, c] (a, c < g) and t[j - g] = sum_i L[i, j] V[i, j] (g <= j < b), summed per chunk of
+// BILINEAR_CHUNK rows into `partial` (bilinear_partial_doubles(n, b, g) doubles) and then over the chunks in ascending order.
+constexpr int64_t BILINEAR_CHUNK = 2048;
+size_t bilinear_partial_doubles(int64_t n, int64_t b, int64_t g);
+void bilinear_terms(hipStream_t st, int64_t n, int64_t b, int64_t g, const double* L, const double* Y, const double* R,
+                    const double* dd, double* partial, double* out);
 
 }}  // namespace gsi::hipk

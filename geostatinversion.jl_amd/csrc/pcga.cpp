@@ -5,6 +5,7 @@
 #include "saddle_host.hpp"
 #include "posterior_host.hpp"
 #include "posterior_exact_host.hpp"
+#include "bilinear_terms_host.hpp"
 #include "fwd_adjoint_host.hpp"
 #include <algorithm>
 #include <cmath>
@@ -548,6 +549,41 @@ int64_t rowdot_acc(Context& c, int64_t n, int64_t b, const double* A, int64_t ld
   postx_host::rowdot_acc(n, b, Ah.data(), n, same ? Ah.data() : Bh.data(), n, ah.data());
   be->upload2d(acc, n, ah.data(), n, n, 1);
   return PATH_HOST;
+}
+
+// ---- the bilinear forms of the likelihood gradient ------------------------------------------------
+int64_t bilinear_terms(Context& c, int64_t n, int64_t b, int64_t g, const double* L, const double* Y, const double* R,
+                       const double* dd, double* gram, double* t) {
+  Backend* be = c.be.get();
+  if (!env_forces_host("GSI_BILINEAR_HOST")) {
+    Buf ddev;
+    if (dd != nullptr) {
+      ddev = Buf(be, (size_t)n);
+      be->upload2d(ddev.p, n, dd, n, n, 1);
+    }
+    if (be->bilinear_terms(n, b, g, L, Y, R, ddev.p, gram, t) != 0) return PATH_BACKEND;
+  }
+  const size_t cnt = (size_t)n * (size_t)b;
+  std::vector<double> Lh(cnt), Yh(cnt), Rh(dd != nullptr ? cnt : (size_t)0);
+  be->download2d(Lh.data(), n, L, n, n, b);
+  be->download2d(Yh.data(), n, Y, n, n, b);
+  if (dd != nullptr) be->download2d(Rh.data(), n, R, n, n, b);
+  bilinear_host::terms(n, b, g, Lh.data(), Yh.data(), dd != nullptr ? Rh.data() : nullptr, dd, gram, t);
+  return PATH_HOST;
+}
+
+int64_t op_bilinear_terms(Context& c, const Operator* dop, const double* ddiag, const double* X, int64_t n, int64_t b, int64_t g,
+                          const double* Wz, double* gram, double* t) {
+  Backend* be = c.be.get();
+  Buf R(be, (size_t)n * (size_t)b), Y(be, (size_t)n * (size_t)b);
+  if (g > 0) be->copy2d(R.p, n, X, n, n, g);
+  if (b > g) be->copy2d(R.p + (size_t)n * (size_t)g, n, Wz, n, n, b - g);
+  if (dop != nullptr) {
+    op_mul(*dop, R.p, n, b, Y.p, n);
+  } else {
+    be->scal_copy(n * b, 0.0, R.p, Y.p);
+  }
+  return bilinear_terms(c, n, b, g, X, Y.p, R.p, ddiag, gram, t);
 }
 
 void posterior_variance_exact(const Operator& A, const double* diag, const double* X, int64_t ldx, int64_t p, int64_t batch,

@@ -83,6 +83,19 @@ int64_t rowdot_acc(Context& c, int64_t n, int64_t b, const double* A, int64_t ld
 void posterior_variance_exact(const Operator& A, const double* diag, const double* X, int64_t ldx, int64_t p, int64_t batch,
                               double* var, PostxInfo& info);
 
+// ---- the bilinear forms of the likelihood gradient (GSI_BILINEAR_HOST) ----
+// With V = Y + dd .* R for n x b panels L, Y, R in backend memory (ld n; dd: n HOST values or null, then R may be null):
+// gram (g x g, host) [a + g c] = sum_i L[i, a] V[i, c] and t (b - g, host) [j - g] = sum_i L[i, j] V[i, j], in the order of
+// bilinear_terms_host.hpp on either path: Backend::bilinear_terms, or -- when it declines or GSI_BILINEAR_HOST=1 -- that
+// header on downloaded panels.  The arguments are validated by the caller.  Returns the path.
+int64_t bilinear_terms(Context& c, int64_t n, int64_t b, int64_t g, const double* L, const double* Y, const double* R,
+                       const double* dd, double* gram, double* t);
+// The whole term of one parameter: R = [X[:, :g], Wz] (n x b, b = g + Wz's columns) formed in backend memory, Y = dop R by
+// op_mul with that operator's own batching (dop null: Y = 0), then bilinear_terms with L = X.  X: n x b, Wz: n x (b - g),
+// both in backend memory with ld n.  Only ddiag (n host values, or null) crosses the host link.  One rank.
+int64_t op_bilinear_terms(Context& c, const Operator* dop, const double* ddiag, const double* X, int64_t n, int64_t b, int64_t g,
+                          const double* Wz, double* gram, double* t);
+
 // A sparse forward model (gsi_fwd): h(s)[r] = sum over the nonzeros t of row r of the CSR matrix H of
 // vals[t] g(w[j_t] s[j_t]), g = identity (link 0) or exp (link 1).  The CSR arrays live in backend memory (integers in
 // double-typed allocations) with the segment table of fwd_plan.hpp beside them, and on the host for the host path.

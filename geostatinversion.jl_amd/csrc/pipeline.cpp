@@ -35,14 +35,19 @@ void check_async_errors(Context& c) {
 }
 
 Operator::~Operator() {
-  if (at && ctx && ctx->be) ctx->be->points_at_destroy(at);
-  // (the FFT plan goes with the last holder of plan_ref)
+  // (the FFT plan goes with the last holder of plan_ref, the points plan with the last holder of at_ref)
 }
 void own_fft_plan(Operator& A, void* plan) {
   Context* c = A.ctx;
   // (if the control block cannot be allocated, shared_ptr's constructor calls the deleter itself before it throws)
   A.plan_ref = std::shared_ptr<void>(plan, [c](void* p) { if (p && c && c->be) c->be->fftcov_destroy(p); });
   A.plan = plan;
+}
+
+void own_points_at(Operator& A, void* at) {
+  Context* c = A.ctx;
+  A.at_ref = std::shared_ptr<void>(at, [c](void* p) { if (p && c && c->be) c->be->points_at_destroy(p); });
+  A.at = at;
 }
 
 // C (m x l) = G[roff .. roff + m, koff .. koff + k) * B for the two generated (never stored) symmetric covariances: a table

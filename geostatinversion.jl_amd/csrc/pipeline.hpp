@@ -78,9 +78,11 @@ struct Operator {
   int fft_ndims = 0;                    // OP_FFT_COV / OP_FFT_COV_AT: the grid as the caller gave it (axes of one point included)
   int64_t fft_N[3] = {1, 1, 1};
   // OP_FFT_COV_AT (m x m, one rank): A = W C W', C the grid operator whose plan is shared above, W the multilinear
-  // interpolation at m scattered points.  at = Backend::points_at_create's handle (owned): the points plan and its inverted
-  // index, resident for the operator's lifetime; at_info = what that call reported.
+  // interpolation at m scattered points.  at = Backend::points_at_create's handle: the points plan and its inverted index,
+  // resident; at_info = what that call reported.  at_ref owns it (own_points_at) and is shared with every operator that
+  // gsi_op_fft_at_like builds on this one's points: the plan lives until the last of them is destroyed, in whatever order.
   void* at = nullptr;
+  std::shared_ptr<void> at_ref;
   int64_t at_info[4] = {0, 0, 0, 0};
   // OP_FWD_COV (nobs x nobs, one rank): A = H C H', C the grid operator whose plan is shared above, H the sparse matrix of a
   // forward model (gsi_fwd, link 0) over the n = prod fft_N cells of that grid.  The model is shared with its gsi_fwd handle:
@@ -103,6 +105,8 @@ struct Operator {
 
 // A.plan = plan, owned by A.plan_ref: destroyed through the context's backend when the last holder lets go
 void own_fft_plan(Operator& A, void* plan);
+// A.at = at, owned by A.at_ref in the same way (Backend::points_at_destroy)
+void own_points_at(Operator& A, void* at);
 
 // block-row layout used whenever a caller does not supply one
 void default_shard(int64_t m, int nranks, int rank, int64_t* row0, int64_t* mloc);

@@ -54,4 +54,41 @@ GSI_PC_HD inline double kernel(const Params& p, double d2, bool same) {
   v *= p.sigma2;
   return same ? v + p.nugget : v;
 }
+// ---- derivatives of sigma2 k(r) with respect to the covariance parameters (gsi_op_fft_gridcov_deriv) ----
+// (the values of GSI_DPARAM_* in include/gsi_hip.h)
+enum { D_LOG_SIGMA2 = 0, D_LOG_ELL = 1, D_LOG_ELL0 = 2, D_LOG_ELL1 = 3, D_LOG_ELL2 = 4, D_THETA = 5, D_NUGGET = 6, NUM_DPARAMS = 7 };
+// The derivative profile g(r) = -k'(r) / r of the unit-variance kernel, at r2 = r^2: Gaussian k, exponential e^-r / r,
+// Matern 3/2 3 e^(-sqrt3 r), Matern 5/2 (5/3)(1 + sqrt5 r) e^(-sqrt5 r).  The exponential kernel has a cusp at r = 0: every
+// derivative below multiplies g by a factor that vanishes there, so g(0) is DEFINED as 0, by a select (never 0 * inf).
+GSI_PC_HD inline double dprofile(int kind, double r2) {
+  if (kind == GAUSSIAN) return exp_nonpos(-0.5 * r2);
+  const double r = sqrt(r2);
+  if (kind == EXPONENTIAL) {
+    const bool zero = !(r > 0.0);
+    const double e = exp_nonpos(-r) / (zero ? 1.0 : r);
+    return zero ? 0.0 : e;
+  }
+  if (kind == MATERN32) return 3.0 * exp_nonpos(-1.7320508075688772 * r);
+  const double a = 2.23606797749979 * r;
+  return (5.0 / 3.0) * (1.0 + a) * exp_nonpos(-a);
+}
+// d (sigma2 k(r)) / d param off the diagonal at the SCALED lag (u, v, w) = (u_a / ell_a), r^2 = u^2 + v^2 + w^2 (in rotated
+// 2-D: u, v along the rotated axes).  With q_a = (u_a / ell_a)^2:  log ell_a: sigma2 g q_a;  log ell (all axes): sigma2 g r^2;
+// theta: -sigma2 g u v rot, rot = ell1 / ell0 - ell0 / ell1;  log sigma2: sigma2 k;  nugget: 0 (its derivative is the identity,
+// which the plan adds to the spectrum as it adds the nugget itself).
+GSI_PC_HD inline double dkernel(int kind, int param, double sigma2, double u, double v, double w, double rot) {
+  const double q0 = u * u, q1 = v * v, q2 = w * w, r2 = q0 + q1 + q2;
+  if (param == D_NUGGET) return 0.0;
+  if (param == D_LOG_SIGMA2) {
+    Params p;
+    p.d = 3; p.kind = kind; p.inv_ell = 1.0; p.sigma2 = sigma2; p.nugget = 0.0;
+    return kernel(p, r2, false);
+  }
+  const double g = sigma2 * dprofile(kind, r2);
+  if (param == D_LOG_ELL) return g * r2;
+  if (param == D_LOG_ELL0) return g * q0;
+  if (param == D_LOG_ELL1) return g * q1;
+  if (param == D_LOG_ELL2) return g * q2;
+  return -(g * (u * v)) * rot;                      // D_THETA
+}
 }}  // namespace gsi::pointcov

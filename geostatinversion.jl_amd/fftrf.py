@@ -240,7 +240,7 @@ class FFTOperatorAt(Operator):
         return out
 
 
-def fft_operator_at(ctx, grid_op, points, *, box=None):
+def fft_operator_at(ctx, grid_op, points=None, *, box=None, like=None):
     """An FFT covariance operator read at scattered points (`gsi_op_fft_at`): A = W C W', m x m, with C the covariance of
     `grid_op` (from `fft_gridcov_operator` or `fft_powerlaw_operator`, 2 or 3 axes of at least 2 points) and W the
     interpolation matrix of `interpolate` at `points` (ndims x m) on that grid, spanned by the points' extrema or `box`.
@@ -248,9 +248,19 @@ def fft_operator_at(ctx, grid_op, points, *, box=None):
     noise; one product is a spread, a grid product and a gather, and the points plan stays in HBM.  One GPU only.
     The grid operator's `ell` is in grid spacings (see `steps` of the result; steps that differ per axis need per-axis
     `ell`).  A `nugget` on the grid operator is interpolated with everything else: noise at the points is the caller's R.
-    Usable wherever an `Operator` is: `randsvd`, `rangefinder`, `eig_nystrom`, `getxis_device`."""
+    Usable wherever an `Operator` is: `randsvd`, `rangefinder`, `eig_nystrom`, `getxis_device`.
+    `like`: an `FFTOperatorAt` of the same grid shape instead of `points` and `box` -- the new operator shares its points plan
+    and inverted index on the device (`gsi_op_fft_at_like`): nothing is planned or uploaded, and the product is bit-identical
+    to that of a freshly planned operator.  The operators may be closed in any order."""
     Ns = getattr(grid_op, "Ns", None)
     h = C.c_void_p()
+    if like is not None:
+        if points is not None or box is not None:
+            raise ValueError("like replaces points and box: pass one or the other")
+        L.check(ctx.lib.gsi_op_fft_at_like(ctx.h, C.byref(h), grid_op.h, like.h), ctx.lib)
+        return FFTOperatorAt(ctx, h, grid_op, like.Ns, like._P, like._B)
+    if points is None:
+        raise ValueError("fft_operator_at needs points or like")
     if Ns is None or len(Ns) not in (2, 3):
         # not an FFT grid operator of 2 or 3 axes: the library names the limit
         P = np.asfortranarray(np.asarray(points, dtype=np.float64))

@@ -337,8 +337,17 @@ def log_likelihood(op, y, noise=None, drift=None, restricted=True, precond=None,
     Z = _probe_matrix(op, precond, probes, seed)
     s = Z.shape[1]
     X, rep = solve_trace(op, np.column_stack([yv, G, Z]), s, diag=noise, precond=precond, tol=tol, maxiter=maxiter, qmax=qmax)
+    val, info, _ = _likelihood_value(yv, G, X, rep, s, precond, restricted, tol, "log_likelihood")
+    return (val, info) if return_info else val
+
+
+def _likelihood_value(yv, G, X, rep, s, precond, restricted, tol, who):
+    """The value and the report of `log_likelihood` from the solved columns: X (m x b host array, column-major) needs its
+    first 1 + p columns only.  One body for `log_likelihood` and `log_likelihood_grad`: the two values agree bit for bit.  Also
+    returns G'M^-1 G (p x p)."""
+    m, p = yv.size, G.shape[1]
     if (rep["relres"][:1 + p] > tol).any():
-        raise RuntimeError(f"log_likelihood: a data column did not reach tol = {tol:g} (largest relative residual "
+        raise RuntimeError(f"{who}: a data column did not reach tol = {tol:g} (largest relative residual "
                            f"{rep['relres'][:1 + p].max():.3e})")
     My, MG = X[:, 0], X[:, 1:1 + p]
     if p:
@@ -347,7 +356,7 @@ def log_likelihood(op, y, noise=None, drift=None, restricted=True, precond=None,
         xi = My - MG @ beta
         ld_gmg = float(np.linalg.slogdet(0.5 * (GMG + GMG.T))[1])
     else:
-        beta, xi, ld_gmg = np.zeros(0), My, 0.0
+        GMG, beta, xi, ld_gmg = np.zeros((0, 0)), np.zeros(0), My, 0.0
     quadform = float((yv - G @ beta) @ xi)
     ldP = precond.logdet if precond is not None else 0.0
     ld = ldP + float(np.mean(rep["quad"][-s:]))
@@ -355,11 +364,333 @@ def log_likelihood(op, y, noise=None, drift=None, restricted=True, precond=None,
         val = -0.5 * (quadform + ld + ld_gmg + (m - p) * np.log(2.0 * np.pi))
     else:
         val = -0.5 * (quadform + ld + m * np.log(2.0 * np.pi))
-    if not return_info:
-        return val
     info = _slq_report(rep, s, ldP)
     info.update({"xi": xi, "beta": beta, "quadform": quadform, "logdet": ld, "logdet_GMG": ld_gmg, "restricted": bool(restricted)})
-    return val, info
+    return val, info, GMG
+
+
+def mat_bilinear(L_, Y, R=None, dd=None, g=0):
+    """The bilinear reduction of the likelihood gradient on resident matrices (`gsi_mat_bilinear`):
+    with V = Y + dd .* R (`dd`: n host values, `R` a `DeviceMatrix`; both None: V = Y), returns `(gram, t)` with
+    gram[a, c] = sum_i L[i, a] V[i, c] for a, c < g and t[j - g] = sum_i L[i, j] V[i, j] for g <= j < b.  Every product is
+    rounded on its own, chunks of 2048 rows are summed in row order and then added in chunk order: the result is a pure
+    function of the operands' bits."""
+    ctx, lib = L_.ctx, L_.ctx.lib
+    b = L_.shape[1]
+    g = int(g)
+    d = None if dd is None else np.ascontiguousarray(np.asarray(dd, dtype=np.float64).reshape(-1))
+    if d is not None and d.shape != (L_.shape[0],):
+        raise ValueError(f"dd must hold one value per row, {L_.shape[0]}")
+    gram, t = np.zeros(max(g, 0) ** 2), np.zeros(max(b - g, 0))
+    L.check(lib.gsi_mat_bilinear(ctx.h, L_.h, Y.h, R.h if R is not None else None, L.dptr(d) if d is not None else None, g,
+                                 L.dptr(gram) if gram.size else None, L.dptr(t) if t.size else None), lib)
+    return gram.reshape((g, g), order="F"), t
+
+
+def op_bilinear_terms(dop, ddiag, X, g, Wz):
+    """One parameter's terms of the likelihood gradient (`gsi_op_bilinear_terms`): with dM = `dop` + diag(`ddiag`) (either may
+    be None), X the resident solution M^-1 [y, G, Z] and Wz = P^-1 Z resident, returns `(S, t)`: S = X0' dM X0 for the first
+    `g` columns X0 and t[i] = x_{g+i}' dM w_i.  R = [X0, Wz] and dop R are formed on the device."""
+    ctx, lib = X.ctx, X.ctx.lib
+    n, b = X.shape
+    g = int(g)
+    d = _diag_arg(ddiag, n)
+    gram, t = np.zeros(max(g, 0) ** 2), np.zeros(max(b - g, 0))
+    L.check(lib.gsi_op_bilinear_terms(ctx.h, dop.h if dop is not None else None, L.dptr(d) if d is not None else None, X.h, g,
+                                      Wz.h if Wz is not None else None, L.dptr(gram) if gram.size else None,
+                                      L.dptr(t) if t.size else None), lib)
+    return gram.reshape((g, g), order="F"), t
+
+
+def _probe_device(op, precond, probes, seed):
+    """`_probe_matrix`'s probes as a `DeviceMatrix` (the same bits), made on the device where `probes` is a count."""
+    ctx, n = op.ctx, op.shape[0]
+    if isinstance(probes, DeviceMatrix):
+        if probes.shape[0] != n or probes.shape[1] < 1:
+            raise ValueError(f"probes must have one row per row of the operator, {n}, and at least one column; got {probes.shape}")
+        return probes, False
+    if isinstance(probes, (int, np.integer)):
+        s = int(probes)
+        if s < 1:
+            raise ValueError("probes must be at least 1")
+        G2 = DeviceMatrix(ctx, n, s)
+        try:
+            G2.randn(int(seed) + 1)
+            if precond is None:
+                out, G2 = G2, None
+                return out, True
+            G1 = DeviceMatrix(ctx, precond.rank, s)
+            try:
+                G1.randn(int(seed))
+                return precond.sample(G1, G2), True
+            finally:
+                G1.close()
+        finally:
+            if G2 is not None:
+                G2.close()
+    return DeviceMatrix.from_host(ctx, _probe_matrix(op, precond, probes, seed)), True
+
+
+def log_likelihood_grad(op, dops, y, noise=None, dnoise=None, drift=None, restricted=True, precond=None, probes=16, seed=0,
+                        tol=1e-8, maxiter=None, qmax=512, return_info=False):
+    """`log_likelihood` and its gradient with respect to K covariance parameters, from the ONE traced solve the value needs
+    (DESIGN.md section 4.6n).  `dops`: a list of K operators dA/dtheta_k (e.g. from `fft_gridcov_derivative` through
+    `fft_operator_at` / `linear_data_operator`; an entry None is the zero operator), or None; `dnoise`: a list of K vectors
+    d noise / d theta_k (entries None: zero), or None; so d_k M = dops[k] + diag(dnoise[k]).  With X = M^-1 [y, G, Z],
+    c = [1; -beta] and W_z = P^-1 Z,
+        S_k = X0' (d_k M) X0,    t_ki = x_{1+p+i}' (d_k M) w_i    (E t_ki = tr(M^-1 d_k M)),
+        REML  dL/dtheta_k = -1/2 [mean_i t_ki - tr((G'M^-1 G)^-1 S_k[1:, 1:]) - c' S_k c]      (ML: without the middle term).
+    The solution X and the probes stay on the device: one `gsi_op_bilinear_terms` call per parameter, of which only
+    (1 + p)^2 + s numbers come back.  The value equals `log_likelihood` with the same arguments bit for bit.  Returns
+    `(value, grad)`; `return_info`: also a dict with `t` (K x s), `grad_stderr` (K: std(t_k) / (2 sqrt(s)), the standard error of
+    grad[k]; `stderr` stays that of the log-determinant), `S` (K matrices) and what `log_likelihood` reports.  One GPU only."""
+    op, _ = RMF._as_operator(op)
+    ctx, lib = op.ctx, op.ctx.lib
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    m = yv.size
+    if op.shape[0] != m:
+        raise ValueError(f"y must hold one value per row of the operator, {op.shape[0]}")
+    G = np.zeros((m, 0)) if drift is None else np.asarray(drift, dtype=np.float64).reshape(m, -1)
+    p = G.shape[1]
+    K = max(len(dops) if dops is not None else 0, len(dnoise) if dnoise is not None else 0)
+    dops = [None] * K if dops is None else list(dops)
+    dnoise = [None] * K if dnoise is None else list(dnoise)
+    if len(dops) != K or len(dnoise) != K:
+        raise ValueError("dops and dnoise must have one entry per parameter")
+    d = _diag_arg(noise, m)
+    maxit = 10 * m if maxiter is None else int(maxiter)
+    owned = []
+    try:
+        Zd, mine = _probe_device(op, precond, probes, seed)
+        if mine:
+            owned.append(Zd)
+        s = Zd.shape[1]
+        b = 1 + p + s
+        B = DeviceMatrix(ctx, m, b)
+        owned.append(B)
+        head = DeviceMatrix.from_host(ctx, np.column_stack([yv, G]))
+        owned.append(head)
+        L.check(lib.gsi_mat_copy_cols(ctx.h, B.h, 0, head.h, 0, 1 + p), lib)
+        L.check(lib.gsi_mat_copy_cols(ctx.h, B.h, 1 + p, Zd.h, 0, s), lib)
+        X = DeviceMatrix(ctx, m, b)
+        owned.append(X)
+        info7 = (C.c_int64 * 7)()
+        relres, iters, quad = np.zeros(b), np.zeros(b, dtype=np.int64), np.zeros(2 * b)
+        L.check(lib.gsi_op_solve_trace(ctx.h, op.h, L.dptr(d) if d is not None else None, precond.h if precond is not None else None,
+                                       B.h, X.h, s, int(qmax), float(tol), maxit, info7, L.dptr(relres),
+                                       iters.ctypes.data_as(C.POINTER(C.c_int64)), L.dptr(quad)), lib)
+        rep = {"products": int(info7[0]), "converged": int(info7[1]), "path": PATHS.get(int(info7[2]), int(info7[2])),
+               "breakdown": int(info7[3]), "breakdown_kind": int(info7[4]), "rank": int(info7[5]), "truncated": int(info7[6]),
+               "relres": relres, "iters": iters, "columns": b, "quad": quad[:b].copy(), "rho0": quad[b:].copy()}
+        # the 1 + p data and drift columns, into an array laid out as `solve_trace` lays out its whole solution
+        Xh = np.empty((m, b), order="F")
+        for c in range(1 + p):
+            L.check(lib.gsi_mat_download_col(ctx.h, X.h, c, L.dptr(Xh[:, c])), lib)
+        val, info, GMG = _likelihood_value(yv, G, Xh, rep, s, precond, restricted, tol, "log_likelihood_grad")
+        Wz = Zd
+        if precond is not None:
+            Wz = precond.apply(Zd)
+            owned.append(Wz)
+        cvec = np.concatenate([[1.0], -info["beta"]])
+        grad, T, S = np.zeros(K), np.zeros((K, s)), []
+        for k in range(K):
+            Sk, tk = op_bilinear_terms(dops[k], dnoise[k], X, 1 + p, Wz)
+            mid = float(np.trace(np.linalg.solve(GMG, Sk[1:, 1:]))) if (restricted and p) else 0.0
+            grad[k] = -0.5 * (float(np.mean(tk)) - mid - float(cvec @ Sk @ cvec))
+            T[k] = tk
+            S.append(Sk)
+    finally:
+        for h in owned:
+            h.close()
+    if not return_info:
+        return val, grad
+    info.update({"t": T, "S": S, "grad_stderr": (np.std(T, axis=1, ddof=1) / (2.0 * np.sqrt(s))) if s > 1 else np.full(K, np.nan)})
+    return val, grad, info
+
+
+COV_PARAMS = ("log_sigma2", "log_ell", "log_ell0", "log_ell1", "log_ell2", "theta", "nugget")
+
+
+class CovarianceFamily:
+    """`covariance_family`'s result: the covariance functions of `fft_gridcov_operator` on one grid, read on the grid, at
+    scattered points (`fft_operator_at`) or through a linear forward model (`linear_data_operator`), as a function of the
+    parameters.  `params`: a dict with `log_sigma2` (default 0), `log_ell` (all axes) and / or `log_ell0`, `log_ell1`,
+    `log_ell2` (added to `log_ell`), `theta` (default 0) and `nugget` (default 0); other keys (`log_noise`) are ignored here.
+    Operators made here are the caller's to `release`; the points plan of the first point operator is kept (and with it the
+    FFT plan of the grid operator it was made on) and shared by every later one until `close()`."""
+
+    def __init__(self, ctx, Ns, kind, points=None, box=None, model=None):
+        if points is not None and model is not None:
+            raise ValueError("a family reads the grid at points or through a model, not both")
+        self.ctx, self.Ns, self.kind = ctx, tuple(int(v) for v in Ns), kind
+        self.points, self.box, self.model = points, box, model
+        self._base = None                    # the FFTOperatorAt whose points plan the others share
+
+    def cov_args(self, params):
+        d = len(self.Ns)
+        le = float(params.get("log_ell", 0.0))
+        ell = [float(np.exp(le + float(params.get(f"log_ell{a}", 0.0)))) for a in range(d)]
+        return dict(kind=self.kind, ell=ell, theta=float(params.get("theta", 0.0)), sigma2=float(np.exp(params.get("log_sigma2", 0.0))))
+
+    def _wrap(self, gop):
+        try:
+            if self.points is not None:
+                if self._base is None:              # the one operator that plans and uploads the points
+                    self._base = FFTRF.fft_operator_at(self.ctx, gop, self.points, box=self.box)
+                return FFTRF.fft_operator_at(self.ctx, gop, like=self._base)
+            if self.model is not None:
+                from .pcga import linear_data_operator
+                return linear_data_operator(gop, self.model)
+            return gop
+        except Exception:
+            gop.close()
+            raise
+
+    def operator(self, params):
+        """The covariance operator at `params`."""
+        from .context import fft_gridcov_operator
+        return self._wrap(fft_gridcov_operator(self.ctx, self.Ns, nugget=float(params.get("nugget", 0.0)), **self.cov_args(params)))
+
+    def derivatives(self, params, wrt):
+        """The operators dA / d wrt[k] at `params`, one per name in `wrt` (`COV_PARAMS`); None for a name that is not a
+        covariance parameter (`log_noise`)."""
+        from .context import fft_gridcov_derivative
+        out = []
+        try:
+            for name in wrt:
+                out.append(self._wrap(fft_gridcov_derivative(self.ctx, self.Ns, name, **self.cov_args(params)))
+                           if name in COV_PARAMS else None)
+        except Exception:
+            for o in out:
+                self.release(o)
+            raise
+        return out
+
+    @staticmethod
+    def release(op):
+        """Close an operator of `operator` / `derivatives` and the grid operator under it."""
+        if op is None:
+            return
+        gop = getattr(op, "grid_op", None)
+        op.close()
+        if gop is not None:
+            gop.close()
+
+    def close(self):
+        if self._base is not None:
+            self._base.close()          # (its grid operator was released with the operator that was built beside it)
+            self._base = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def covariance_family(ctx, Ns, kind, *, points=None, box=None, model=None):
+    """The family of covariance operators `fit_covariance` searches: `fft_gridcov_operator(ctx, Ns, kind, ...)` itself, read
+    at `points` (ndims x m, with `box`) by `fft_operator_at`, or seen through `model` (a `LinearForwardModel`) by
+    `linear_data_operator`.  See `CovarianceFamily`."""
+    return CovarianceFamily(ctx, Ns, kind, points=points, box=box, model=model)
+
+
+def fit_covariance(family, params0, y, noise, drift=None, wrt=("log_sigma2", "log_ell"), restricted=True, precond=None, probes=16,
+                   seed=0, tol=1e-8, maxiter=50, gtol=1e-4, cg_maxiter=None, qmax=512, armijo=1e-4, max_backtracks=20):
+    """Maximise the (restricted) log-likelihood of `y` over the parameters named in `wrt` by BFGS on `log_likelihood_grad`
+    (DESIGN.md section 4.6n).  `family`: a `CovarianceFamily`; `params0`: its parameter dict at the start (the names not in
+    `wrt` stay fixed); `wrt`: names of `COV_PARAMS` and / or "log_noise", which scales the noise vector by exp(log_noise), so
+    that its derivative of M is diag(exp(log_noise) noise).  `probes` (a count: drawn once with `seed`; or a matrix), the seed
+    and `precond` stay the same at every evaluation, so the objective is one deterministic function.  BFGS in numpy with a
+    backtracking Armijo search (first step 1 after the first iteration, 1 / max(1, |g|) at the start).  Stops when
+    max|grad| <= `gtol` ("gtol"), after `maxiter` iterations ("maxiter"), or when the search finds no sufficient increase
+    within `max_backtracks` halvings ("linesearch").  Returns `(params, report)`: report["stop"], report["trace"] = one dict
+    (params, value, grad, stderr) per accepted point, report["evaluations"]."""
+    wrt = tuple(wrt)
+    for name in wrt:
+        if name not in COV_PARAMS and name != "log_noise":
+            raise ValueError(f"unknown parameter {name!r}")
+    base = dict(params0)
+    for name in wrt:
+        base.setdefault(name, 0.0)
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    nz = _diag_arg(noise, yv.size)
+    if nz is None:
+        if "log_noise" in wrt:
+            raise ValueError("log_noise needs a noise vector")
+        nz = np.zeros(yv.size)
+    state = {"evals": 0, "probes": probes}
+
+    def evaluate(x):
+        prm = dict(base)
+        prm.update({name: float(v) for name, v in zip(wrt, x)})
+        nv = nz * np.exp(float(prm.get("log_noise", 0.0)))
+        op = family.operator(prm)
+        dops = []
+        try:
+            dops = family.derivatives(prm, wrt)
+            if isinstance(state["probes"], (int, np.integer)):          # drawn once, then the same matrix at every evaluation
+                state["probes"] = _probe_matrix(op, precond, state["probes"], seed)
+            dn = [nv if name == "log_noise" else None for name in wrt]
+            val, grad, info = log_likelihood_grad(op, dops, yv, noise=nv, dnoise=dn, drift=drift, restricted=restricted,
+                                                  precond=precond, probes=state["probes"], seed=seed, tol=tol,
+                                                  maxiter=cg_maxiter, qmax=qmax, return_info=True)
+        finally:
+            for o in dops:
+                family.release(o)
+            family.release(op)
+        state["evals"] += 1
+        return prm, val, grad, info["grad_stderr"]
+
+    x0 = np.array([float(base[name]) for name in wrt])
+    prm, stop, trace = _bfgs_maximize(evaluate, x0, gtol, maxiter, armijo, max_backtracks)
+    return prm, {"stop": stop, "trace": trace, "evaluations": state["evals"], "wrt": wrt}
+
+
+def _bfgs_maximize(evaluate, x0, gtol=1e-4, maxiter=50, armijo=1e-4, max_backtracks=20):
+    """BFGS ascent with a backtracking Armijo search, in numpy.  `evaluate(x)` -> (params, value, grad, stderr); a point where
+    it raises `GsiError` or `RuntimeError`, or whose value is not finite, counts as a failed trial step.  Returns (params of
+    the last accepted point, "gtol" | "maxiter" | "linesearch", trace of accepted points)."""
+    x = np.asarray(x0, dtype=np.float64).copy()
+    prm, val, grad, se = evaluate(x)
+    trace = [{"params": prm, "value": val, "grad": np.array(grad, dtype=np.float64), "stderr": se}]
+    H = np.eye(x.size)
+    stop = "maxiter"
+    for it in range(int(maxiter)):
+        if np.max(np.abs(grad)) <= gtol:
+            break
+        direction = H @ grad                                   # ascent on the likelihood
+        if direction @ grad <= 0.0:
+            H = np.eye(x.size)
+            direction = np.array(grad, dtype=np.float64)
+        step = 1.0 if it > 0 else 1.0 / max(1.0, float(np.linalg.norm(grad)))
+        slope = float(direction @ grad)
+        found = False
+        for _ in range(int(max_backtracks) + 1):
+            xn = x + step * direction
+            try:
+                prm_n, val_n, grad_n, se_n = evaluate(xn)
+            except (L.GsiError, RuntimeError):
+                step *= 0.5                                    # outside the family's domain, or no convergence there
+                continue
+            if np.isfinite(val_n) and val_n >= val + armijo * step * slope:
+                found = True
+                break
+            step *= 0.5
+        if not found:
+            stop = "linesearch"
+            break
+        sk, yk = xn - x, -(np.asarray(grad_n) - grad)          # BFGS on f = -L
+        sy = float(sk @ yk)
+        if sy > 1e-12 * float(np.linalg.norm(sk) * np.linalg.norm(yk)):
+            rho = 1.0 / sy
+            I = np.eye(x.size)
+            H = (I - rho * np.outer(sk, yk)) @ H @ (I - rho * np.outer(yk, sk)) + rho * np.outer(sk, sk)
+        x, prm, val, grad, se = xn, prm_n, val_n, np.array(grad_n, dtype=np.float64), se_n
+        trace.append({"params": prm, "value": val, "grad": grad.copy(), "stderr": se})
+    if stop == "maxiter" and np.max(np.abs(grad)) <= gtol:
+        stop = "gtol"
+    return prm, stop, trace
 
 
 def _grid_product(at_op, G):
